@@ -17,11 +17,18 @@ through the package's public Python surface (the reference README's calls) and i
 region; the boundary hands over device pointers only (no PCIe term).  Every step renders the whole frame with fresh
 seeds; nothing is cached between steps.  (Since round 4 the interior term passes over the samples of pixels no ray can
 leave towards a triangle - a conservative coverage mask of the scene, built at scene creation; the value of such a sample is
-zero in the reference as well, the frame is checked against the CPU restatement in the run (`parity`), and
+zero in the reference as well, the frame is checked against the CPU restatement in a --full run (`parity`), and
 PSDR_NO_LIVE_MASK=1 switches the mask off: 7.21 instead of 7.08 ms.  The samples still count in `value`, as they do for the
 reference, which launches them.)
 
-Prints ONE JSON line (rank 0).  Extra objects (N = 1, rank 0; each can be switched off, none is inside the timed region):
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`) and
+nothing else.  --dump-outputs DIR then writes the last timed step's image and derivative as DIR/image.npy and DIR/derivative.npy (float32
+[pixels, 3], pixel = y W + x; a frame of more than DUMP_PIXELS pixels as a fixed, seeded sample of DUMP_PIXELS of them).  The seeds of every
+step are fixed, so the same arguments give the same inputs in every run.  With --full the line also carries the extra objects (N = 1, rank 0
+unless said otherwise; each can be switched off, none is inside the timed region):
+  scale_breakdown - (N > 1) per-rank render and all-reduce times of extra steps, both collective forms, the row-tile partition.
+  static_edges_skipped - the same workload with psdr_render_args.skip_static_edges (identical outputs).
+  live_pixels  - the interior term's live-pixel mask: its fraction of the frame, `value_traced` = the samples it traces per second.
   roofline     - the dominant kernel against the ceiling that binds it.  The scene is LDS / SGPR resident and the
                  compulsory HBM traffic is the two output images, so the bound is fp32 VALU issue: achieved =
                  SURVEY §8(d) flops (60 / node visit + 45 / triangle test + 250 / shaded hit, counted by the
@@ -30,12 +37,12 @@ Prints ONE JSON line (rank 0).  Extra objects (N = 1, rank 0; each can be switch
                  process, so they are read from the committed summary named in `counters_source` (null if absent).
   backward     - reverse mode on the same workload: ms per psdr_hip_render_d_bwd (adjoints of every triangle row, BSDF colour, emitter,
                  edge row: nothing filtered), all three terms and each alone, HIP events on the launch stream.
-  config5      - (default run only) the BVH path at BASELINE config 5's full size: ms per renderD, per-kernel HIP-event times, counted
+  config5      - (default configuration only) the BVH path at BASELINE config 5's full size: ms per renderD, per-kernel HIP-event times, counted
                  nodes / triangles per ray, the dominant kernel against the L2 ceiling (34.5 TB/s) with the HBM rate and L2 hit rate
                  of the committed rocprofv3 passes; `--config 5` makes it the headline workload instead.
   api          - (N = 1) through the public Python surface (tools/configure_timing.py): api_call_ms = renderD + forward_grad as a user calls them, configure_ms per kind
                  of change (nothing / a colour / moved vertices / the rebuild of rounds 1-4), step_ms = configure + renderD + backward; the same inside `config5`.
-  rccl         - PSDR_BENCH_FORCE_DIST=1 runs the N > 1 code path (process group with device_id, device-pointer all-reduce, teardown)
+  rccl         - (N > 1) the process group's backend and bytes.  PSDR_BENCH_FORCE_DIST=1 runs the N > 1 code path (process group with device_id, device-pointer all-reduce, teardown)
                  at whatever world size the launcher gives, also 1 (the preflight of tests/test_gpu_distributed.py).
   parity       - relative L2 of this run's GPU image / derivative against the oracle on the same shard and seeds.
   cpu_baseline - the CPU restatement (oracle/, test infrastructure), built -O3 -march=native on this host, 1 warm-up +
@@ -61,6 +68,7 @@ GUIDING = [2000, 5, 5, 32]     # config 5: preprocess_secondary_edges grid (tuto
 VALU_PEAK_TFLOPS = 157.3       # MI355X_MICROARCH.md: fp32 vector peak
 L2_PEAK_TBPS = 34.5            # MI355X_MICROARCH.md: aggregate L2 bandwidth (8 XCDs x 4 MiB)
 COUNTERS = os.path.join(ROOT, "profiles", "counters.json")      # written by tools/prof_summary.py from the rocprofv3 --pmc passes
+DUMP_PIXELS = 1 << 21          # --dump-outputs: at most 2^21 pixels x 3 channels x 2 arrays x 4 B = 48 MiB
 
 
 def readme_scene(psdr, res, spp):
@@ -156,7 +164,11 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--dry", action="store_true", help="check that --gpus N can run on this node (visible devices, launcher environment), print the verdict, render nothing")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline (the extra objects of the docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's image and derivative as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     import torch
@@ -255,6 +267,7 @@ def main():
         return full
 
     def step(i, single=None):
+        """one renderD of the whole frame with seeds i -> the [2, pixels, 3] buffer that holds its image and derivative"""
         if use_dist and rows_timed and single is None:
             return step_rows(i)
         # N > 1: the form psdr_jit_amd._render_terms uses - the interior term (disjoint pixels per rank, first to finish) goes into its own all_reduce, which RCCL's
@@ -271,6 +284,7 @@ def main():
             dist.all_reduce(edge[1], op=dist.ReduceOp.SUM)
             work.wait()
             buf[1] += edge[1]
+        return buf
 
     def sync():
         if use_dist:
@@ -282,7 +296,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        last = step(i)
     sync()
     dt = time.perf_counter() - t0
     if use_dist:
@@ -290,10 +304,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # (before the extras of --full, which launch into the same buffer)
+        got = last.cpu().numpy()
+        if npx > DUMP_PIXELS:
+            got = got[:, np.sort(np.random.default_rng(0).choice(npx, DUMP_PIXELS, replace=False))]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("image", got[0]), ("derivative", got[1])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
     # N > 1 (outside the timed region): what a step consists of on every rank - HIP events on the launch stream around the render and around the
     # all-reduce of three extra steps - so that a scaling curve can be attributed (a slow rank, a slow collective, or launch skew)
     breakdown = None
-    if use_dist:
+    if use_dist and args.full:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         acc = [0.0, 0.0]
         reps = 3
@@ -368,7 +390,7 @@ def main():
 
     if breakdown is not None:
         out["scale_breakdown"] = breakdown
-    if n == 1 and not args.no_static_skip:
+    if args.full and n == 1 and not args.no_static_skip:
         # psdr_render_args.skip_static_edges (ABI 14), what the Python surface asks for: a primary-edge sample on an edge that does not move under the installed tangent
         # adds exactly zero to the derivative image and is not traced - the same numbers reach the image and the derivative (tests/test_gpu_configs.py).  The headline above traces
         # every sample, as the reference does and as rounds 1-4 did.
@@ -381,21 +403,22 @@ def main():
         dt1 = time.perf_counter() - t1
         out["static_edges_skipped"] = {"ms_per_step": round(dt1 / args.steps * 1e3, 4), "value": round(samples_per_step / (dt1 / args.steps) / 1e6, 3),
                                        "note": "the same workload with psdr_render_args.skip_static_edges = 1: identical outputs, the primary-edge samples with a zero edge velocity not traced"}
-    try:        # the live-pixel mask of the timed scene (psdr_hip_scene_live_pixels): which part of the frame the interior term passes over
-        n_live = C.c_int64(0)
-        cabi.check(cabi.lib().psdr_hip_scene_live_pixels(C.c_void_p(handle), 0, None, C.byref(n_live)))
-        # `value` counts every sample the reference would launch; `value_traced` only the interior samples this build traces (live pixels x spp) - the
-        # like-for-like figure against builds without the mask (PSDR_NO_LIVE_MASK=1) and against rounds 1-3
-        out["traced_samples_per_step"] = int(n_live.value * spp)
-        out["value_traced"] = round(n_live.value * spp / (dt / args.steps) / 1e6, 3)
-        out["live_pixels"] = {"fraction": round(n_live.value / float(npx), 4),
-                              "note": "interior-term samples of the other pixels are provably zero and are passed over before seeding (they count in `value`, as for the reference, "
-                                      "which launches them); PSDR_NO_LIVE_MASK=1 renders them"}
-    except Exception as e:      # (never in the way of the line)
-        out["live_pixels"] = {"error": str(e)[:200]}
+    if args.full:
+        try:        # the live-pixel mask of the timed scene (psdr_hip_scene_live_pixels): which part of the frame the interior term passes over
+            n_live = C.c_int64(0)
+            cabi.check(cabi.lib().psdr_hip_scene_live_pixels(C.c_void_p(handle), 0, None, C.byref(n_live)))
+            # `value` counts every sample the reference would launch; `value_traced` only the interior samples this build traces (live pixels x spp) - the
+            # like-for-like figure against builds without the mask (PSDR_NO_LIVE_MASK=1) and against rounds 1-3
+            out["traced_samples_per_step"] = int(n_live.value * spp)
+            out["value_traced"] = round(n_live.value * spp / (dt / args.steps) / 1e6, 3)
+            out["live_pixels"] = {"fraction": round(n_live.value / float(npx), 4),
+                                  "note": "interior-term samples of the other pixels are provably zero and are passed over before seeding (they count in `value`, as for the reference, "
+                                          "which launches them); PSDR_NO_LIVE_MASK=1 renders them"}
+        except Exception as e:      # (never in the way of the line)
+            out["live_pixels"] = {"error": str(e)[:200]}
 
     counters = None
-    if os.path.exists(COUNTERS):
+    if args.full and os.path.exists(COUNTERS):
         try:
             counters = json.load(open(COUNTERS))
         except Exception:
@@ -455,7 +478,7 @@ def main():
         }
 
     # ---------------------------------------------------------------- roofline of the dominant kernel (rank 0, N = 1)
-    if rank == 0 and n == 1 and not args.no_roofline:
+    if args.full and rank == 0 and n == 1 and not args.no_roofline:
         per = per_kernel(launch, handle, buf, guiding, max(3 if cfg == 5 else 5, args.steps // 2))
         if cfg == 5:
             out["roofline"] = bvh_roofline(per, handle, "config5")
@@ -515,13 +538,13 @@ def main():
                             "nothing filtered" % (n_tri, nb_, ne_, n_sec, n_prim),
                 "timing": "HIP events on the launch stream around %d psdr_hip_render_d_bwd calls (fresh seeds), d loss / d image = 1" % reps}
 
-    if rank == 0 and n == 1 and not args.no_backward:
+    if args.full and rank == 0 and n == 1 and not args.no_backward:
         b = backward_leg(sc, handle, guiding, npx, max(3, args.steps // 4))
         b["forward_ms"] = round(ms_per_step, 4)
         out["backward"] = b
 
-    # ---------------------------------------------------------------- the BVH path at BASELINE config 5's size (default run only)
-    if rank == 0 and n == 1 and cfg == 3 and not args.no_config5 and not (args.res or args.spp):
+    # ---------------------------------------------------------------- the BVH path at BASELINE config 5's size (default configuration only)
+    if args.full and rank == 0 and n == 1 and cfg == 3 and not args.no_config5 and not (args.res or args.spp):
         import synth
         c5 = CONFIGS[5]
         sc5, leaf5 = synth.config5_scene(psdr, c5["res"], c5["spp"])
@@ -574,12 +597,12 @@ def main():
                 out["config5"]["api"] = {"error": repr(e)[:300]}
         del buf5, sc5
 
-    if use_dist:
+    if args.full and use_dist:
         out["rccl"] = {"backend": backend, "ranks": world, "all_reduce_bytes": int(buf.numel() * 4),
                        "note": "process group bound with device_id, one all_reduce(sum) of the device buffer per step, destroy_process_group at exit"}
 
     # ---------------------------------------------------------------- the oracle legs (rank 0, N = 1): parity + CPU baseline
-    if rank == 0 and n == 1 and not (args.no_cpu_baseline and args.no_parity):
+    if args.full and rank == 0 and n == 1 and not (args.no_cpu_baseline and args.no_parity):
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from oracle import oracle as orc
         import scenes                                    # the oracle's neutral description of the same README scene
@@ -645,7 +668,7 @@ def main():
             }
 
     # ---------------------------------------------------------------- the calls a user makes (rank 0, N = 1; last: these legs reconfigure the scene)
-    if rank == 0 and n == 1 and not args.no_api and cfg != 5:
+    if args.full and rank == 0 and n == 1 and not args.no_api and cfg != 5:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import configure_timing

@@ -4,7 +4,8 @@ from /root/reference by `make -C oracle ref` into oracle/_ref/libref_loaders.so 
 tutorials (tutorials/data/{cbox,mesh,envmap}; the product ships byte-identical copies under examples/data as inputs).
 
 The digests are DATA (outputs of the reference run here); tests/test_ref_loaders.py checks the product's readers against them on
-any box, and against the library itself where it exists.
+any box, and against the library itself where it exists.  It also writes tests/golden/ref_loaders_arrays.npz, the arrays the library
+returns (an OBJ's whole, a fixed, seeded sample of an EXR's texels), for the boxes where the library cannot be built.
 
     python tests/golden/make_ref_loader_vectors.py
 """
@@ -20,6 +21,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 DATA = os.path.join(ROOT, "examples", "data")
 REF_DATA = "/root/reference/tutorials/data"
+ARRAYS = os.path.join(HERE, "ref_loaders_arrays.npz")        # keys "<file>|<array>"
+EXR_SAMPLE = 16384                                           # texels of an EXR kept in ARRAYS (its digest covers the whole image)
+OBJ_ARRAYS = ("vertices", "faces", "texcoords", "face_uvs")
 
 
 class RefObj(C.Structure):
@@ -66,6 +70,23 @@ def digest(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
+def kept_arrays(L, rel, root=DATA):
+    """what ARRAYS keeps of `rel`: an OBJ's arrays whole (texcoords / face_uvs where the file has them), an EXR's RGB at a fixed, seeded
+    sample of its texels (`rgb_index`: texel = y W + x)"""
+    path = os.path.join(root, rel)
+    if rel.endswith(".exr"):
+        rgb = ref_exr(L, path)[:, :, :3].reshape(-1, 3)
+        idx = np.sort(np.random.default_rng(0).choice(rgb.shape[0], min(rgb.shape[0], EXR_SAMPLE), replace=False)).astype(np.int64)
+        return {"rgb_index": idx, "rgb_sample": rgb[idx]}
+    return {k: a for k, a in zip(OBJ_ARRAYS, ref_obj(L, path)) if a is not None}
+
+
+def load_kept(rel):
+    """ARRAYS' entries of `rel` -> {array name: array}"""
+    with np.load(ARRAYS) as z:
+        return {k.split("|")[1]: z[k] for k in z.files if k.split("|")[0] == rel}
+
+
 def data_files():
     out = []
     for sub in ("cbox", "mesh", "envmap"):
@@ -98,4 +119,5 @@ if __name__ == "__main__":
         # the shipped copy is the reference's file
         assert open(os.path.join(DATA, rel), "rb").read() == open(os.path.join(REF_DATA, rel), "rb").read(), rel
     json.dump(out, open(os.path.join(HERE, "ref_loaders.json"), "w"), indent=1, sort_keys=True)
+    np.savez_compressed(ARRAYS, **{"%s|%s" % (rel, k): a for rel in out for k, a in kept_arrays(L, rel).items()})
     print("wrote", len(out), "entries")

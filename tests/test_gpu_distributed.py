@@ -44,7 +44,7 @@ def test_bench_two_ranks_config4_strong_scaling_line():
     import torch
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a visible MI355X (no CPU fallback exists)")
-    r = _torchrun(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1"], {"PSDR_BENCH_BACKEND": "gloo"})
+    r = _torchrun(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], {"PSDR_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stdout[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-3000:]
@@ -88,7 +88,7 @@ def test_rccl_preflight_world_size_one():
     env.update({"PSDR_BENCH_FORCE_DIST": "1", "PSDR_BENCH_BACKEND": "nccl"})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), "bench.py", "--gpus", "1", "--config", "4", "--res", "256", "--spp", "8", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-parity", "--no-roofline", "--no-backward", "--no-config5"]
+           "--full", "--no-cpu-baseline", "--no-parity", "--no-roofline", "--no-backward", "--no-config5"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

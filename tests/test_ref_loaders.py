@@ -3,9 +3,10 @@ src/core/bitmap_loader.cpp:12-52 drives them, the host model's OBJ reader (csrc/
 tiny_obj_loader as src/shape/mesh.cpp:166-243 drives it - on all 12 data files of the reference's tutorials, bit for bit.
 
 Two legs: (1) against tests/golden/ref_loaders.json, digests of the reference readers' outputs generated in the build container
-by tests/golden/make_ref_loader_vectors.py (runs on any box); (2) where oracle/_ref/libref_loaders.so exists (built from
-/root/reference by `make -C oracle ref`, __graft_entry__.build() does it when the reference is present) against the library
-itself, array by array."""
+by tests/golden/make_ref_loader_vectors.py (runs on any box); (2) array by array against what the library returns: the library
+itself where oracle/_ref/libref_loaders.so exists (built from the reference sources by `make -C oracle ref`, __graft_entry__.build()
+does it where they are present), on every box against tests/golden/ref_loaders_arrays.npz, the arrays the same generator kept of
+it (an OBJ's whole, a fixed, seeded sample of the EXR's texels)."""
 import json
 import os
 import sys
@@ -65,17 +66,26 @@ def test_reader_matches_the_reference_digest(psdr, rel):
 
 
 def test_readers_match_the_reference_library(psdr):
-    L = gen.ref_lib()
-    if L is None:
-        pytest.skip("oracle/_ref/libref_loaders.so not built (needs /root/reference)")
+    L = gen.ref_lib()                                            # None where the reference sources are not on the box
     for rel in sorted(GOLD):
         path = os.path.join(gen.DATA, rel)
-        assert gen.describe(L, rel) == GOLD[rel], rel           # the fixture is what the library returns today
+        kept = gen.load_kept(rel)
+        if L is not None:
+            assert gen.describe(L, rel) == GOLD[rel], rel       # the fixtures are what the library returns today
+            now = gen.kept_arrays(L, rel)
+            assert sorted(now) == sorted(kept) and all(np.array_equal(now[k], kept[k]) for k in now), rel
         if rel.endswith(".exr"):
-            assert np.array_equal(product_exr(psdr, path), gen.ref_exr(L, path)[:, :, :3])
+            got = product_exr(psdr, path)
+            if L is not None:
+                assert np.array_equal(got, gen.ref_exr(L, path)[:, :, :3])
+            assert np.array_equal(got.reshape(-1, 3)[kept["rgb_index"]], kept["rgb_sample"]), rel
         else:
-            got, want = product_obj(psdr, path), gen.ref_obj(L, path)
-            for g, w in zip(got, want):
-                assert (g is None) == (w is None)
-                if g is not None:
-                    assert np.array_equal(g, w), rel
+            got = dict(zip(gen.OBJ_ARRAYS, product_obj(psdr, path)))
+            if L is not None:
+                for g, w in zip(got.values(), gen.ref_obj(L, path)):
+                    assert (g is None) == (w is None)
+                    if g is not None:
+                        assert np.array_equal(g, w), rel
+            assert sorted(k for k, g in got.items() if g is not None) == sorted(kept), rel
+            for k, w in kept.items():
+                assert np.array_equal(got[k], w), (rel, k)

@@ -16,7 +16,7 @@ OUT=$REPO/gpurun_out
 mkdir -p $OUT
 BENCH="python $REPO/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-parity --no-backward --no-config5 --no-api --no-static-skip"
 cd /tmp && export TMPDIR=/tmp
-python $REPO/bench.py > $OUT/bench_line.json 2> $OUT/bench_err.log
+python $REPO/bench.py --full > $OUT/bench_line.json 2> $OUT/bench_err.log
 rm -rf $OUT/prof_kt $OUT/prof_fetch $OUT/prof_write $OUT/prof_l2 $OUT/prof_sq $OUT/prof_sq2
 rocprofv3 --kernel-trace --stats -d $OUT/prof_kt -- $BENCH > $OUT/prof_kt.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/prof_fetch -- $BENCH > $OUT/prof_fetch.log 2>&1
