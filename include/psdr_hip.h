@@ -307,6 +307,23 @@ int psdr_hip_bvh_node_bytes(void);
  * {valid, mesh id (-1 = miss), t, J, p.xyz, n.xyz (geometric), sh_frame.s.xyz, .t.xyz, .n.xyz, wi.xyz (local), uv.xy} */
 #define PSDR_ITS_STRIDE 24
 int psdr_hip_ray_intersect(const psdr_hip_scene *scene, int32_t n, const float *o, const float *d, float *out, void *stream);
+/* Scene::ray_intersect<true> (reference src/scene/scene.cpp:774-797, ad = true, path_space = false; bound to Python as
+ * Scene.unit_ray_intersectAD, src/psdr.cpp:405): the record of the differentiable re-intersection of the hit triangle
+ * (ray_intersect_triangle<true>, include/psdr/utils.h:83-93), same layout as above, J = 1.  d_o[n*3], d_d[n*3]: tangents of the
+ * rays (NULL = zero); the triangle rows carry the scene's installed tangents.  out_d[n*24]: the record's forward tangent (NULL = not
+ * wanted).  out_hit[n]: the hit's slot in the device scene (-1 = miss), an opaque handle for the adjoint below, valid until the
+ * scene is updated again. */
+int psdr_hip_ray_intersect_ad(const psdr_hip_scene *scene, int32_t n, const float *o, const float *d,
+                              const float *d_o, const float *d_d,
+                              float *out, float *out_d, int32_t *out_hit, void *stream);
+/* The transpose of the record above (reference: drjit's backward through scene.cpp:774-797), from the slots it returned, without a
+ * traversal.  g_rec[n*24]: adjoint of the record (the valid / mesh / J words are ignored).  Writes g_o[n*3], g_d[n*3] (each may be
+ * NULL; zero for misses and all-zero rows of g_rec) and ADDS the triangle-row adjoints [p0 e1 e2 n0 n1 n2 face_normal] into
+ * g_triangles[n_triangles*22] (psdr_grads.g_triangles layout, original triangle order; face_area gets nothing; NULL = not wanted),
+ * only for the meshes with mesh_filter[mesh] != 0 (NULL = all).  Non-finite values add nothing. */
+int psdr_hip_ray_intersect_adj(const psdr_hip_scene *scene, int32_t n, const float *o, const float *d,
+                               const int32_t *hit, const float *g_rec, const uint8_t *mesh_filter,
+                               float *g_triangles, float *g_o, float *g_d, void *stream);
 /* closest hit for a batch of rays (device arrays o[n*3], d[n*3] -> tri[n], uv[n*2], t[n]); parity aid */
 int psdr_hip_trace(const psdr_hip_scene *scene, int32_t n, const float *o, const float *d,
                    int32_t *out_tri, float *out_uv, float *out_t, void *stream);

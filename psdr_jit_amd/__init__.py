@@ -668,6 +668,8 @@ def _configure(self, active_sensor=()):
     _sync_params(self)
     self._configure(list(active_sensor))
     self.__dict__["_psdr_active"] = list(active_sensor)
+    # (a record of unit_ray_intersectAD refers to the rows of one configuration: its backward() / forward_grad check this count)
+    self.__dict__["_psdr_config_count"] = self.__dict__.get("_psdr_config_count", 0) + 1
 
 
 Scene.add_Sensor = _add_Sensor
@@ -710,7 +712,18 @@ class IntersectionC:
         return self._valid
 
 
-IntersectionD = IntersectionC
+class IntersectionD:
+    """What Scene.unit_ray_intersectAD returns (reference intersection.h:24-60, Intersection<true>): t, p, n, sh_frame.s / .t / .n, wi and uv are
+    outputs of one autograd node (their grad_fn), attached to the rays' o / d and to the meshes' geometry leaves; shape, J (ones) and is_valid()
+    are detached."""
+
+    def __init__(self, outs, valid, shape, J):
+        self.t, self.p, self.n, s, t, n, self.wi, self.uv = outs
+        self.sh_frame = FrameC(s, t, n)
+        self._valid, self.shape, self.J = valid, shape, J
+
+    def is_valid(self):
+        return self._valid
 
 
 class InteractionC:
@@ -807,8 +820,8 @@ Mesh.valid_edge_indices = property(_get_valid_edge_indices, _set_valid_edge_indi
 
 
 def _unit_ray_intersect(self, ray, active=None):
-    """Scene.unit_ray_intersect (reference psdr.cpp:404, scene.cpp:809-...): closest hits of a batch of rays on the GPU.
-    The AD variant returns the same detached record (derivatives of intersections are taken inside renderD)."""
+    """Scene.unit_ray_intersect (reference psdr.cpp:404, scene.cpp:809-...): closest hits of a batch of rays on the GPU, a detached record.
+    The AD variant, whose members carry derivatives, is _unit_ray_intersect_ad below."""
     dev = _device()
     o = _torch.as_tensor(ray.o, dtype=_torch.float32).to(dev).reshape(-1, 3).contiguous()
     d = _torch.as_tensor(ray.d, dtype=_torch.float32).to(dev).reshape(-1, 3).contiguous()
@@ -822,6 +835,140 @@ def _unit_ray_intersect(self, ray, active=None):
     if active is not None:
         its._valid = its._valid & _torch.as_tensor(active, dtype=_torch.bool, device=dev).reshape(-1)
     return its
+
+
+_GEO_NAMES = ("vertex_positions", "to_world_left", "to_world", "to_world_right")
+# (first word, width) in the 24-float record of the outputs of _IntersectADFn, in IntersectionD's order: t, p, n, sh_frame.s / .t / .n, wi, uv
+_ITS_AD_OUT = ((2, 1), (4, 3), (7, 3), (10, 3), (13, 3), (16, 3), (19, 3), (22, 2))
+
+
+def _ray_f32(x, dev):
+    return x.detach().to(device=dev, dtype=_torch.float32).reshape(-1, 3).contiguous()
+
+
+def _its_columns(rec):
+    return tuple((rec[:, a] if w == 1 else rec[:, a:a + w]).clone() for a, w in _ITS_AD_OUT)
+
+
+class _IntersectADFn(_torch.autograd.Function):
+    """Autograd node of Scene.unit_ray_intersectAD.  forward = psdr_hip_ray_intersect_ad (record + hit slots); backward = psdr_hip_ray_intersect_adj
+    (adjoints of o, d and of the hit triangles' rows, from the saved slots) followed by the host chain rule from the rows to the meshes' leaves
+    (chain.native_geometry_grads, as renderD's backward)."""
+
+    @staticmethod
+    def forward(ctx, state, o_in, d_in, *leaf_tensors):
+        scene, dev = state["scene"], state["dev"]
+        o, d = _ray_f32(o_in, dev), _ray_f32(d_in, dev)
+        n = int(o.shape[0])
+        rec = _torch.zeros((n, 24), dtype=_torch.float32, device=dev)
+        hit = _torch.full((n,), -1, dtype=_torch.int32, device=dev)
+        if n:
+            _core._ray_intersect_ad(scene, n, o.data_ptr(), d.data_ptr(), 0, 0, rec.data_ptr(), 0, hit.data_ptr(), _stream_ptr())
+        state.update(o=o, d=d, hit=hit, rec=rec)
+        ctx.isect = state
+        return _its_columns(rec)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        from . import chain
+        st = ctx.isect
+        scene, dev = st["scene"], st["dev"]
+        if scene.__dict__.get("_psdr_config_count", 0) != st["config"]:
+            raise RuntimeError("unit_ray_intersectAD: the scene was configured again between the call and backward(); the record's triangle rows "
+                               "are gone - call unit_ray_intersectAD again after configure()")
+        o, d, hit = st["o"], st["d"], st["hit"]
+        n = int(o.shape[0])
+        g_rec = _torch.zeros((n, 24), dtype=_torch.float32, device=dev)
+        for (a, w), g in zip(_ITS_AD_OUT, grads):
+            if g is not None:
+                g_rec[:, a:a + w] = g.detach().to(dev, _torch.float32).reshape(n, w)
+        g_rec[~st["valid"]] = 0.0                                  # misses and inactive rays: no adjoint
+        needs = ctx.needs_input_grad
+        leaves = st["leaves"]
+        want_mesh = _np.zeros(max(1, scene.num_meshes), dtype=_np.uint8)
+        geo_wanted = []
+        for (obj, name, t), need in zip(leaves, needs[3:]):
+            if need:
+                want_mesh[_mesh_index(scene, obj)] = 1
+                geo_wanted.append((obj, name))
+        n_tris, n_sec = (int(x) for x in scene._snapshot_counts())
+        g_tri = _torch.zeros(n_tris * 22, dtype=_torch.float32, device=dev) if geo_wanted else None
+        g_o = _torch.zeros((n, 3), dtype=_torch.float32, device=dev) if needs[1] else None
+        g_d = _torch.zeros((n, 3), dtype=_torch.float32, device=dev) if needs[2] else None
+        mesh_filter = _torch.from_numpy(want_mesh).to(dev)
+        ptr = lambda x: x.data_ptr() if x is not None else 0
+        if n and (g_tri is not None or g_o is not None or g_d is not None):
+            _core._ray_intersect_adj(scene, n, o.data_ptr(), d.data_ptr(), hit.data_ptr(), g_rec.data_ptr(), mesh_filter.data_ptr(),
+                                     ptr(g_tri), ptr(g_o), ptr(g_d), _stream_ptr())
+        out = [None] * len(leaves)
+        if geo_wanted:
+            if "Sensor[0]" not in scene.param_map:
+                raise RuntimeError("unit_ray_intersectAD: the chain rule to the mesh parameters needs a configured scene with a sensor")
+            n_prim = int(_np.asarray(scene.param_map["Sensor[0]"]._primary_edge_ids()).reshape(-1, 3).shape[0])
+            geo = chain.native_geometry_grads(scene, 0, geo_wanted, g_tri.cpu().numpy(), _np.zeros(6 * n_sec, _np.float32),
+                                              _np.zeros(4 * n_prim, _np.float32), None)
+            for i, ((obj, name, t), need) in enumerate(zip(leaves, needs[3:])):
+                if need:
+                    out[i] = _torch.as_tensor(_np.ascontiguousarray(geo[(id(obj), name)])).reshape(t.shape).to(t.device, t.dtype)
+        o_in, d_in = st["o_in"], st["d_in"]
+        go = g_o.reshape(o_in.shape).to(o_in.device, o_in.dtype) if g_o is not None else None
+        gd = g_d.reshape(d_in.shape).to(d_in.device, d_in.dtype) if g_d is not None else None
+        return (None, go, gd) + tuple(out)
+
+
+def _unit_ray_intersect_ad(self, ray, active=None):
+    """Scene.unit_ray_intersectAD (reference psdr.cpp:405, scene.cpp:774-797 with ad = true, path_space = false): the closest hits of a batch
+    of rays, re-intersected differentiably with the hit triangles.  Returns an IntersectionD whose t, p, n, sh_frame, wi and uv carry
+    derivatives with respect to the rays' o and d (torch tensors on any device) and to the meshes' vertex_positions / to_world* leaves, in
+    reverse mode (backward()) and in forward mode (forward_grad(member, P)).  The primal values equal unit_ray_intersect's to float rounding.
+    Inactive rays and misses get zero derivatives; a configure() between this call and backward() is an error."""
+    dev = _device()
+    o_in = ray.o if isinstance(ray.o, _torch.Tensor) else _torch.as_tensor(_np.asarray(ray.o, dtype=_np.float32))
+    d_in = ray.d if isinstance(ray.d, _torch.Tensor) else _torch.as_tensor(_np.asarray(ray.d, dtype=_np.float32))
+    if o_in.numel() != d_in.numel() or o_in.numel() % 3 != 0:
+        raise RuntimeError("unit_ray_intersectAD: origins and directions differ in size")
+    leaves = [(obj, name, t) for (obj, name, t) in _leaves(self) if isinstance(obj, Mesh) and name in _GEO_NAMES]
+    state = {"scene": self, "dev": dev, "leaves": leaves, "o_in": o_in, "d_in": d_in, "active": self.__dict__.get("_psdr_active", []),
+             "config": self.__dict__.get("_psdr_config_count", 0)}
+    outs = _IntersectADFn.apply(state, o_in, d_in, *[t for (_, _, t) in leaves])
+    rec = state["rec"]
+    valid = rec[:, 0] > 0
+    if active is not None:
+        valid = valid & _torch.as_tensor(active, dtype=_torch.bool).to(dev).reshape(-1)
+    state["valid"] = valid
+    return IntersectionD(outs, valid, rec[:, 1].to(_torch.int32), rec[:, 3].clone())
+
+
+def _intersect_forward_grad(member, fn, param, direction):
+    """forward_grad on a member of an IntersectionD: the leaves' tangents d leaf / d param . direction installed in the scene, the rays' tangents
+    by the same double-backward trick, one psdr_hip_ray_intersect_ad launch with out_d, the scene restored"""
+    st = fn.isect
+    scene, dev = st["scene"], st["dev"]
+    if scene.__dict__.get("_psdr_config_count", 0) != st["config"]:
+        raise RuntimeError("forward_grad: the scene was configured again after unit_ray_intersectAD; call it again after configure()")
+    o_in, d_in = st["o_in"], st["d_in"]
+    tangents = _jvp_tangents(_leaves(scene), param, direction)
+    ray_t = _jvp_tangents([(None, "o", o_in), (None, "d", d_in)], param, direction)
+    as_dev = lambda a: _torch.as_tensor(_np.asarray(a, dtype=_np.float32)).to(dev).reshape(-1, 3).contiguous()
+    d_o = as_dev(ray_t[id(o_in)]) if id(o_in) in ray_t else None
+    d_d = as_dev(ray_t[id(d_in)]) if id(d_in) in ray_t else None
+    n = int(st["o"].shape[0])
+    rec = _torch.zeros((n, 24), dtype=_torch.float32, device=dev)
+    rec_d = _torch.zeros((n, 24), dtype=_torch.float32, device=dev)
+    hit = _torch.empty((n,), dtype=_torch.int32, device=dev)
+    if tangents:
+        _sync_params(scene, tangents)
+        scene._configure(st["active"])
+    try:
+        if n:
+            _core._ray_intersect_ad(scene, n, st["o"].data_ptr(), st["d"].data_ptr(), d_o.data_ptr() if d_o is not None else 0,
+                                    d_d.data_ptr() if d_d is not None else 0, rec.data_ptr(), rec_d.data_ptr(), hit.data_ptr(), _stream_ptr())
+    finally:
+        if tangents:
+            _sync_params(scene, None)
+            scene._configure(st["active"])
+    rec_d[~st["valid"]] = 0.0
+    return _its_columns(rec_d)[member.output_nr]
 
 
 class SensorDirectSample:
@@ -855,7 +1002,7 @@ def _sample_direct(self, p):
 
 PerspectiveCamera.sample_direct = _sample_direct
 Scene.unit_ray_intersect = _unit_ray_intersect
-Scene.unit_ray_intersectAD = _unit_ray_intersect
+Scene.unit_ray_intersectAD = _unit_ray_intersect_ad
 Scene.add_EnvironmentMap = _add_EnvironmentMap
 
 
@@ -1356,9 +1503,12 @@ def _renderD(self, scene, sensor_id=0, seed=-1, batch_pix=-1, terms=TERM_ALL):
 
 def forward_grad(img, param, direction=None):
     """d img / d param along `direction` (default: ones) — the torch spelling of
-    drjit.set_grad(P, 1); drjit.forward_to(img); drjit.grad(img) (reference README.md:102-104)."""
+    drjit.set_grad(P, 1); drjit.forward_to(img); drjit.grad(img) (reference README.md:102-104).
+    `img` may also be a member (t, p, n, sh_frame.s / .t / .n, wi, uv) of what Scene.unit_ray_intersectAD returned."""
     import weakref
     fn = img.grad_fn
+    if fn is not None and hasattr(fn, "isect"):
+        return _intersect_forward_grad(img, fn, param, direction)          # a member of Scene.unit_ray_intersectAD's record
     if fn is None or not hasattr(fn, "state"):
         raise RuntimeError("forward_grad: img does not come from renderD with differentiable scene parameters")
     st = fn.state

@@ -27,6 +27,7 @@
 #include "paths.h"
 #include "adjoint.h"
 #include "adjoint_mat.h"
+#include "isect_ad.h"
 
 using namespace psdr;
 
@@ -647,6 +648,133 @@ __global__ __launch_bounds__(kBlock) void k_intersect(const float4 *__restrict__
     }
 }
 
+// Scene::ray_intersect<true> for a batch of rays (Scene.unit_ray_intersectAD, reference psdr.cpp:405, scene.cpp:774-797): the record of
+// k_intersect from the differentiable re-intersection of the hit triangle (isect_ad.h), its forward tangent (rays' tangents d_o / d_d, NULL =
+// zero; triangle rows' tangents = the scene's installed tangent rows) when out_d is given, and the hit's slot (-1 = miss) for k_intersect_adj
+template <int LDS>
+__global__ __launch_bounds__(kBlock) void k_intersect_ad(const float4 *__restrict__ blob, const SceneTables T, int n, const float *__restrict__ o,
+                                                         const float *__restrict__ d, const float *__restrict__ d_o, const float *__restrict__ d_d,
+                                                         float *__restrict__ out, float *__restrict__ out_d, int *__restrict__ out_hit) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem[];
+    SceneView<LDS> S = make_view<LDS>(blob, T, smem);
+    for (long long i = (long long) blockIdx.x * kBlock + threadIdx.x; i < (long long) ((n + kBlock - 1) / kBlock) * kBlock; i += (long long) gridDim.x * kBlock) {
+        if (i < n) {
+            const Vec3f ro(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+            const Hit h = trace<LDS, false>(S, ro, rd);
+            float *q = out + 24 * i;
+            float *qd = out_d ? out_d + 24 * i : nullptr;
+            out_hit[i] = h.slot;
+            if (h.slot < 0) {
+                for (int k = 0; k < 24; ++k) q[k] = 0.f;
+                q[1] = -1.f;
+                if (qd) for (int k = 0; k < 24; ++k) qd[k] = 0.f;
+                continue;
+            }
+            const Vec3f to = d_o ? Vec3f(d_o[3 * i], d_o[3 * i + 1], d_o[3 * i + 2]) : Vec3f(0.f);
+            const Vec3f td = d_d ? Vec3f(d_d[3 * i], d_d[3 * i + 1], d_d[3 * i + 2]) : Vec3f(0.f);
+            IsectGeom<Dual> g;
+            IsectConst c;
+            isect_load<true, LDS>(S, h.slot, g, c);
+            IsectOut<Dual> r;
+            isect_ad_eval<Dual>(make_dual(ro, to), make_dual(rd, td), g, c, r);
+            const Dual rec[22] = {r.t, Dual(1.f), r.p.x, r.p.y, r.p.z, g.fn.x, g.fn.y, g.fn.z, r.fs.x, r.fs.y, r.fs.z, r.ft.x, r.ft.y, r.ft.z,
+                                  r.fn.x, r.fn.y, r.fn.z, r.wi.x, r.wi.y, r.wi.z, r.tu, r.tv};
+            q[0] = 1.f; q[1] = (float) c.mesh;
+            for (int k = 0; k < 22; ++k) q[2 + k] = rec[k].v;
+            if (qd) { qd[0] = 0.f; qd[1] = 0.f; for (int k = 0; k < 22; ++k) qd[2 + k] = rec[k].d; }
+        }
+    }
+}
+
+#ifndef PSDR_ISECT_ADJ_ROUNDS     // wave reductions per 64 rays before the lanes left over add their own rows (tools/time_intersect_ad.py, LABNOTES.md:
+#define PSDR_ISECT_ADJ_ROUNDS 16  // C3 camera rays 14.96 / 2.67 / 0.40 / 0.40 ms at 0 / 2 / 4 / 16 rounds, config-5 random rays 15.6 / 10.3 / 7.5 / 3.7 ms)
+#endif
+// The transpose of k_intersect_ad from the saved hit slots (no traversal): per ray the adjoints of o and d (plain stores), and the adjoints of
+// the hit triangle's row [p0 e1 e2 n0 n1 n2 face_normal] added into g_tri[orig * 22 + ...] (ORIGINAL triangle order, psdr_grads.g_triangles).
+// Camera-like batches put most rays of a wave on one or two triangles: per round the wave takes the row of its first pending lane, sums the
+// 21 components over the lanes that share it (butterfly shuffles) and one lane adds them; after `rounds` rounds the lanes still pending (a
+// wave of incoherent rays: little contention) add their rows with one atomic per component.  rounds = 0: per-lane atomics only.
+template <int LDS>
+__global__ __launch_bounds__(kBlock) void k_intersect_adj(const float4 *__restrict__ blob, const SceneTables T, int n, const float *__restrict__ o,
+                                                          const float *__restrict__ d, const int *__restrict__ hit, const float *__restrict__ g_rec,
+                                                          const unsigned char *__restrict__ mesh_filter, float *__restrict__ g_tri,
+                                                          float *__restrict__ g_o, float *__restrict__ g_d, int rounds) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem[];
+    const float4 *B = blob;
+    if (in_lds(LDS)) {
+        for (int k = threadIdx.x; k < T.blob_words; k += kBlock) smem[k] = blob[k];
+        __syncthreads();
+        B = smem;
+    }
+    const int lane = threadIdx.x & 63;
+    for (long long i = (long long) blockIdx.x * kBlock + threadIdx.x; i < (long long) ((n + kBlock - 1) / kBlock) * kBlock; i += (long long) gridDim.x * kBlock) {
+        bool pend = false;
+        int row = -1;
+        float gt[kIsectRowComps];
+#pragma unroll
+        for (int k = 0; k < kIsectRowComps; ++k) gt[k] = 0.f;
+        if (i < n) {
+            const int slot = hit[i];
+            Vec3f go(0.f), gd(0.f);
+            if (slot >= 0 && slot < T.n_tris) {           // (a slot outside the scene's range is not loaded)
+                float gr[24];
+                bool any = false;
+#pragma unroll
+                for (int k = 0; k < 24; ++k) { gr[k] = g_rec[24 * i + k]; if (!finite_(gr[k])) gr[k] = 0.f; }
+#pragma unroll
+                for (int k = 2; k < 24; ++k) any = any || (k != 3 && gr[k] != 0.f);
+                if (any) {
+                    const int w = T.trav_off + 3 * slot, ws = T.shade_off + 6 * slot;
+                    const float4 a = B[w], b = B[w + 1], cc = B[w + 2];
+                    const float4 s0 = B[ws], s1 = B[ws + 1], s2 = B[ws + 2], s3 = B[ws + 3], s4 = B[ws + 4], s5 = B[ws + 5];
+                    IsectGeom<float> g;
+                    g.p0 = Vec3f(a.x, a.y, a.z); g.e1 = Vec3f(a.w, b.x, b.y); g.e2 = Vec3f(b.z, b.w, cc.x);
+                    g.n0 = Vec3f(s0.x, s0.y, s0.z); g.n1 = Vec3f(s1.x, s1.y, s1.z); g.n2 = Vec3f(s2.x, s2.y, s2.z); g.fn = Vec3f(s3.x, s3.y, s3.z);
+                    IsectConst c;
+                    c.uv[0] = s4.x; c.uv[1] = s4.y; c.uv[2] = s4.z; c.uv[3] = s4.w; c.uv[4] = s5.x; c.uv[5] = s5.y;
+                    c.flat = (__float_as_int(s2.w) & 1) != 0;
+                    c.mesh = __float_as_int(s1.w);
+                    isect_ad_adjoint(Vec3f(o[3 * i], o[3 * i + 1], o[3 * i + 2]), Vec3f(d[3 * i], d[3 * i + 1], d[3 * i + 2]), g, c, gr, gt, go, gd);
+                    if (!finite_(go.x)) go.x = 0.f;
+                    if (!finite_(go.y)) go.y = 0.f;
+                    if (!finite_(go.z)) go.z = 0.f;
+                    if (!finite_(gd.x)) gd.x = 0.f;
+                    if (!finite_(gd.y)) gd.y = 0.f;
+                    if (!finite_(gd.z)) gd.z = 0.f;
+                    const bool wanted = g_tri != nullptr && c.mesh >= 0 && c.mesh < T.n_meshes && (mesh_filter == nullptr || mesh_filter[c.mesh] != 0);
+                    row = __float_as_int(cc.y);                 // the original triangle id (k_trace)
+                    if (wanted && row >= 0 && row < T.n_tris) {
+                        pend = true;
+#pragma unroll
+                        for (int k = 0; k < kIsectRowComps; ++k) if (!finite_(gt[k])) gt[k] = 0.f;
+                    }
+                }
+            }
+            if (g_o) { g_o[3 * i] = go.x; g_o[3 * i + 1] = go.y; g_o[3 * i + 2] = go.z; }
+            if (g_d) { g_d[3 * i] = gd.x; g_d[3 * i + 1] = gd.y; g_d[3 * i + 2] = gd.z; }
+        }
+        // every lane of the wave is here (the loop runs over whole blocks): wave-wide reductions of the lanes that share a row
+        for (int r = 0; r < rounds; ++r) {
+            const unsigned long long m = __ballot(pend);
+            if (m == 0ull) break;
+            const int leader = __ffsll((long long) m) - 1;
+            const int lead_row = __builtin_amdgcn_readlane(row, leader);
+            const bool mine = pend && row == lead_row;
+#pragma unroll
+            for (int k = 0; k < kIsectRowComps; ++k) {
+                float x = mine ? gt[k] : 0.f;
+                for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+                if (lane == leader && x != 0.f && finite_(x)) atomicAdd(&g_tri[(long long) lead_row * 22 + k], x);
+            }
+            pend = pend && !mine;
+        }
+        if (pend) {
+#pragma unroll
+            for (int k = 0; k < kIsectRowComps; ++k) if (gt[k] != 0.f) atomicAdd(&g_tri[(long long) row * 22 + k], gt[k]);
+        }
+    }
+}
+
 // EnvironmentMap::sample_position / sample_position_pdf alone (parity aids)
 #ifndef PSDR_TU        // (plain kernels: the main unit only)
 __global__ void k_env_sample(const SceneTables T, int n, const float *__restrict__ ref_p, const float *__restrict__ s2,
@@ -1234,6 +1362,35 @@ int psdr_hip_ray_intersect(const psdr_hip_scene *sc, int32_t n, const float *o, 
     SCRATCH_GUARD(sc, stream);
     if (sc->lds) LAUNCH(1, (k_intersect<true>), sc, (long long) n, stream, sc->blob.as<float4>(), sc->T, n, o, d, out);
     else LAUNCH(0, (k_intersect<false>), sc, (long long) n, stream, sc->blob.as<float4>(), sc->T, n, o, d, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// Scene::ray_intersect<true, false> (reference src/scene/scene.cpp:774-797, Scene.unit_ray_intersectAD at src/psdr.cpp:405): isect_ad.h
+int psdr_hip_ray_intersect_ad(const psdr_hip_scene *sc, int32_t n, const float *o, const float *d, const float *d_o, const float *d_d,
+                              float *out, float *out_d, int32_t *out_hit, void *stream) {
+    if (!sc) return fail("null scene");
+    if (n <= 0) return 0;
+    if (!o || !d || !out || !out_hit) return fail("null ray / output buffer");
+    SCRATCH_GUARD(sc, stream);
+    if (sc->lds) LAUNCH(1, (k_intersect_ad<true>), sc, (long long) n, stream, sc->blob.as<float4>(), sc->T, n, o, d, d_o, d_d, out, out_d, out_hit);
+    else LAUNCH(0, (k_intersect_ad<false>), sc, (long long) n, stream, sc->blob.as<float4>(), sc->T, n, o, d, d_o, d_d, out, out_d, out_hit);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the transpose of psdr_hip_ray_intersect_ad (the reference gets it by drjit::backward through the same re-intersection)
+int psdr_hip_ray_intersect_adj(const psdr_hip_scene *sc, int32_t n, const float *o, const float *d, const int32_t *hit, const float *g_rec,
+                               const uint8_t *mesh_filter, float *g_triangles, float *g_o, float *g_d, void *stream) {
+    if (!sc) return fail("null scene");
+    if (n <= 0) return 0;
+    if (!o || !d || !hit || !g_rec) return fail("null ray / hit / adjoint buffer");
+    SCRATCH_GUARD(sc, stream);
+    // measurement knob, read per call: wave reductions per 64 rays before per-lane atomics (0 = per-lane atomics only)
+    int rounds = PSDR_ISECT_ADJ_ROUNDS;
+    if (const char *e = std::getenv("PSDR_ISECT_ADJ_ROUNDS")) rounds = std::max(0, std::min(64, std::atoi(e)));
+    if (sc->lds) hipLaunchKernelGGL((k_intersect_adj<true>), dim3(grid_for(sc, n)), dim3(kBlock), (size_t) sc->T.blob_words * 16, (hipStream_t) stream,
+                                    sc->blob.as<float4>(), sc->T, n, o, d, hit, g_rec, mesh_filter, g_triangles, g_o, g_d, rounds);
+    else hipLaunchKernelGGL((k_intersect_adj<false>), dim3(grid_for(sc, n)), dim3(kBlock), 0, (hipStream_t) stream,
+                            sc->blob.as<float4>(), sc->T, n, o, d, hit, g_rec, mesh_filter, g_triangles, g_o, g_d, rounds);
     HIPCHK(hipGetLastError());
     return 0;
 }

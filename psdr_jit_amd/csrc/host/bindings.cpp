@@ -536,6 +536,32 @@ PYBIND11_MODULE(_psdr_core, m) {
                                    reinterpret_cast<void *>(stream)))
             throw Exception(std::string("libpsdr_hip: ") + psdr_hip_last_error());
     });
+    // Scene::ray_intersect<true> (psdr_hip_ray_intersect_ad): record, its forward tangent (out_d = 0: none) and the hit slots
+    m.def("_ray_intersect_ad", [](const Scene &scene, int n, uintptr_t o, uintptr_t d, uintptr_t d_o, uintptr_t d_d, uintptr_t out, uintptr_t out_d,
+                                  uintptr_t out_hit, uintptr_t stream) {
+        if (!scene.is_ready()) throw Exception("Input scene must be configured!");
+        int rc;
+        {
+            py::gil_scoped_release rel;
+            rc = psdr_hip_ray_intersect_ad(scene.m_hip, n, reinterpret_cast<const float *>(o), reinterpret_cast<const float *>(d), reinterpret_cast<const float *>(d_o),
+                                           reinterpret_cast<const float *>(d_d), reinterpret_cast<float *>(out), reinterpret_cast<float *>(out_d),
+                                           reinterpret_cast<int32_t *>(out_hit), reinterpret_cast<void *>(stream));
+        }
+        if (rc) throw Exception(std::string("libpsdr_hip: ") + psdr_hip_last_error());
+    });
+    // its transpose (psdr_hip_ray_intersect_adj): g_o / g_d written, triangle-row adjoints added into g_triangles
+    m.def("_ray_intersect_adj", [](const Scene &scene, int n, uintptr_t o, uintptr_t d, uintptr_t hit, uintptr_t g_rec, uintptr_t mesh_filter, uintptr_t g_triangles,
+                                   uintptr_t g_o, uintptr_t g_d, uintptr_t stream) {
+        if (!scene.is_ready()) throw Exception("Input scene must be configured!");
+        int rc;
+        {
+            py::gil_scoped_release rel;
+            rc = psdr_hip_ray_intersect_adj(scene.m_hip, n, reinterpret_cast<const float *>(o), reinterpret_cast<const float *>(d), reinterpret_cast<const int32_t *>(hit),
+                                            reinterpret_cast<const float *>(g_rec), reinterpret_cast<const uint8_t *>(mesh_filter), reinterpret_cast<float *>(g_triangles),
+                                            reinterpret_cast<float *>(g_o), reinterpret_cast<float *>(g_d), reinterpret_cast<void *>(stream));
+        }
+        if (rc) throw Exception(std::string("libpsdr_hip: ") + psdr_hip_last_error());
+    });
 
     // (offsets[3*n_bsdfs], total) of psdr_hip_scene_tex_layout
     m.def("_tex_layout", [](const Scene &scene) {
