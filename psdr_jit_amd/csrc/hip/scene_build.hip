@@ -263,6 +263,8 @@ __global__ void k_geo_vnormal(const GeoMeshDev *__restrict__ M, const int *__res
 }
 
 __device__ inline float geo_ibits(int v) { return __int_as_float(v); }
+__device__ inline float4 geo_f4(float x, float y, float z, float w) { using psdr_host::canon_nan; return make_float4(canon_nan(x), canon_nan(y), canon_nan(z), canon_nan(w)); }
+__device__ inline float geo_c(float x) { return psdr_host::canon_nan(x); }
 
 __global__ void k_geo_rows(float4 *__restrict__ blob, SceneTables T, const GeoMeshDev *__restrict__ M, const int *__restrict__ fmesh, const int *__restrict__ faces,
                            const float *__restrict__ world, const float *__restrict__ fnrm, const float *__restrict__ farea, const float *__restrict__ vn, int nf, int values, int tangents) {
@@ -279,23 +281,23 @@ __global__ void k_geo_rows(float4 *__restrict__ blob, SceneTables T, const GeoMe
     const DF area = a2 * DF(0.5f);
     if (values) {
         float4 *t = blob + T.trav_off + 3 * (size_t) slot;
-        t[0] = make_float4(p0.x.v, p0.y.v, p0.z.v, e1.x.v);
-        t[1] = make_float4(e1.y.v, e1.z.v, e2.x.v, e2.y.v);
-        t[2] = make_float4(e2.z.v, geo_ibits(f), 0.f, 0.f);
+        t[0] = geo_f4(p0.x.v, p0.y.v, p0.z.v, e1.x.v);
+        t[1] = geo_f4(e1.y.v, e1.z.v, e2.x.v, e2.y.v);
+        t[2] = make_float4(geo_c(e2.z.v), geo_ibits(f), 0.f, 0.f);
         float4 *w = blob + T.shade_off + 6 * (size_t) slot;          // (words 4 and 5 - the uv of the three corners - do not depend on the vertices)
-        w[0] = make_float4(n0.x.v, n0.y.v, n0.z.v, area.v);
-        w[1] = make_float4(n1.x.v, n1.y.v, n1.z.v, geo_ibits(m.mesh_id));
-        w[2] = make_float4(n2.x.v, n2.y.v, n2.z.v, geo_ibits(m.flat ? 1 : 0));
-        w[3] = make_float4(fn.x.v, fn.y.v, fn.z.v, geo_ibits(f));
+        w[0] = geo_f4(n0.x.v, n0.y.v, n0.z.v, area.v);
+        w[1] = make_float4(geo_c(n1.x.v), geo_c(n1.y.v), geo_c(n1.z.v), geo_ibits(m.mesh_id));
+        w[2] = make_float4(geo_c(n2.x.v), geo_c(n2.y.v), geo_c(n2.z.v), geo_ibits(m.flat ? 1 : 0));
+        w[3] = make_float4(geo_c(fn.x.v), geo_c(fn.y.v), geo_c(fn.z.v), geo_ibits(f));
     }
     if (tangents && T.has_tangent) {
         float4 *w = blob + T.tan_off + 6 * (size_t) slot;
-        w[0] = make_float4(p0.x.d, p0.y.d, p0.z.d, e1.x.d);
-        w[1] = make_float4(e1.y.d, e1.z.d, e2.x.d, e2.y.d);
-        w[2] = make_float4(e2.z.d, n0.x.d, n0.y.d, n0.z.d);
-        w[3] = make_float4(n1.x.d, n1.y.d, n1.z.d, n2.x.d);
-        w[4] = make_float4(n2.y.d, n2.z.d, fn.x.d, fn.y.d);
-        w[5] = make_float4(fn.z.d, area.d, 0.f, 0.f);
+        w[0] = geo_f4(p0.x.d, p0.y.d, p0.z.d, e1.x.d);
+        w[1] = geo_f4(e1.y.d, e1.z.d, e2.x.d, e2.y.d);
+        w[2] = geo_f4(e2.z.d, n0.x.d, n0.y.d, n0.z.d);
+        w[3] = geo_f4(n1.x.d, n1.y.d, n1.z.d, n2.x.d);
+        w[4] = geo_f4(n2.y.d, n2.z.d, fn.x.d, fn.y.d);
+        w[5] = geo_f4(fn.z.d, area.d, 0.f, 0.f);
     }
 }
 
@@ -312,12 +314,34 @@ __global__ void k_geo_sec(float4 *__restrict__ blob, int sec_off, const GeoMeshD
     float n1[3] = {0.f, 0.f, 0.f};
     if (e[4] >= 0) { const D3 q = geo_ld(fnrm, (size_t) e[4]) / DF(farea[2 * (size_t) e[4]], farea[2 * (size_t) e[4] + 1]); n1[0] = q.x.v; n1[1] = q.y.v; n1[2] = q.z.v; }
     float4 *w = blob + sec_off + 6 * (size_t) r;
-    w[0] = make_float4(a.x.v, a.y.v, a.z.v, e1[0]);
-    w[1] = make_float4(e1[1], e1[2], n0.x.v, n0.y.v);
-    w[2] = make_float4(n0.z.v, n1[0], n1[1], n1[2]);
-    w[3] = make_float4(c.x.v, c.y.v, c.z.v, geo_ibits(e[4] < 0 ? 1 : 0));
-    w[4] = make_float4(a.x.d, a.y.d, a.z.d, de1[0]);
-    w[5] = make_float4(de1[1], de1[2], 0.f, 0.f);
+    w[0] = geo_f4(a.x.v, a.y.v, a.z.v, e1[0]);
+    w[1] = geo_f4(e1[1], e1[2], n0.x.v, n0.y.v);
+    w[2] = geo_f4(n0.z.v, n1[0], n1[1], n1[2]);
+    w[3] = make_float4(geo_c(c.x.v), geo_c(c.y.v), geo_c(c.z.v), geo_ibits(e[4] < 0 ? 1 : 0));
+    w[4] = geo_f4(a.x.d, a.y.d, a.z.d, de1[0]);
+    w[5] = geo_f4(de1[1], de1[2], 0.f, 0.f);
+}
+
+// The topology lists of one mesh, checked before anything is filled or uploaded: the kernels above index the world vertices, face normals and areas with these
+// ids unchecked, so one bad id is an out-of-bounds device read.  -> 1 (fail() with the list named) on the first violation.
+static int validate_geometry(const psdr_mesh_geometry &g, int mesh) {
+    const int nv = g.n_vertices, nf = g.n_faces;
+    auto bad = [&](const char *what) { return fail("psdr_mesh_geometry[" + std::to_string(mesh) + "]: " + what); };
+    if (nv < 0 || nf < 0 || g.n_edges < 0) return bad("negative count");
+    for (size_t i = 0; i < 3 * (size_t) nf; ++i)
+        if (g.faces[i] < 0 || g.faces[i] >= nv) return bad("faces: vertex id outside the mesh's vertices");
+    if (g.vf_begin[0] != 0) return bad("vf_begin[0] is not 0");
+    for (int v = 0; v < nv; ++v)
+        if (g.vf_begin[v + 1] < g.vf_begin[v]) return bad("vf_begin decreases");
+    if ((size_t) g.vf_begin[nv] != 3 * (size_t) nf) return bad("vf_begin[n_vertices] is not 3 * n_faces");
+    for (size_t k = 0; k < 3 * (size_t) nf; ++k)
+        if (g.vf_item[k] < 0 || (g.vf_item[k] >> 2) >= nf) return bad("vf_item: face id outside the mesh's faces");
+    for (size_t e = 0; e < (size_t) g.n_edges; ++e) {
+        const int32_t *q = g.edges + 5 * e;            // v0 v1 f0 f1 opp
+        if (q[0] < 0 || q[0] >= nv || q[1] < 0 || q[1] >= nv || q[4] < 0 || q[4] >= nv) return bad("edges: v0 / v1 / opp outside the mesh's vertices");
+        if (q[2] < 0 || q[2] >= nf || q[3] < -1 || q[3] >= nf) return bad("edges: f0 / f1 outside the mesh's faces (f1 = -1: boundary)");
+    }
+    return 0;
 }
 
 // uploads what the kernels need (topology when a mesh's version changed, raw vertices and transforms of the moved meshes) and runs them; -> 1 on error.
@@ -339,6 +363,10 @@ static int geometry_on_device(psdr_hip_scene *sc, const psdr_scene_snapshot *s, 
     for (int i = 0; same_topo && i < nm; ++i)
         same_topo = sc->geo_versions[(size_t) i] == G[i].topology_version && sc->geo_counts[3 * (size_t) i] == G[i].n_vertices && sc->geo_counts[3 * (size_t) i + 1] == G[i].n_faces &&
                     sc->geo_counts[3 * (size_t) i + 2] == G[i].n_edges;
+    // (the lists are read only when the topology travels; a kept topology was checked when it did)
+    if (!same_topo)
+        for (int i = 0; i < nm; ++i)
+            if (validate_geometry(G[i], i)) return 1;
     std::vector<GeoMeshDev> mt((size_t) nm);
     {
         size_t vo = 0, fo = 0, eo = 0;
@@ -365,11 +393,7 @@ static int geometry_on_device(psdr_hip_scene *sc, const psdr_scene_snapshot *s, 
             for (int v = 0; v < m.n_v; ++v) vmesh[(size_t) m.v_off + (size_t) v] = i;
             for (int f = 0; f < m.n_f; ++f) {
                 fmesh[(size_t) m.f_off + (size_t) f] = i;
-                for (int c = 0; c < 3; ++c) {
-                    const int vi = G[i].faces[3 * (size_t) f + c];
-                    if (vi < 0 || vi >= m.n_v) return fail("psdr_mesh_geometry: face index outside the mesh's vertices");
-                    faces[3 * ((size_t) m.f_off + (size_t) f) + c] = m.v_off + vi;
-                }
+                for (int c = 0; c < 3; ++c) faces[3 * ((size_t) m.f_off + (size_t) f) + c] = m.v_off + G[i].faces[3 * (size_t) f + c];
             }
             // (vf_begin of a mesh counts from 0; items are (local face << 2 | corner): both move to the global numbering)
             for (int v = 0; v < m.n_v; ++v) {
@@ -382,7 +406,6 @@ static int geometry_on_device(psdr_hip_scene *sc, const psdr_scene_snapshot *s, 
                 d[0] = m.v_off + q[0]; d[1] = m.v_off + q[1]; d[2] = m.v_off + q[4]; d[3] = m.f_off + q[2]; d[4] = q[3] >= 0 ? m.f_off + q[3] : -1; d[5] = i;
             }
         }
-        if (k != 3 * NF) return fail("psdr_mesh_geometry: vf lists do not cover the faces");
         if (up("geo.faces", faces.data(), faces.size() * 4) || up("geo.vmesh", vmesh.data(), vmesh.size() * 4) || up("geo.fmesh", fmesh.data(), fmesh.size() * 4) ||
             up("geo.vf_begin", vfb.data(), vfb.size() * 4) || up("geo.vf_item", vfi.data(), vfi.size() * 4) || up("geo.edges", edges.data(), edges.size() * 4)) return 1;
         if (up("geo.raw", nullptr, 12 * NV) || up("geo.d_raw", nullptr, 12 * NV) || up("geo.world", nullptr, 24 * NV) || up("geo.vn", nullptr, 24 * NV) ||

@@ -430,6 +430,39 @@ PYBIND11_MODULE(_psdr_core, m) {
         .def("_snapshot_counts", [](const Scene &s) { return py::make_tuple((int64_t) s.snap.area.size(), (int64_t) s.snap.n_sec_edges); })
         .def("_hip_handle", [](const Scene &s) { return (uintptr_t) s.m_hip; })
         .def("_check_device_rows", &Scene::check_device_rows)
+        // test aid: psdr_hip_scene_update with this state's snapshot, except that psdr_mesh_geometry[mesh] carries a new topology version, raw vertices scaled by 2
+        // (rows computed from them differ from the snapshot's) and ONE list broken as `fault` names -> (return code, psdr_hip_last_error()).  The scene object's
+        // own bookkeeping is untouched: a failed update poisons the device handle, and the next configure() sends everything again
+        .def("_update_with_malformed_geometry", [](Scene &s, int mesh, const std::string &fault) {
+            if (s.m_hip == nullptr) throw Exception("configure() first");
+            psdr_scene_snapshot sn;
+            s.fill_snapshot(sn, true);
+            if (!sn.geometry || mesh < 0 || mesh >= sn.n_meshes) throw Exception("no psdr_mesh_geometry for this mesh");
+            std::vector<psdr_mesh_geometry> G(sn.geometry, sn.geometry + sn.n_meshes);
+            psdr_mesh_geometry &g = G[(size_t) mesh];
+            const int nv = g.n_vertices, nf = g.n_faces;
+            std::vector<int32_t> faces(g.faces, g.faces + 3 * (size_t) nf), vfb(g.vf_begin, g.vf_begin + nv + 1), vfi(g.vf_item, g.vf_item + 3 * (size_t) nf);
+            std::vector<int32_t> edges(g.edges, g.edges + (g.edges ? 5 * (size_t) g.n_edges : 0));
+            std::vector<float> raw(g.vertices_raw, g.vertices_raw + 3 * (size_t) nv);
+            for (float &x : raw) x *= 2.f;
+            if (fault == "faces") faces[0] = nv;
+            else if (fault == "vf_begin[0]") vfb[0] = 1;
+            else if (fault == "vf_begin order") vfb[1] = -1;
+            else if (fault == "vf_begin end") vfb[(size_t) nv] = 3 * nf + 3;
+            else if (fault == "vf_item") vfi[0] = nf << 2;
+            else if (fault.rfind("edges.", 0) == 0 && !edges.empty()) {
+                static const char *cols[5] = {"v0", "v1", "f0", "f1", "opp"};
+                int c = -1;
+                for (int k = 0; k < 5; ++k) if (fault == std::string("edges.") + cols[k]) c = k;
+                if (c < 0) throw Exception("unknown fault " + fault);
+                edges[(size_t) c] = c == 2 || c == 3 ? nf : nv;
+            } else throw Exception("unknown fault " + fault);
+            g.faces = faces.data(); g.vf_begin = vfb.data(); g.vf_item = vfi.data(); g.edges = edges.empty() ? nullptr : edges.data(); g.vertices_raw = raw.data();
+            g.topology_version = ~g.topology_version; g.moved = 1;
+            sn.geometry = G.data();
+            psdr_update_info info{};
+            const int rc = psdr_hip_scene_update(s.m_hip, &sn, 0u, &info);
+            return py::make_tuple(rc, std::string(rc ? psdr_hip_last_error() : "")); })
         // what the last configure() did to the device copy (psdr_update_info, include/psdr_hip.h)
         .def("_last_update", [](const Scene &s) {
             py::dict d;

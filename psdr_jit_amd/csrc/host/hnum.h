@@ -34,6 +34,10 @@ PSDR_HNUM_HD inline DF operator/(DF a, DF b) { float q = a.v / b.v; return {q, (
 PSDR_HNUM_HD inline DF dfma(DF a, DF b, DF c) { return {std::fmaf(a.v, b.v, c.v), a.d * b.v + a.v * b.d + c.d}; }
 PSDR_HNUM_HD inline DF dsqrt(DF a) { float s = std::sqrt(a.v); return {s, a.d / (2.f * s)}; }
 PSDR_HNUM_HD inline DF drcp(DF a) { return DF(1.f) / a; }
+// Every float a row holds goes through this: 0/0 - the unit normal of a zero-area face, the vertex normal of a vertex whose faces all have zero
+// area, their tangents - is NaN on both sides, but x86 writes the default NaN with the sign bit set and the GPU a positive one.  Written as the one positive quiet
+// NaN, the rows hold the same bits whichever side computed them.
+PSDR_HNUM_HD inline float canon_nan(float x) { return x != x ? __builtin_nanf("") : x; }
 
 struct D3 { DF x, y, z; };
 PSDR_HNUM_HD inline D3 operator+(D3 a, D3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }

@@ -275,8 +275,8 @@ static void process_mesh(const std::vector<D3> &V, const std::vector<int> &F, in
     }
     tri.resize(22 * (size_t) nf); d_tri.resize(22 * (size_t) nf);
     auto put = [&](size_t row, int col, const D3 &a) {
-        tri[22 * row + col] = a.x.v; tri[22 * row + col + 1] = a.y.v; tri[22 * row + col + 2] = a.z.v;
-        d_tri[22 * row + col] = a.x.d; d_tri[22 * row + col + 1] = a.y.d; d_tri[22 * row + col + 2] = a.z.d;
+        tri[22 * row + col] = canon_nan(a.x.v); tri[22 * row + col + 1] = canon_nan(a.y.v); tri[22 * row + col + 2] = canon_nan(a.z.v);
+        d_tri[22 * row + col] = canon_nan(a.x.d); d_tri[22 * row + col + 1] = canon_nan(a.y.d); d_tri[22 * row + col + 2] = canon_nan(a.z.d);
     };
     psdr::parallel_for((size_t) nf, 4096, [&](size_t b, size_t e) {
         for (size_t f = b; f < e; ++f) {
@@ -285,7 +285,7 @@ static void process_mesh(const std::vector<D3> &V, const std::vector<int> &F, in
             put(f, 9, vn[F[3 * f]]); put(f, 12, vn[F[3 * f + 1]]); put(f, 15, vn[F[3 * f + 2]]);
             put(f, 18, fnrm[f] / farea[f]);
             const DF a = farea[f] * DF(0.5f);
-            tri[22 * f + 21] = a.v; d_tri[22 * f + 21] = a.d;
+            tri[22 * f + 21] = canon_nan(a.v); d_tri[22 * f + 21] = canon_nan(a.d);
         }
     });
 }
@@ -342,7 +342,7 @@ void Mesh::configure() {
                 const float n[3] = {std::fmaf(e1[1], e2[2], -(e1[2] * e2[1])), std::fmaf(e1[2], e2[0], -(e1[0] * e2[2])), std::fmaf(e1[0], e2[1], -(e1[1] * e2[0]))};
                 const float a2 = std::sqrt(std::fmaf(n[2], n[2], std::fmaf(n[1], n[1], n[0] * n[0])));
                 float *o = &face_p0n[6 * f];
-                o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = n[0] / a2; o[4] = n[1] / a2; o[5] = n[2] / a2;
+                o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = canon_nan(n[0] / a2); o[4] = canon_nan(n[1] / a2); o[5] = canon_nan(n[2] / a2);
                 areas[f] = a2 * 0.5f;
             }
         });
@@ -1090,9 +1090,9 @@ void Scene::fill_sec_rows() {
             const MeshEdge &e = mesh->edges[i];
             const size_t r = base + i;
             for (int k = 0; k < 3; ++k) {
-                S.se_e1[3 * r + k] = P[3 * e.v1 + k] - P[3 * e.v0 + k]; S.se_d_e1[3 * r + k] = dP[3 * e.v1 + k] - dP[3 * e.v0 + k];
-                S.se_p0[3 * r + k] = P[3 * e.v0 + k]; S.se_d_p0[3 * r + k] = dP[3 * e.v0 + k];
-                S.se_p2[3 * r + k] = P[3 * e.opp + k];
+                S.se_e1[3 * r + k] = canon_nan(P[3 * e.v1 + k] - P[3 * e.v0 + k]); S.se_d_e1[3 * r + k] = canon_nan(dP[3 * e.v1 + k] - dP[3 * e.v0 + k]);
+                S.se_p0[3 * r + k] = canon_nan(P[3 * e.v0 + k]); S.se_d_p0[3 * r + k] = canon_nan(dP[3 * e.v0 + k]);
+                S.se_p2[3 * r + k] = canon_nan(P[3 * e.opp + k]);
                 S.se_n0[3 * r + k] = mesh->face_p0n[6 * (size_t) e.f0 + 3 + k];
                 S.se_n1[3 * r + k] = e.f1 >= 0 ? mesh->face_p0n[6 * (size_t) e.f1 + 3 + k] : 0.f;
             }
