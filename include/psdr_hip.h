@@ -29,6 +29,8 @@
 extern "C" {
 #endif
 
+/* (psdr_hip_render_d_fwd_batch / psdr_hip_render_d_bwd_batch were ADDED under version 16: no struct changed its layout and no existing entry point its behaviour,
+ * so every ABI-16 caller stays valid; a caller that wants the two functions looks the symbols up) */
 #define PSDR_HIP_ABI_VERSION 16
 
 /* TriangleInfo SoA, reference include/psdr/types.h:162-175 (+ Scene::m_triangle_uv,
@@ -213,7 +215,8 @@ typedef struct psdr_render_args {
     int32_t max_depth;            /* PathTracer(max_depth) */
     int32_t hide_emitters;        /* PathTracer::m_hide_emitters */
     psdr_sampler samplers[3];     /* interior / primary edge / secondary edge */
-    const int32_t *pix_ids;       /* DEVICE pointer, batch_pix (integrator.cpp:139-176); NULL = full frame */
+    const int32_t *pix_ids;       /* DEVICE pointer, batch_pix (integrator.cpp:139-176); NULL = full frame.  psdr_hip_render_d_fwd / _bwd: interior term only;
+                                     psdr_hip_render_d_fwd_batch / _bwd_batch: interior term + the edge terms of the listed pixels */
     int32_t n_pix;
     int32_t terms;                /* PSDR_TERM_* mask (renderD only) */
     int32_t shard_rank, shard_count;  /* multi-GPU: rank r of c evaluates the PSDR_SHARD_CHUNK-lane chunks k of each
@@ -352,11 +355,21 @@ int psdr_hip_render_c(const psdr_hip_scene *scene, const psdr_render_args *args,
 /* Integrator::renderD + forward derivative: out_rgb = image, out_drgb = d image / d theta */
 int psdr_hip_render_d_fwd(const psdr_hip_scene *scene, const psdr_render_args *args,
                           float *out_rgb, float *out_drgb, void *stream);
+/* Batch rendering WITH the edge terms (what Integrator::renderD means to do for a pixel list, integrator.cpp:68-90, where it seeds samplers 1 and 2 with the
+ * full-frame counts and calls render_primary_edges / render_secondary_edges - and then scatters at the full-frame pixel index into a result of n_pix rows,
+ * integrator.cpp:195).  Requires args->pix_ids (n_pix full-frame pixel ids, duplicates allowed, any order).  Row k of out_drgb = the interior derivative of row k,
+ * as psdr_hip_render_d_fwd gives it for the same list, PLUS the full-frame primary- and secondary-edge derivative of pixel pix_ids[k]: the edge samplers run over the
+ * full-frame lane counts (W*H*sppe, W*H*sppse; args->samplers[1..2], guiding, shard_rank / shard_count / shard_mode exactly as in the full-frame call with the same
+ * arguments), and a sample whose pixel is not listed is dropped BEFORE its rays are traced - the primary-edge sample at sampling time, the secondary-edge sample once
+ * the hit of its opposite ray has been projected to the sensor.  A pixel listed twice receives its edge share in both rows.  args->terms selects the terms as in
+ * psdr_hip_render_d_fwd (0 = all three).  The shards of such a call add up to the unsharded call, as those of the full frame do. */
+int psdr_hip_render_d_fwd_batch(const psdr_hip_scene *scene, const psdr_render_args *args,
+                                float *out_rgb, float *out_drgb, void *stream);
 /* Reverse mode of renderD (the reference's drjit.backward through Integrator::renderD, README.md:102-106):
  * given d_rgb = d loss / d image ([n_pixels*3], device), accumulate the adjoints of the snapshot quantities
  * the image depends on.  All buffers are DEVICE pointers owned by the caller; rows follow the snapshot order.
  * The host chains them to vertices / transforms / colours / camera pose.  With args->pix_ids (batch rendering) d_rgb is
- * [n_pix*3] and only the interior term exists, as in the forward path.  g_bsdf / g_mat / psdr_hip_scene_tex_layout rows cover
+ * [n_pix*3] and only the interior term exists, as in the forward path (psdr_hip_render_d_bwd_batch has the edge terms too).  g_bsdf / g_mat / psdr_hip_scene_tex_layout rows cover
  * every entry of psdr_scene_snapshot.bsdfs, including the records nested in normal maps. */
 typedef struct psdr_grads {
     float *g_triangles;    /* [n_triangles*22] rows [p0 e1 e2 n0 n1 n2 face_normal face_area] */
@@ -401,6 +414,10 @@ typedef struct psdr_grads {
 int psdr_hip_scene_tex_layout(const psdr_hip_scene *scene, int64_t *offsets, int64_t *total);
 int psdr_hip_render_d_bwd(const psdr_hip_scene *scene, const psdr_render_args *args, const float *d_rgb,
                           const psdr_grads *grads, void *stream);
+/* the transpose of psdr_hip_render_d_fwd_batch (requires args->pix_ids; d_rgb is [n_pix*3]): the adjoint an edge sample on pixel p sees is the sum of d_rgb over the
+ * rows k with pix_ids[k] == p; samples on pixels that are not listed are not traced */
+int psdr_hip_render_d_bwd_batch(const psdr_hip_scene *scene, const psdr_render_args *args, const float *d_rgb,
+                                const psdr_grads *grads, void *stream);
 /* same kernels with traversal counters enabled (slower; counters is a HOST struct, call synchronises) */
 int psdr_hip_render_c_counted(const psdr_hip_scene *scene, const psdr_render_args *args, float *out_rgb,
                               psdr_counters *counters, void *stream);

@@ -1173,8 +1173,21 @@ def _render_terms(render, n, dev, world, terms, split_ok=True, tile=0):
     return buf[0], buf[1] + edge[1]
 
 
-def _render_d_raw(self, scene, sensor_id, seed, batch_pix, terms, distributed=None):
+def _batch_edges_checked(batch_edges, batch_pix):
+    batch_edges = bool(batch_edges)
+    if batch_edges and (batch_pix is None or (isinstance(batch_pix, int) and batch_pix == -1)):
+        raise ValueError("batch_edges=True needs batch_pix: a full-frame renderD always has its edge terms")
+    return batch_edges
+
+
+def _batch_kw(batch_edges):
+    """the keyword travels to _render_d_raw only when it is on: a call without it is the call it has always been"""
+    return {"batch_edges": True} if batch_edges else {}
+
+
+def _render_d_raw(self, scene, sensor_id, seed, batch_pix, terms, distributed=None, batch_edges=False):
     dev = _device()
+    batch_edges = _batch_edges_checked(batch_edges, batch_pix)
     pix = _pix(batch_pix, dev)
     n = int(pix.numel()) if pix is not None else scene.opts.width * scene.opts.height
     rank, world = _shard() if distributed in (None, True) else (0, 1)
@@ -1183,7 +1196,8 @@ def _render_d_raw(self, scene, sensor_id, seed, batch_pix, terms, distributed=No
     tile = _row_tile(n, scene.opts.width, world, pix is not None) if self._shard_mode == 1 else 0
 
     def render(launch_terms, continue_streams, image, derivative):
-        self._renderD(scene, sensor_id, -1 if continue_streams else seed, pp, n, image.data_ptr(), derivative.data_ptr(), _stream_ptr(), rank, world, launch_terms)
+        self._renderD(scene, sensor_id, -1 if continue_streams else seed, pp, n, image.data_ptr(), derivative.data_ptr(), _stream_ptr(), rank, world, launch_terms, batch_edges)
+    # (a pixel list on several ranks: one all_reduce of the whole buffer in both shard modes - with batch_edges the edge rows of every rank are partial sums)
     return _render_terms(render, n, dev, world, terms, split_ok=pix is None, tile=tile)
 
 
@@ -1328,7 +1342,8 @@ class _RenderDFn(_torch.autograd.Function):
                             g_env.data_ptr() if g_env is not None else 0, g_env_scale.data_ptr() if g_env_scale is not None else 0,
                             g_mat.data_ptr() if g_mat is not None else 0, g_env_xf.data_ptr() if g_env_xf is not None else 0,
                             bpix.data_ptr() if bpix is not None else 0, int(bpix.numel()) if bpix is not None else 0,
-                            g_uv.data_ptr() if g_uv is not None else 0, prim_filter.data_ptr() if prim_filter is not None else 0)
+                            g_uv.data_ptr() if g_uv is not None else 0, prim_filter.data_ptr() if prim_filter is not None else 0,
+                            bool(st.get("batch_edges", False)) and bpix is not None)
         _all_reduce(flat, world > 1)
         for extra in (g_env, g_env_scale, g_mat, g_env_xf, g_uv):
             if extra is not None:
@@ -1435,7 +1450,7 @@ def _replay_forward(integ, scene, st, tangents):
     after = [scene._sampler_state(k) for k in range(3)]
     for k, s in enumerate(st["samplers"]):
         scene._set_sampler_state(k, *s)
-    _, dimg = _render_d_raw(integ, scene, st["sensor_id"], st["seed"], st["batch_pix"], _derivative_terms(st["terms"], st["leaves"], tangents))
+    _, dimg = _render_d_raw(integ, scene, st["sensor_id"], st["seed"], st["batch_pix"], _derivative_terms(st["terms"], st["leaves"], tangents), **_batch_kw(st.get("batch_edges", False)))
     for k, s in enumerate(after):
         scene._set_sampler_state(k, *s)
     return dimg
@@ -1462,15 +1477,21 @@ def _jvp_tangents(leaves, param, direction=None):
     return tangents
 
 
-def _renderD(self, scene, sensor_id=0, seed=-1, batch_pix=-1, terms=TERM_ALL):
+def _renderD(self, scene, sensor_id=0, seed=-1, batch_pix=-1, terms=TERM_ALL, batch_edges=False):
     """Integrator.renderD (reference integrator.cpp:51-100).  Returns the image as a tensor attached
-    to the autograd graph of the scene's torch parameters."""
+    to the autograd graph of the scene's torch parameters.
+
+    batch_pix: a list of full-frame pixel ids (duplicates allowed, any order) - the image has one row per entry.  Its derivative has the interior term only,
+    unless batch_edges=True: then row k also carries the full-frame primary- and secondary-edge derivative of pixel batch_pix[k] (the edge samplers run
+    over the whole frame with the same seed; the samples that land on a pixel outside the list are dropped before their rays are traced), in
+    forward_grad and in backward() alike."""
     import weakref
+    batch_edges = _batch_edges_checked(batch_edges, batch_pix)
     leaves = _leaves(scene, self)
     for _name, _t in self.__dict__.get("_psdr_params", {}).items():       # the integrator's own tensor parameters (m_intensity)
         _v = _t.detach().to("cpu", _torch.float32).numpy().reshape(-1)
         self._set(_name, _v, _zeros_like(_v))
-    state = {"integrator": self, "scene": scene, "sensor_id": sensor_id, "batch_pix": batch_pix, "terms": terms,
+    state = {"integrator": self, "scene": scene, "sensor_id": sensor_id, "batch_pix": batch_pix, "terms": terms, "batch_edges": batch_edges,
              "active": scene.__dict__.get("_psdr_active", []), "leaves": leaves, "seed": seed,
              "samplers": [scene._sampler_state(k) for k in range(3)]}      # the streams this call starts from
     tens = [t for (_, _, t) in leaves]
@@ -1489,15 +1510,15 @@ def _renderD(self, scene, sensor_id=0, seed=-1, batch_pix=-1, terms=TERM_ALL):
             if tangents:
                 _sync_params(scene, tangents, self)
                 scene._configure(state["active"])
-                img, dimg = _render_d_raw(self, scene, sensor_id, seed, batch_pix, _derivative_terms(terms, leaves, tangents))
+                img, dimg = _render_d_raw(self, scene, sensor_id, seed, batch_pix, _derivative_terms(terms, leaves, tangents), **_batch_kw(batch_edges))
                 _sync_params(scene, None, self)
                 scene._configure(state["active"])
                 state["img"], state["dimg"], state["dimg_param"] = img, dimg, weakref.ref(param)
                 return _RenderDFn.apply(state, *tens)
-        img, _ = _render_d_raw(self, scene, sensor_id, seed, batch_pix, (terms & TERM_INTERIOR) | ((terms & 7) << 4))
+        img, _ = _render_d_raw(self, scene, sensor_id, seed, batch_pix, (terms & TERM_INTERIOR) | ((terms & 7) << 4), **_batch_kw(batch_edges))
         state["img"] = img
         return _RenderDFn.apply(state, *tens)
-    img, dimg = _render_d_raw(self, scene, sensor_id, seed, batch_pix, terms)
+    img, dimg = _render_d_raw(self, scene, sensor_id, seed, batch_pix, terms, **_batch_kw(batch_edges))
     return img
 
 
@@ -1537,10 +1558,12 @@ for _cls in (FieldExtractionIntegrator, CollocatedIntegrator):
 CollocatedIntegrator.m_intensity = _make_param_property("m_intensity", lambda self, value: (1,))
 
 
-def render_d_fwd(integrator, scene, sensor_id=0, seed=-1, batch_pix=-1, terms=TERM_ALL, tangents=None):
+def render_d_fwd(integrator, scene, sensor_id=0, seed=-1, batch_pix=-1, terms=TERM_ALL, tangents=None, batch_edges=False):
     """One-shot renderD + forward derivative: returns (img, d_img).  `tangents` maps scene leaf tensors
-    (by identity) to their tangent arrays; host objects whose tangents were set through `_set` keep them."""
+    (by identity) to their tangent arrays; host objects whose tangents were set through `_set` keep them.
+    batch_edges: with batch_pix, add the edge terms of the listed pixels (see Integrator.renderD)."""
+    batch_edges = _batch_edges_checked(batch_edges, batch_pix)
     if tangents is not None:
         _sync_params(scene, {id(k): v for k, v in tangents.items()})
         scene._configure(scene.__dict__.get("_psdr_active", []))
-    return _render_d_raw(integrator, scene, sensor_id, seed, batch_pix, terms)
+    return _render_d_raw(integrator, scene, sensor_id, seed, batch_pix, terms, **_batch_kw(batch_edges))

@@ -795,6 +795,39 @@ __global__ void k_env_pdf(const SceneTables T, int n, const float *__restrict__ 
                                   Vec3f(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]));
 }
 
+// Batch rendering with edge terms (psdr_hip_render_d_fwd_batch / _bwd_batch).  The edge samples of a renderD are spread over the WHOLE frame; the ones whose pixel is in
+// the list are kept.  slot_of[full-frame pixel] = the smallest k with pix_ids[k] == pixel (unsigned atomicMin over a table preset to ~0u = -1: deterministic with
+// duplicates), -1 = not listed: SceneTables::slot_of, read by the edge kernels where a sample's pixel becomes known.  Kept samples add into (forward) / read their adjoint
+// from (reverse) a buffer of n_pix rows indexed by that representative slot; the two kernels below carry it to and from the caller's rows, duplicates included.
+__global__ void k_batch_slots(const int *__restrict__ pix_ids, int n_pix, int n_full, int *__restrict__ slot_of) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_pix) return;
+    const int p = pix_ids[k];
+    if (p >= 0 && p < n_full) atomicMin(reinterpret_cast<unsigned *>(slot_of) + p, (unsigned) k);
+}
+// forward: row k += the edge share of pixel pix_ids[k]
+__global__ void k_batch_gather(const int *__restrict__ pix_ids, int n_pix, int n_full, const int *__restrict__ slot_of, const float *__restrict__ rows, float *__restrict__ dout) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_pix) return;
+    const int p = pix_ids[k];
+    if (p < 0 || p >= n_full) return;
+    const int s = slot_of[p];
+    if (s < 0 || s >= n_pix) return;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { const float v = rows[3 * (long long) s + c]; if (v != 0.f) dout[3 * (long long) k + c] += v; }
+}
+// reverse: the adjoint an edge sample on pixel p sees = the sum of d_rgb over the rows k with pix_ids[k] == p, kept at p's representative slot
+__global__ void k_batch_reduce(const int *__restrict__ pix_ids, int n_pix, int n_full, const int *__restrict__ slot_of, const float *__restrict__ d_rgb, float *__restrict__ rows) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_pix) return;
+    const int p = pix_ids[k];
+    if (p < 0 || p >= n_full) return;
+    const int s = slot_of[p];
+    if (s < 0 || s >= n_pix) return;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { const float v = d_rgb[3 * (long long) k + c]; if (v != 0.f) atomicAdd(&rows[3 * (long long) s + c], v); }
+}
+
 __global__ void k_sampler_floats(unsigned long long seed_value, unsigned long long lane, unsigned long long skip, int n, float *out) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         LaneRng r; r.seed(seed_value, lane, skip_ahead(skip));        // (the kernels' form of the skip-ahead: sampler.h)
@@ -961,10 +994,29 @@ static int check_args(const psdr_hip_scene *sc, const psdr_render_args *a) {
     return 0;
 }
 
+// batch rendering with edge terms: builds the pixel -> slot map of this call's list in the scene's scratch (k_batch_slots) and clears the n_pix edge rows
+static int batch_edge_scratch(const psdr_hip_scene *sc, const psdr_render_args *a, hipStream_t st, int *&slot_of, float *&rows) {
+    const size_t n_full = (size_t) sc->T.width * sc->T.height;
+    const size_t map_bytes = sizeof(int) * n_full, row_bytes = sizeof(float) * 3 * (size_t) a->n_pix;
+    if (n_full >= (1ull << 31)) return fail("batch rendering with edge terms: frame too large");
+    if (sc->batch_map.bytes < map_bytes || sc->batch_rows.bytes < row_bytes) {
+        // (every earlier user of the scratch was ordered before this stream by the guard: its completion is this stream's)
+        HIPCHK(hipStreamSynchronize(st));
+        if (sc->batch_map.bytes < map_bytes && sc->batch_map.ensure(map_bytes)) return 1;
+        if (sc->batch_rows.bytes < row_bytes && sc->batch_rows.ensure(row_bytes)) return 1;
+    }
+    slot_of = (int *) sc->batch_map.p; rows = (float *) sc->batch_rows.p;
+    HIPCHK(hipMemsetAsync(slot_of, 0xff, map_bytes, st));
+    HIPCHK(hipMemsetAsync(rows, 0, row_bytes, st));
+    hipLaunchKernelGGL(k_batch_slots, dim3((a->n_pix + 255) / 256), dim3(256), 0, st, a->pix_ids, a->n_pix, (int) n_full, slot_of);
+    return 0;
+}
+
 template <bool COUNT>
 static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool ad, float *out, float *dout, float *lanes_out,
-                       long long lane_b, long long lane_e, psdr_counters *counters, void *stream) {
+                       long long lane_b, long long lane_e, psdr_counters *counters, void *stream, bool batch_edges = false) {
     if (check_args(sc, a)) return 1;
+    if (batch_edges && !a->pix_ids) return fail("psdr_hip_render_d_fwd_batch needs args->pix_ids (the full frame has its edge terms in psdr_hip_render_d_fwd)");
     SCRATCH_GUARD(sc, stream);
     const SceneTables &T = sc->T;
     hipStream_t st = (hipStream_t) stream;
@@ -1036,11 +1088,20 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
             }
         }
     }
-    if (ad && !a->pix_ids && !lanes_out) {
-        if ((terms & PSDR_TERM_PRIMARY) && T.sppe > 0 && cam.n_edges > 0) {
+    if (ad && (!a->pix_ids || batch_edges) && !lanes_out) {
+        // the edge samplers run over the FULL frame, with or without a pixel list (integrator.cpp:68-90)
+        const long long npx_e = (long long) T.width * T.height;
+        const bool want_prim = (terms & PSDR_TERM_PRIMARY) && T.sppe > 0 && cam.n_edges > 0, want_sec = (terms & PSDR_TERM_SECONDARY) && T.sppse > 0 && sc->E.n > 0;
+        float *edge_out = dout;
+        int *slot_of = nullptr;
+        if (batch_edges && (want_prim || want_sec)) {
+            if (batch_edge_scratch(sc, a, st, slot_of, edge_out)) return 1;
+            T_prim.slot_of = slot_of; T_sec.slot_of = slot_of;
+        }
+        if (want_prim) {
             PathParams P{};
             P.max_depth = fh_field >= 0 ? 0 : (a->direct_mode > 0 ? 1 : a->max_depth); P.mis = a->direct_mode - 1; P.field = fh_field; P.field_object = a->field_object; P.intensity = a->intensity; P.d_intensity = a->d_intensity; P.hide_emitters = a->hide_emitters; P.seed = a->samplers[1].seed; P.skip = skip_ahead(a->samplers[1].skip);
-            set_shard(P, a, npx * T.sppe, kBlock, rank, count); P.dout = dout;
+            set_shard(P, a, npx_e * T.sppe, kBlock, rank, count); P.dout = edge_out;
             P.skip_static = a->skip_static_edges;
             if (P.n_local > 0) {
                 if (fork) P.counter = q_prim; else if (next_queue(P.counter)) return 1;
@@ -1050,10 +1111,10 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
                 else ON_CLS0(LAUNCH(0, (k_paths<false, 0, COUNT, 1>), sc, P.n_local, s_prim, sc->blob.as<float4>(), T_prim, cam, P, ctr));
             }
         }
-        if ((terms & PSDR_TERM_SECONDARY) && T.sppse > 0 && sc->E.n > 0) {
+        if (want_sec) {
             PathParams P{};
             P.max_depth = fh_field >= 0 ? 0 : (a->direct_mode > 0 ? 1 : a->max_depth); P.mis = a->direct_mode - 1; P.field = fh_field; P.field_object = a->field_object; P.intensity = a->intensity; P.d_intensity = a->d_intensity; P.hide_emitters = a->hide_emitters; P.seed = a->samplers[2].seed; P.skip = skip_ahead(a->samplers[2].skip);
-            set_shard(P, a, npx * T.sppse, kBlock, rank, count); P.dout = dout;
+            set_shard(P, a, npx_e * T.sppse, kBlock, rank, count); P.dout = edge_out;
             GuidingDev G{};
             const int use_g = a->guiding ? 1 : 0;
             if (a->guiding) G = a->guiding->G;
@@ -1065,6 +1126,8 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
                 else ON_CLS0(LAUNCH(0, (k_secondary_edges<0, COUNT, false>), sc, P.n_local, s_sec, sc->blob.as<float4>(), T_sec, sc->E, cam, P, G, use_g, ctr));
             }
         }
+        if (slot_of != nullptr)
+            hipLaunchKernelGGL(k_batch_gather, dim3((a->n_pix + 255) / 256), dim3(256), 0, st, a->pix_ids, a->n_pix, (int) npx_e, (const int *) slot_of, (const float *) edge_out, dout);
     }
     if (fork) {
         HIPCHK(hipEventRecord(sc->ev_join[0], sc->aux[0]));
@@ -1092,6 +1155,10 @@ int psdr_hip_render_d_fwd(const psdr_hip_scene *sc, const psdr_render_args *a, f
     if (!out || !dout) return fail("null output");
     return render_impl<false>(sc, a, true, out, dout, nullptr, 0, 0, nullptr, stream);
 }
+int psdr_hip_render_d_fwd_batch(const psdr_hip_scene *sc, const psdr_render_args *a, float *out, float *dout, void *stream) {
+    if (!out || !dout) return fail("null output");
+    return render_impl<false>(sc, a, true, out, dout, nullptr, 0, 0, nullptr, stream, true);
+}
 int psdr_hip_render_c_counted(const psdr_hip_scene *sc, const psdr_render_args *a, float *out, psdr_counters *c, void *stream) {
     if (!out) return fail("null output");
     return render_impl<true>(sc, a, false, out, nullptr, nullptr, 0, 0, c, stream);
@@ -1113,11 +1180,12 @@ int psdr_hip_scene_tex_layout(const psdr_hip_scene *sc, int64_t *offsets, int64_
     return 0;
 }
 
-int psdr_hip_render_d_bwd(const psdr_hip_scene *sc, const psdr_render_args *a, const float *d_rgb, const psdr_grads *g, void *stream) {
+static int render_bwd_impl(const psdr_hip_scene *sc, const psdr_render_args *a, const float *d_rgb, const psdr_grads *g, void *stream, bool batch_edges) {
     if (check_args(sc, a)) return 1;
+    if (batch_edges && !a->pix_ids) return fail("psdr_hip_render_d_bwd_batch needs args->pix_ids (the full frame has its edge terms in psdr_hip_render_d_bwd)");
     if (!d_rgb || !g || !g->g_triangles || !g->g_bsdf || !g->g_emitter) return fail("null gradient buffer");
     SCRATCH_GUARD(sc, stream);
-    // batch rendering (integrator.cpp:139-176): d_rgb is [n_pix*3]; only the interior term exists for a pixel list (as in the forward path)
+    // batch rendering (integrator.cpp:139-176): d_rgb is [n_pix*3]; the edge terms of a pixel list only with batch_edges (as in the forward path)
     const SceneTables &T = sc->T;
     hipStream_t st = (hipStream_t) stream;
     const long long npx_full = (long long) T.width * T.height;
@@ -1262,28 +1330,40 @@ int psdr_hip_render_d_bwd(const psdr_hip_scene *sc, const psdr_render_args *a, c
             else ON_CLS0(hipLaunchKernelGGL((k_interior_adjoint<0>), dim3(grid), dim3(kBlock), smem, st, sc->blob.as<float4>(), Ta, cam, P));
         }
     }
-    if (!a->pix_ids && (terms & PSDR_TERM_PRIMARY) && T.sppe > 0 && cam.n_edges > 0) {
+    const bool want_prim = (!a->pix_ids || batch_edges) && (terms & PSDR_TERM_PRIMARY) && T.sppe > 0 && cam.n_edges > 0;
+    const bool want_sec = (!a->pix_ids || batch_edges) && (terms & PSDR_TERM_SECONDARY) && T.sppse > 0 && sc->E.n > 0;
+    // a pixel list: the edge samples read their adjoint at the representative slot of their pixel (k_batch_reduce), the others are dropped
+    const float *edge_w = d_rgb;
+    SceneTables Tp = T;
+    if (batch_edges && (want_prim || want_sec)) {
+        int *slot_of = nullptr;
+        float *rows = nullptr;
+        if (batch_edge_scratch(sc, a, st, slot_of, rows)) return 1;
+        hipLaunchKernelGGL(k_batch_reduce, dim3((a->n_pix + 255) / 256), dim3(256), 0, st, a->pix_ids, a->n_pix, (int) npx_full, (const int *) slot_of, d_rgb, rows);
+        Tp.slot_of = slot_of; Ta.slot_of = slot_of; edge_w = rows;
+    }
+    if (want_prim) {
         if (!g->g_prim_edges) return fail("g_prim_edges is required when the primary-edge term is requested");
         PathParams P{};
         P.max_depth = fh_field >= 0 ? 0 : (a->direct_mode > 0 ? 1 : a->max_depth); P.mis = a->direct_mode - 1; P.field = fh_field; P.field_object = a->field_object; P.intensity = a->intensity; P.d_intensity = a->d_intensity; P.hide_emitters = a->hide_emitters; P.seed = a->samplers[1].seed; P.skip = skip_ahead(a->samplers[1].skip);
         set_shard(P, a, npx_full * T.sppe, kBlock, rank, count);
-        P.adj_w = d_rgb; P.g_prim = g->g_prim_edges; P.n_prim = cam.n_edges; P.lds_acc = (cam.n_edges <= 2048) ? 1 : 0;
+        P.adj_w = edge_w; P.g_prim = g->g_prim_edges; P.n_prim = cam.n_edges; P.lds_acc = (cam.n_edges <= 2048) ? 1 : 0;
         P.prim_filter = g->prim_edge_filter;
         if (P.n_local > 0) {
             if (next_queue(P.counter)) return 1;
             const int grid = grid_for(sc, P.n_local);
             const size_t sm = smem_for(sc, cls) + (P.lds_acc ? sizeof(float) * 4 * (size_t) cam.n_edges : 0);
-            if (cls == 1) ON_CLS1(hipLaunchKernelGGL((k_paths<false, 1, false, 1>), dim3(grid), dim3(kBlock), sm, st, sc->blob.as<float4>(), T, cam, P, (Counters *) nullptr));
-            else if (cls == 2) ON_CLS2(hipLaunchKernelGGL((k_paths<false, 2, false, 1>), dim3(grid), dim3(kBlock), sm, st, sc->blob.as<float4>(), T, cam, P, (Counters *) nullptr));
-            else ON_CLS0(hipLaunchKernelGGL((k_paths<false, 0, false, 1>), dim3(grid), dim3(kBlock), sm, st, sc->blob.as<float4>(), T, cam, P, (Counters *) nullptr));
+            if (cls == 1) ON_CLS1(hipLaunchKernelGGL((k_paths<false, 1, false, 1>), dim3(grid), dim3(kBlock), sm, st, sc->blob.as<float4>(), Tp, cam, P, (Counters *) nullptr));
+            else if (cls == 2) ON_CLS2(hipLaunchKernelGGL((k_paths<false, 2, false, 1>), dim3(grid), dim3(kBlock), sm, st, sc->blob.as<float4>(), Tp, cam, P, (Counters *) nullptr));
+            else ON_CLS0(hipLaunchKernelGGL((k_paths<false, 0, false, 1>), dim3(grid), dim3(kBlock), sm, st, sc->blob.as<float4>(), Tp, cam, P, (Counters *) nullptr));
         }
     }
-    if (!a->pix_ids && (terms & PSDR_TERM_SECONDARY) && T.sppse > 0 && sc->E.n > 0) {
+    if (want_sec) {
         if (!g->g_sec_edges) return fail("g_sec_edges is required when the secondary-edge term is requested");
         PathParams P{};
         P.max_depth = fh_field >= 0 ? 0 : (a->direct_mode > 0 ? 1 : a->max_depth); P.mis = a->direct_mode - 1; P.field = fh_field; P.field_object = a->field_object; P.intensity = a->intensity; P.d_intensity = a->d_intensity; P.hide_emitters = a->hide_emitters; P.seed = a->samplers[2].seed; P.skip = skip_ahead(a->samplers[2].skip);
         set_shard(P, a, npx_full * T.sppse, kBlock, rank, count);
-        P.adj_w = d_rgb; P.g_sec = g->g_sec_edges; P.g_tri = g->g_triangles; P.n_sec = sc->E.n;
+        P.adj_w = edge_w; P.g_sec = g->g_sec_edges; P.g_tri = g->g_triangles; P.n_sec = sc->E.n;
         P.g_cam = g->g_camera;
         P.sec_closed = no_sweep ? 0 : 1;
         const size_t sec_acc = sizeof(float) * (6 * (size_t) sc->E.n + 22 * (size_t) T.n_tris);
@@ -1306,6 +1386,13 @@ int psdr_hip_render_d_bwd(const psdr_hip_scene *sc, const psdr_render_args *a, c
     }
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+int psdr_hip_render_d_bwd(const psdr_hip_scene *sc, const psdr_render_args *a, const float *d_rgb, const psdr_grads *g, void *stream) {
+    return render_bwd_impl(sc, a, d_rgb, g, stream, false);
+}
+int psdr_hip_render_d_bwd_batch(const psdr_hip_scene *sc, const psdr_render_args *a, const float *d_rgb, const psdr_grads *g, void *stream) {
+    return render_bwd_impl(sc, a, d_rgb, g, stream, true);
 }
 
 static int trace_impl(const psdr_hip_scene *sc, int32_t n, const float *o, const float *d, int32_t *out_tri, float *out_uv, float *out_t, void *stream, int pairs) {

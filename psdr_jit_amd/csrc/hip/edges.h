@@ -62,6 +62,7 @@ PSDR_DEV SensorDirectSample sample_direct(const SceneTables &T, const SensorDev 
     const int ix = (int) floorf(q.x * (float) T.width), iy = (int) floorf(q.y * (float) T.height);
     r.valid = ix >= 0 && ix < T.width && iy >= 0 && iy < T.height;
     r.pixel_idx = r.valid ? iy * T.width + ix : -1;
+    edge_pixel_slot(T, r.pixel_idx, r.valid);          // (a pixel outside a batch list: the segment ends here, before its camera ray)
     Vec3f dir = p - Vec3f(cam.cam_pos[0], cam.cam_pos[1], cam.cam_pos[2]);
     const float dist2 = squared_norm(dir);
     dir = dir / safe_sqrt(dist2);

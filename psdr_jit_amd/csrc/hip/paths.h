@@ -211,8 +211,9 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                         const Dual px = fma_(p0x, oms, p1x * s), py = fma_(p0y, oms, p1y * s);
                         const Dual x_dot_n = fma_(py, ny, px * nx);
                         const int ix = (int) floorf(px.v * (float) T.width), iy = (int) floorf(py.v * (float) T.height);
-                        const bool edge_valid = ix >= 0 && ix < T.width && iy >= 0 && iy < T.height && !edge_sample_idle(P, ei, x_dot_n.d);
-                        park_i(kPix, edge_valid ? iy * T.width + ix : -1);
+                        const int edge_slot = (ix >= 0 && ix < T.width && iy >= 0 && iy < T.height) ? edge_pixel_slot(T, iy * T.width + ix) : -1;      // (-1 also: not in the batch list)
+                        const bool edge_valid = edge_slot >= 0 && !edge_sample_idle(P, ei, x_dot_n.d);
+                        park_i(kPix, edge_valid ? edge_slot : -1);
                         const RayT<false> ray_p = sample_primary_ray<false>(cam, px.v + kEdgeEpsilon * nx, py.v + kEdgeEpsilon * ny);
                         const RayT<false> ray_n = sample_primary_ray<false>(cam, px.v - kEdgeEpsilon * nx, py.v - kEdgeEpsilon * ny);
                         if constexpr (!AD) { ext = ray_n; cam_p = ray_p; trace_p = edge_valid; }      // (ray_p is rebuilt from (edge_i, edge_s) when the first path has ended: make_its wants it)
@@ -666,8 +667,9 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                             const Dual px = fma_(p0x, oms, p1x * s), py = fma_(p0y, oms, p1y * s);
                             const Dual x_dot_n = fma_(py, ny, px * nx);
                             const int ix = (int) floorf(px.v * (float) T.width), iy = (int) floorf(py.v * (float) T.height);
-                            edge_valid = ix >= 0 && ix < T.width && iy >= 0 && iy < T.height && !edge_sample_idle(P, ei, x_dot_n.d);
-                            pix_slot = edge_valid ? iy * T.width + ix : -1;
+                            const int edge_slot = (ix >= 0 && ix < T.width && iy >= 0 && iy < T.height) ? edge_pixel_slot(T, iy * T.width + ix) : -1;      // (-1 also: not in the batch list)
+                            edge_valid = edge_slot >= 0 && !edge_sample_idle(P, ei, x_dot_n.d);
+                            pix_slot = edge_valid ? edge_slot : -1;
                             const RayT<false> ray_n = sample_primary_ray<false>(cam, px.v - kEdgeEpsilon * nx, py.v - kEdgeEpsilon * ny);
                             if constexpr (!AD) ext = ray_n;
                             side = 0;

@@ -82,7 +82,22 @@ struct SceneTables {
     float emitter_sum;
     int blob_words;            // float4 count
     int width, height, spp, sppe, sppse;
+    // batch rendering with edge terms (psdr_hip_render_d_fwd_batch / _bwd_batch; set per launch, NULL = full frame): [width*height] full-frame pixel -> the row of the
+    // call's edge buffer that pixel's edge samples add to (the smallest k with pix_ids[k] == pixel), -1 = the pixel is not listed - its samples are dropped before a ray is traced
+    const int *slot_of;
 };
+
+// the pixel an edge sample lands on -> the row it adds to, -1 = a pixel nobody listed: the sample ends.  Two spellings, each the one that leaves the register
+// allocation of its kernel's full-frame instantiations alone (LABNOTES: spills of k_paths<.., 1> / k_secondary_edges before and after):
+// the path kernels (paths.h, MODE 1) ...
+PSDR_DEV int edge_pixel_slot(const SceneTables &T, int pix) { return T.slot_of != nullptr ? T.slot_of[pix] : pix; }
+// ... and sample_direct (edges.h; `pix` is -1 when !valid)
+PSDR_DEV void edge_pixel_slot(const SceneTables &T, int &pix, bool &valid) {
+    if (__builtin_expect(T.slot_of != nullptr, 0)) {
+        if (valid) pix = T.slot_of[pix];
+        valid = pix >= 0;
+    }
+}
 
 // Secondary-edge table inside the blob: 6 words per edge
 //   {p0.xyz, e1.x} {e1.yz, n0.xy} {n0.z, n1.xyz} {p2.xyz, bits(is_boundary)} {d_p0.xyz, d_e1.x} {d_e1.yz, 0, 0}

@@ -115,6 +115,7 @@ struct psdr_hip_scene {
     size_t gstack_slice = 0;
     mutable psdr::DevBuf adj_rec;        // per-lane records of the interior adjoint when they do not fit LDS (deep paths), grown on demand
     mutable size_t adj_rec_bytes = 0;
+    mutable psdr::DevBuf batch_map, batch_rows;   // batch rendering with edge terms: pixel -> slot map [width*height] and the edge rows [n_pix*3] of the call in flight, grown on demand
     mutable unsigned queue_slot = 0;
     mutable bool adj_attr_set = false;   // the adjoint kernels' dynamic-LDS limit has been raised on this scene's device
     int n_leaves = 0, max_depth = 0, grid = 0;

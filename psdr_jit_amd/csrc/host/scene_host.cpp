@@ -1448,13 +1448,14 @@ void Integrator::renderC(const Scene &scene, int sensor_id, int seed, uintptr_t 
 }
 
 void Integrator::renderD(const Scene &scene, int sensor_id, int seed, uintptr_t pix_ids, int n_pix, uintptr_t out, uintptr_t dout, uintptr_t stream,
-                         int rank, int count, int terms) const {
+                         int rank, int count, int terms, bool batch_edges) const {
     using namespace std::chrono;
     const auto start_time = high_resolution_clock::now();
     const RenderOption &opts = scene.m_opts;
     PSDR_ASSERT_MSG(!(pix_ids != 0 && seed == -1), "While using batch rendering, seed must be set!");
     PSDR_ASSERT_MSG(scene.is_ready(), "Input scene must be configured!");
     PSDR_ASSERT_MSG(sensor_id >= 0 && sensor_id < scene.m_num_sensors, "Invalid sensor id!");
+    PSDR_ASSERT_MSG(!(batch_edges && pix_ids == 0), "batch_edges needs batch_pix: the full frame always has its edge terms");
     const int64_t num_pixels = (int64_t) opts.height * opts.width;
     const int64_t npx = pix_ids ? n_pix : num_pixels;
     if (seed != -1) {
@@ -1471,12 +1472,13 @@ void Integrator::renderD(const Scene &scene, int sensor_id, int seed, uintptr_t 
     terms = ((terms >> 4) & 7) ? ((terms >> 4) & 7) : launch;
     if (field() >= 0) terms &= ~PSDR_TERM_SECONDARY;         // Integrator::render_secondary_edges is a no-op for the first-hit integrators
     a.terms = launch & terms;
+    // batch_edges: the full-frame edge samples that land on a listed pixel are kept (psdr_hip_render_d_fwd_batch); without it a pixel list has the interior term only
     if (a.terms)
-        hip_check(psdr_hip_render_d_fwd(scene.m_hip, &a, reinterpret_cast<float *>(out), reinterpret_cast<float *>(dout), reinterpret_cast<void *>(stream)));
+        hip_check((batch_edges ? psdr_hip_render_d_fwd_batch : psdr_hip_render_d_fwd)(scene.m_hip, &a, reinterpret_cast<float *>(out), reinterpret_cast<float *>(dout), reinterpret_cast<void *>(stream)));
     const PerspectiveCamera *cam = static_cast<const PerspectiveCamera *>(scene.m_sensors[sensor_id]);
     if (opts.spp > 0 && (terms & PSDR_TERM_INTERIOR)) scene.m_samplers[0].skip += 2 + (uint64_t) draws_per_level() * (uint64_t) max_depth();
-    if (opts.sppe > 0 && cam->m_enable_edges && (terms & PSDR_TERM_PRIMARY) && !pix_ids) scene.m_samplers[1].skip += 1 + 2 * (uint64_t) draws_per_level() * (uint64_t) max_depth();
-    if (opts.sppse > 0 && (terms & PSDR_TERM_SECONDARY) && !pix_ids) scene.m_samplers[2].skip += 3;
+    if (opts.sppe > 0 && cam->m_enable_edges && (terms & PSDR_TERM_PRIMARY) && (!pix_ids || batch_edges)) scene.m_samplers[1].skip += 1 + 2 * (uint64_t) draws_per_level() * (uint64_t) max_depth();
+    if (opts.sppse > 0 && (terms & PSDR_TERM_SECONDARY) && (!pix_ids || batch_edges)) scene.m_samplers[2].skip += 3;
     if (opts.log_level) {
         std::ostringstream oss;
         oss << "Rendered in " << duration_cast<duration<double>>(high_resolution_clock::now() - start_time).count() << " seconds.";

@@ -365,7 +365,7 @@ struct Integrator : Object {
     void renderC(const Scene &scene, int sensor_id, int seed, uintptr_t pix_ids, int n_pix, uintptr_t out, uintptr_t stream,
                  int shard_rank, int shard_count) const;
     void renderD(const Scene &scene, int sensor_id, int seed, uintptr_t pix_ids, int n_pix, uintptr_t out, uintptr_t dout, uintptr_t stream,
-                 int shard_rank, int shard_count, int terms) const;
+                 int shard_rank, int shard_count, int terms, bool batch_edges = false) const;
     virtual int max_depth() const = 0;
     virtual bool hide_emitters() const = 0;
     virtual const psdr_hip_guiding *guiding(int sensor_id) const { (void) sensor_id; return nullptr; }
