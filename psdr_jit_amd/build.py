@@ -21,13 +21,17 @@ LIBDIR = os.path.join(HERE, "lib")
 HIP_LIB = os.path.join(LIBDIR, "libpsdr_hip.so")
 CORE_LIB = os.path.join(HERE, "_psdr_core" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
 
-API_SRC = os.path.join(CSRC, "hip", "api.hip")                  # the render entry points and every kernel (compiled as seven units, see _compile_hip)
+API_SRC = os.path.join(CSRC, "hip", "api.hip")                  # the host unit: the render entry points (C ABI) and the small kernels
+UNITS_SRC = os.path.join(CSRC, "hip", "render_units.hip")       # the eight kernel units: the heavy kernel templates of render_kernels.h, one list of instantiations each (see hip_units)
 SCENE_SRC = os.path.join(CSRC, "hip", "scene_build.hip")        # psdr_hip_scene_create / _update: tree build and refit, blob layout, uploads
-HIP_SRCS = [API_SRC, SCENE_SRC]
+HIP_SRCS = [API_SRC, UNITS_SRC, SCENE_SRC]
 BUILD_DEPS = [os.path.join(HERE, "isa_lint.py")]          # part of the recipe: a change of the lint re-builds (and re-lints) the library
 _H = lambda *names: [os.path.join(CSRC, "hip", f) for f in names]
-COMMON_DEPS = _H("scene_obj.h", "scene_dev.h", "dmath.h", "trav4.h") + [os.path.join(ROOT, "include", "psdr_hip.h"), os.path.join(CSRC, "common", "threads.h")]
-API_DEPS = COMMON_DEPS + _H("sampler.h", "shade.h", "edges.h", "paths.h", "adjoint.h", "adjoint_mat.h", "microfacet.h", "isect_ad.h") + [os.path.join(CSRC, "common", "envmath.h")] + BUILD_DEPS
+# every quoted #include a unit's source reaches is in that unit's list (tests/test_build_deps.py walks the include graph)
+DEVICE_DEPS = _H("scene_dev.h", "dmath.h", "trav4.h")
+COMMON_DEPS = DEVICE_DEPS + _H("scene_obj.h") + [os.path.join(ROOT, "include", "psdr_hip.h"), os.path.join(CSRC, "common", "threads.h")]
+KERNEL_DEPS = DEVICE_DEPS + _H("render_kernels.h", "sampler.h", "shade.h", "edges.h", "paths.h", "adjoint.h", "adjoint_mat.h", "isect_ad.h", "microfacet.h") + [os.path.join(CSRC, "common", "envmath.h")] + BUILD_DEPS
+API_DEPS = sorted(set(COMMON_DEPS + KERNEL_DEPS))      # the host unit launches the heavy kernels: it sees their header, they do not see api.hip
 SCENE_DEPS = COMMON_DEPS + _H("bvh.h", "filter.h") + [os.path.join(CSRC, "host", "hnum.h")] + BUILD_DEPS
 HIP_DEPS = sorted(set(API_DEPS + SCENE_DEPS))
 HOST_SRCS = [os.path.join(CSRC, "host", f) for f in ("scene_host.cpp", "bindings.cpp", "exr_piz.cpp")]
@@ -74,14 +78,14 @@ def _run(cmd):
     return r.stdout
 
 
-N_KERNEL_UNITS = 8      # api.hip's PSDR_TU1..8: the heavy kernel templates of each scene class
+N_KERNEL_UNITS = 8      # render_kernels.h's PSDR_TU1..8: the heavy kernel templates of each scene class
 UNIT_CLASS_BIT = {1: 1, 2: 1, 6: 1, 8: 1, 3: 2, 4: 4, 7: 4, 5: 8}      # the PSDR_CLS_MASK bit of the scene class a unit instantiates
 
 
 def build_hip(force=False, extra_flags=(), target=None):
-    """api.hip is compiled as seven translation units in parallel - the host code with the small kernels (-DPSDR_SPLIT) and six units
-    that only instantiate the heavy kernel templates of one scene class (-DPSDR_TU=k) -, scene_build.hip as an eighth, and all are linked
-    into one library: ~4 minutes of wall time instead of ~10 for the single unit (PSDR_BUILD_JOBS=1 compiles them one after the other)."""
+    """Ten translation units compiled in parallel - api.hip (the host code with the small kernels), render_units.hip eight times (-DPSDR_TU=k:
+    unit k only instantiates list k of the heavy kernel templates, one scene class each) and scene_build.hip - and linked into one
+    library: ~4 minutes of wall time instead of ~10 for a single unit (PSDR_BUILD_JOBS=1 compiles them one after the other)."""
     os.makedirs(LIBDIR, exist_ok=True)
     flags = [f for f in HIP_FLAGS if f != "-shared"] + list(extra_flags)
     if target is not None:
@@ -142,22 +146,29 @@ def _lint_units(hipcc, flags, units, objdir):
             sys.stderr.write("psdr_jit_amd.build: " + l + "\n")
 
 
-def _compile_hip(flags, target, objdir):
-    """compiles and links api.hip with `flags` into `target`; objects go to `objdir`"""
-    sig = _signature(HIP_SRCS + HIP_DEPS, flags)
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    os.makedirs(objdir, exist_ok=True)
+def hip_units(flags=()):
+    """the translation units of the library as (name, source, defines, dependencies): object api_<name>.o is compiled again when its source, one of
+    its dependencies or a flag changed - the host unit `main` from api.hip, the kernel units `tu<k>` from render_units.hip (NOT from api.hip: an
+    edit of the host code leaves them alone), `scene` from scene_build.hip"""
     # development builds (-DPSDR_CLS_MASK=m: the host code launches the kernels of those scene classes only) skip the other classes' units
     mask = 15
     for f in flags:
         if f.startswith("-DPSDR_CLS_MASK="):
             mask = int(f.split("=")[1])
-    units = [("main", API_SRC, ["-DPSDR_SPLIT"], API_DEPS)] + [("tu%d" % k, API_SRC, ["-DPSDR_TU=%d" % k], API_DEPS) for k in (1, 6, 8, 2, 4, 7, 5, 3) if UNIT_CLASS_BIT[k] & mask] + \
-            [("scene", SCENE_SRC, [], SCENE_DEPS)]
+    return [("main", API_SRC, [], API_DEPS)] + [("tu%d" % k, UNITS_SRC, ["-DPSDR_TU=%d" % k], KERNEL_DEPS) for k in (1, 6, 8, 2, 4, 7, 5, 3) if UNIT_CLASS_BIT[k] & mask] + \
+           [("scene", SCENE_SRC, [], SCENE_DEPS)]
+
+
+def _compile_hip(flags, target, objdir):
+    """compiles the units of hip_units() with `flags` and links them into `target`; objects go to `objdir`"""
+    sig = _signature(HIP_SRCS + HIP_DEPS, flags)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    os.makedirs(objdir, exist_ok=True)
+    units = hip_units(flags)
     jobs = max(1, int(os.environ.get("PSDR_BUILD_JOBS", str(min(len(units), os.cpu_count() or 1)))))
     objs, pending, running = [], [], []
     # an object is compiled again only when ITS sources, headers or flags changed (signature beside it): editing the scene-build unit or
-    # bvh.h leaves the six kernel units - minutes of compile time - alone
+    # bvh.h leaves the eight kernel units - minutes of compile time - alone, and so does editing api.hip
     usigs = {}
     for name, src, defs, deps in units:
         obj = os.path.join(objdir, "api_%s.o" % name)

@@ -69,7 +69,7 @@ struct AdjointParams {
 
 constexpr int kMatOut = 16;         // a BSDF's row of psdr_grads.g_mat
 constexpr int kMatRow = 28;         // ... and of its LDS accumulator when uv transforms are differentiated: the g_mat row, then [rot, scale, tx, ty] of its three bitmaps (g_uv_xf);
-                                    // without g_uv_xf the accumulator's row is the g_mat row alone (`mrow` in the kernels, api.hip::adj LDS sizes)
+                                    // without g_uv_xf the accumulator's row is the g_mat row alone (`mrow` in the kernels, api.hip::render_bwd_impl, the LDS sizes)
 constexpr int kAdjMisc = 32;        // LDS accumulators every path adds to: camera pose, environment scale and transform
 // number of constant material parameters a BSDF record's flags announce (Microfacet 4 - fewer with maps -, RoughConductor 11, RoughDielectric 3)
 PSDR_DEV int mat_param_count(int fl) { return (fl & 4) ? 4 : ((fl & 8) ? 11 : ((fl & 16) ? 3 : 0)); }

@@ -109,7 +109,7 @@ template <int LDS> PSDR_DEV BoundarySegSampleDirect sample_boundary_segment_dire
 // PathTracer::eval_secondary_edge<ad>, reference path.cpp:171-270.
 // AD=true : returns the pixel index (or -1) and the tangent of the estimator in `value`.
 // AD=false: guiding pass, `value` = value0 without the normal velocity (path.cpp:267-268), returns -1.
-// what the closed-form reverse mode of the term needs from one evaluation (api.hip::k_secondary_edges<.., ADJ>): the detached factor, the
+// what the closed-form reverse mode of the term needs from one evaluation (render_kernels.h::k_secondary_edges<.., ADJ>): the detached factor, the
 // normal the velocity is projected on, the two triangles and the camera ray
 struct SecAdjInfo { Vec3f value0, n, x1, cam_o, cam_d, sd; int slot2, slot1; float qx, qy; };
 
@@ -125,7 +125,7 @@ PSDR_DEV int eval_secondary_edge(SceneView<LDS> &S, const SecEdgeTables &E, cons
 }
 
 // The traced part of eval_secondary_edge (path.cpp:176-270) for an already sampled, valid boundary segment, in the three pieces between its three rays
-// (eval_boundary_segment below strings them together one ray at a time; api.hip::k_secondary_edges pipelines them - round 6):
+// (eval_boundary_segment below strings them together one ray at a time; render_kernels.h::k_secondary_edges pipelines them - round 6):
 //   sec_light_hit_ok   the segment reaches its emitter sample (closest hit of p0 -> p2 lies at p2, on an emitter)
 //   sec_camera_sample  the opposite ray's hit p1 is seen by the sensor: sensor sample and camera ray through p1
 //   sec_value          the estimator's value from the three hits

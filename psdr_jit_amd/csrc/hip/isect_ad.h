@@ -6,8 +6,8 @@
 // so t, p, the shading frame, wi and uv move with the triangle's rows and with the ray.  The texture coordinates of the
 // triangle's corners are constants (the reference gathers them from a detached array).
 //
-// isect_ad_eval is the forward in either number type (Dual: one tangent, api.hip::k_intersect_ad); isect_ad_adjoint is its
-// transpose, stage by stage, in float registers from the same rows (api.hip::k_intersect_adj).  tests/test_gpu_intersect_ad.py
+// isect_ad_eval is the forward in either number type (Dual: one tangent, render_kernels.h::k_intersect_ad); isect_ad_adjoint is its
+// transpose, stage by stage, in float registers from the same rows (render_kernels.h::k_intersect_adj).  tests/test_gpu_intersect_ad.py
 // checks the two against each other (<J^T w, v> = <w, J v>) and against a float64 torch restatement.
 #pragma once
 #include "shade.h"

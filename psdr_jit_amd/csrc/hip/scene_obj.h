@@ -1,7 +1,7 @@
 // scene_obj.h — the device-resident scene behind a psdr_hip_scene handle, shared by the two host translation units of
 // libpsdr_hip.so: scene_build.hip (psdr_hip_scene_create / _update: tree build and refit, blob layout, uploads - what the
 // reference does in Scene_OptiX::configure + the jit uploads of Scene::configure, src/scene/scene_optix.cpp:265-332,
-// src/scene/scene.cpp:311-599) and api.hip (the render entry points and their kernels).
+// src/scene/scene.cpp:311-599) and api.hip (the render entry points; their kernels: render_kernels.h).
 #pragma once
 #include "../common/threads.h"
 #include <hip/hip_runtime.h>
@@ -152,7 +152,7 @@ struct psdr_hip_scene {
     // side streams for the edge terms of a renderD (api.hip::render_impl): forked from the caller's stream, joined before the call returns
     mutable hipStream_t aux[2] = {nullptr, nullptr};
     mutable hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
-    int make_term_streams() const {
+    __attribute__((noinline)) int make_term_streams() const {          // (cold - once per scene: out of line, not in the body of every render call)
         if (aux[0]) return 0;
         for (int k = 0; k < 2; ++k) {
             if (hipStreamCreateWithFlags(&aux[k], hipStreamNonBlocking) != hipSuccess) return 1;

@@ -280,7 +280,7 @@ PSDR_DEV Dual env_floor(const Dual &a) { return Dual(floorf(a.v), 0.f); }
 // (envmap.h:40-45): forward mode carries their tangents; in reverse mode the lookup is noted / probed like a BSDF bitmap
 // (scene_dev.h: id kEnvLookup), which yields the texel and scale adjoints.
 // The environment-map branches exist only in the LDS=false instantiations: a scene with an environment map is never
-// staged into LDS (api.hip), so the small-scene kernels (all Cornell boxes) carry none of this code or its registers.
+// staged into LDS (render_kernels.h::make_view), so the small-scene kernels (all Cornell boxes) carry none of this code or its registers.
 template <bool AD, int LDS> PSDR_DEV VecN<AD> env_eval_direction(const SceneView<LDS> &S, const EnvDev &E, const VecN<AD> &wi) {
     using R = Num<AD>;
     VecN<AD> v;
