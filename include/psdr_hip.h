@@ -157,7 +157,7 @@ typedef struct psdr_sensor_rec {
  * drjit device arrays - the reference computes these rows ON THE GPU in every Scene::configure.  With psdr_scene_snapshot.geometry set, psdr_hip_scene_update computes the
  * rows of the meshes flagged `moved` on the device, in the host's own (value, tangent) arithmetic (csrc/host/hnum.h compiled for both sides: the same bits), from the raw vertices
  * and the composed transform: ~1 MB travels instead of the 30 MB of rows the host would write.  The snapshot's row arrays stay valid (they are what psdr_hip_scene_create,
- * a rebuild and the host-side consumers read); the edge CDFs and the sensors' primary edges still come from the host. */
+ * a rebuild and the host-side consumers read); under psdr_hip_scene_update the edge distributions and the sensors' primary edges come from the host; psdr_hip_scene_update_edges selects the primary edges and builds both edge distributions on the device as well (only the float `sum`s are added on the host, from lengths read back). */
 typedef struct psdr_mesh_geometry {
     int32_t n_vertices, n_faces, n_edges;          /* n_edges: this mesh's rows of psdr_sec_edges (0 when its edges are disabled or sppse == 0) */
     const float *vertices_raw, *d_vertices_raw;    /* [n_vertices*3] Mesh::m_vertex_positions_raw and its forward tangent */
@@ -292,6 +292,47 @@ int psdr_hip_scene_check_tree(const psdr_hip_scene *scene, int64_t *violations);
 /* test aid (synchronises, downloads the sections): 32-bit words of the device's triangle rows (traversal, shading, tangent) and secondary-edge rows that differ from the rows
  * the host path would write from `snapshot` - 0 when the kernels that compute a moved mesh's rows on the device (psdr_mesh_geometry) produced the host's bits */
 int psdr_hip_scene_check_rows(const psdr_hip_scene *scene, const psdr_scene_snapshot *snapshot, int64_t *mismatches);
+/* PRIMARY EDGES ON THE DEVICE.  The reference selects every configured sensor's primary edges on drjit device arrays in each Scene::configure (the silhouette test and compressD,
+ * src/sensor/perspective.cpp:52-151).  psdr_hip_scene_update_edges is psdr_hip_scene_update plus that: with the world vertices, face normals and areas of psdr_mesh_geometry resident on
+ * the device, the sensors marked PSDR_EDGES_DEVICE get their edges selected there - keep flags, a stable compaction (the order of an in-order walk over meshes and edges), the rows, in
+ * the host's own arithmetic (csrc/host/edge_select.h compiled for both sides: the same bits) - and no array proportional to an edge count travels to the device.  The distribution
+ * (DiscreteDistribution::init, src/core/pmf.cpp:6-15: a sequential double-precision running sum rounded to float per entry, and a sequential float sum) is completed there too: the
+ * cmf by a parallel scan where every partial sum is provably exact in double (exponent range of the lengths + 24 + log2 n bits within 53, checked on the device); the kept lengths and
+ * ids come BACK (16 B per kept edge, device to host) and the host adds the float sum - and, where the bound does not hold, runs the sequential form itself and sends that cmf (4 B
+ * per entry: the only edge-proportional bytes that can still go up).
+ * Memory: under this call every sensor's edge arrays have room for every edge of the meshes with edges (56 B per edge and sensor, in the scene blob and its pinned host copy);
+ * psdr_hip_scene_create reserves that room for BVH scenes with `geometry` and sppe > 0 (from psdr_mesh_geometry.n_edges - nothing when sppse == 0: the first such update then moves
+ * the blob once), and a scene that has been given the size keeps it under psdr_hip_scene_update.  After an update in which the HOST wrote triangle rows, the next device update recomputes
+ * the world vertices of every mesh, not only of the moved ones.
+ * Under this call every sensor's edge arrays are sized once, to the number of edges of the meshes with edges: a later call never moves them.
+ *   topo [snapshot->n_meshes]: the edge list of every mesh (read when a topology_version, count or flag differs from what the device saw last)
+ *   sensor_mode [snapshot->n_sensors]: PSDR_EDGES_HOST - the snapshot's edge arrays of this sensor, as psdr_hip_scene_update; PSDR_EDGES_DEVICE - select them on the device (the
+ *     snapshot's edge pointers, n_edges and edge_sum of this sensor are ignored); PSDR_EDGES_KEEP - what an earlier PSDR_EDGES_DEVICE selected still holds (same meshes, same sensor)
+ * Returns PSDR_HIP_NEED_ROWS with the scene unchanged when a sensor is not PSDR_EDGES_HOST and the device cannot do it now (a brute-force scene, a tree to build, a blob that moves,
+ * snapshot->geometry NULL, world vertices not resident yet, PSDR_HOST_GEOMETRY set): call again with PSDR_EDGES_HOST for every sensor and the edge arrays filled. */
+typedef struct psdr_edge_topology {
+    int32_t n_edges;                 /* edges of the mesh (Mesh::m_edge_indices) */
+    const int32_t *edges;            /* [n_edges*5] v0 v1 f0 f1 opp, mesh-local ids; f1 = -1: boundary edge */
+    const uint8_t *uv_seam;          /* [n_edges] 1: the two faces do not share exactly two uv indices (perspective.cpp:95-110); NULL: the mesh has no uv coordinates */
+    int32_t enabled;                 /* Mesh::m_enable_edges */
+    uint64_t topology_version;       /* changes whenever edges / uv_seam do */
+} psdr_edge_topology;
+#define PSDR_EDGES_HOST   0
+#define PSDR_EDGES_DEVICE 1
+#define PSDR_EDGES_KEEP   2
+int psdr_hip_scene_update_edges(psdr_hip_scene *scene, const psdr_scene_snapshot *snapshot, uint32_t same, const psdr_edge_topology *topo, const int32_t *sensor_mode,
+                                psdr_update_info *info);
+/* what a sensor keeps (perspective.cpp:112-151): *count edges, *edge_sum = Sensor::m_edge_distrb.sum(); ids (HOST [cap*3], may be NULL): (Mesh id, v0, v1) of the kept edges in their
+ * order - only for a sensor whose edges the device selected */
+int psdr_hip_scene_primary_edges(const psdr_hip_scene *scene, int32_t sensor_id, int32_t *count, int32_t *ids, int32_t cap, float *edge_sum);
+/* test aid (synchronises, downloads the sections): 32-bit words in which the device's primary-edge arrays and distribution of every sensor and the secondary-edge distribution differ
+ * from what the host path would write from `snapshot` (its edge arrays filled) - 0 when the device's selection produced the host's bits in the host's order */
+int psdr_hip_scene_check_edges(const psdr_hip_scene *scene, const psdr_scene_snapshot *snapshot, int64_t *mismatches);
+/* what the last create / update COMPUTED: *path = 0 no edge array or edge distribution was made on the device in it (they came from the host's arrays, or stood as they were:
+ * PSDR_EDGES_KEEP, PSDR_SAME_SEC_EDGES), 1 it selected a sensor's primary edges and / or built the secondary-edge distribution on the device and every cmf came from the parallel scan,
+ * 2 as 1 but a cmf needed the sequential form; *edge_bytes = bytes it sent host to device for the sensors' primary edges (rows, distributions, search tables, the edge list) and for the
+ * secondary-edge distribution (pmf, cmf, search table; not the secondary-edge rows) */
+int psdr_hip_scene_edge_path(const psdr_hip_scene *scene, int32_t *path, int64_t *edge_bytes);
 /* BVH statistics for DESIGN/bench: nodes, leaves, max depth, bytes resident in LDS per workgroup */
 int psdr_hip_scene_stats(const psdr_hip_scene *scene, int32_t *n_nodes, int32_t *n_leaves, int32_t *max_depth, int32_t *lds_bytes);
 /* The live-pixel mask of a sensor (HOST bits[(width*height + 31) / 32], bit y*width + x; either pointer may be NULL): a pixel is dead when

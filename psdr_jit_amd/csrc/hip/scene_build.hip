@@ -21,6 +21,7 @@
 #include "bvh.h"
 #include "filter.h"
 #include "../host/hnum.h"
+#include "../host/edge_select.h"
 
 using namespace psdr;
 
@@ -374,7 +375,7 @@ static int geometry_on_device(psdr_hip_scene *sc, const psdr_scene_snapshot *s, 
             GeoMeshDev &m = mt[(size_t) i];
             std::memcpy(m.tw, G[i].to_world, 64); std::memcpy(m.d_tw, G[i].d_to_world, 64);
             m.v_off = (int) vo; m.n_v = G[i].n_vertices; m.f_off = (int) fo; m.n_f = G[i].n_faces; m.e_off = (int) eo; m.n_e = G[i].n_edges;
-            m.mesh_id = G[i].mesh_id; m.flat = G[i].use_face_normals; m.moved = (G[i].moved || !same_topo) ? 1 : 0; m.pad[0] = m.pad[1] = m.pad[2] = 0;
+            m.mesh_id = G[i].mesh_id; m.flat = G[i].use_face_normals; m.moved = (G[i].moved || !same_topo || !sc->geo_world_current) ? 1 : 0; m.pad[0] = m.pad[1] = m.pad[2] = 0;
             vo += (size_t) G[i].n_vertices; fo += (size_t) G[i].n_faces; eo += (size_t) G[i].n_edges;
         }
     }
@@ -444,14 +445,337 @@ static int geometry_on_device(psdr_hip_scene *sc, const psdr_scene_snapshot *s, 
         hipLaunchKernelGGL(k_geo_sec, dim3(be), dim3(256), 0, nullptr, (float4 *) sc->blob.p, sc->E.off, Md, sc->buf("geo.edges").as<int>(), world, fnrm, farea, (int) NE);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(nullptr));                         // (the mesh table is a local; the kernels take ~0.1 ms)
+    sc->geo_world_current = true;                                  // (world / fnrm / farea hold this state of EVERY mesh: what the primary-edge selection below reads)
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// PRIMARY EDGES ON THE DEVICE (psdr_hip_scene_update_edges, include/psdr_hip.h).  The reference selects a sensor's primary edges on drjit device arrays in every
+// Scene::configure (src/sensor/perspective.cpp:52-151: the silhouette test, then compressD); here the host walked every edge of every mesh and sent the kept rows.
+// With the world vertices, face normals and areas of geometry_on_device resident, three small kernels do it per sensor, calling the host's own keep test and row
+// (csrc/host/edge_select.h, compiled for both sides):
+//   k_pe_flags   one flag per enabled edge + the number kept per 256-thread workgroup (wave64 ballot / popcount)
+//   k_pe_bases   exclusive scan of the workgroup counts (one workgroup; integers, so the order of the partial sums is immaterial), the total behind them
+//   k_pe_rows    rank of a kept edge = workgroup base + kept edges of the earlier waves + popcount of the ballot below its lane: the position an in-order walk over
+//                meshes and edges gives it (no atomics: they would not preserve the order the host's chain rule and ids index by); writes the row, the PMF entry,
+//                the length and the (mesh, v0, v1) ids
+// The distribution is completed by cdf_on_device (below); the kept lengths (the PMF words) and ids come back for the float sum and the host's chain rule.
+// ---- the CDF of an edge distribution on the device.  DiscreteDistribution::init (reference src/core/pmf.cpp:6-15; csrc/host/scene_host.cpp Distrb::init) is a SEQUENTIAL
+// double-precision running sum over the float entries, rounded to float per entry.  A parallel scan gives those bits only where every partial sum is exact in double, whatever the
+// order: the entries are multiples of 2^(emin - 150) below 2^(emax - 126) (emin / emax: smallest / largest biased exponent of a non-zero entry), so a sum of n of them is such a
+// multiple below 2^(emax - 126 + ceil(log2 n)) - exact when (emax - emin + 1) + 24 + ceil(log2 n) <= 53.  The kernels that write the entries record the exponent range
+// (cdf_note_exponent), k_cdf_bases checks the bound ON THE DEVICE; where it does not hold (or an entry is negative, infinite or NaN) the sequential form runs on the HOST, over the
+// lengths that came back for the float sum anyway, and the cmf goes up (4 B per entry) - a single lane walking the table on the device was 50 x slower than that.
+__device__ inline void cdf_note_exponent(int *range, float x) {
+    const unsigned u = __float_as_uint(x);
+    if (u == 0u) return;                                     // (+0 adds nothing)
+    int e = (int) ((u >> 23) & 0xffu);
+    if (e == 0) e = 1;                                       // (subnormals: multiples of 2^-149, as the entries of exponent 1)
+    if ((u >> 31) != 0u) e = 255;                            // (a negative entry: the host refuses it; here it only rules the scan out)
+    atomicMin(&range[0], e); atomicMax(&range[1], e);        // (integers: the result does not depend on the order)
+}
+__device__ inline bool cdf_scan_is_exact(const int *range, int n) {
+    const int emin = range[0], emax = range[1];
+    if (emax == 0) return true;                              // every entry is zero
+    if (emax >= 255) return false;
+    int lg = 0;
+    while ((1ll << lg) < (long long) n) ++lg;
+    return (emax - emin + 1) + 24 + lg <= 53;
+}
+__device__ inline double cdf_wave_inclusive(double x, int lane) {
+    for (int off = 1; off < 64; off <<= 1) { const double y = __shfl_up(x, off); if (lane >= off) x += y; }
+    return x;
+}
+// sums of 256 entries each
+__global__ void __launch_bounds__(256) k_cdf_partial(const float *__restrict__ pmf, int n, double *__restrict__ bsum) {
+    __shared__ double ws[4];
+    const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double x = cdf_wave_inclusive(i < n ? (double) pmf[i] : 0.0, lane);
+    if (lane == 63) ws[wave] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) bsum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+}
+// one workgroup: the bound; exact -> exclusive scan of the block sums in place, *mode = 1; otherwise *mode = 2 and nothing is written
+__global__ void __launch_bounds__(256) k_cdf_bases(double *__restrict__ bsum, int nb, const int *__restrict__ range, int n, int *__restrict__ mode) {
+    __shared__ double ws[4];
+    __shared__ double carry;
+    const bool exact = cdf_scan_is_exact(range, n);           // (uniform: every lane reads the same two words)
+    if (!exact) { if (threadIdx.x == 0) *mode = 2; return; }       // (the caller runs the sequential form: one lane over 26 000 entries took 1.6 ms here, the host 0.03 ms)
+    if (threadIdx.x == 0) { carry = 0.0; *mode = 1; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int begin = 0; begin < nb; begin += 256) {
+        const int i = begin + threadIdx.x;
+        const double c = i < nb ? bsum[i] : 0.0;
+        const double x = cdf_wave_inclusive(c, lane);
+        if (lane == 63) ws[wave] = x;
+        __syncthreads();
+        double before = carry;
+        for (int w = 0; w < wave; ++w) before += ws[w];
+        if (i < nb) bsum[i] = before + x - c;
+        __syncthreads();
+        if (threadIdx.x == 255) carry = before + x;
+        __syncthreads();
+    }
+}
+__global__ void __launch_bounds__(256) k_cdf_apply(const float *__restrict__ pmf, float *__restrict__ cmf, const double *__restrict__ bsum, const int *__restrict__ mode, int n) {
+    __shared__ double ws[4];
+    if (*mode != 1) return;                                   // (the sequential form writes the cmf)
+    const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double x = cdf_wave_inclusive(i < n ? (double) pmf[i] : 0.0, lane);
+    if (lane == 63) ws[wave] = x;
+    __syncthreads();
+    double before = bsum[blockIdx.x];
+    for (int w = 0; w < wave; ++w) before += ws[w];
+    if (i < n) cmf[i] = (float) (before + x);
+}
+// the guide table of scene_obj.h::build_cdf_guide, one bucket bound per thread, in the same float arithmetic
+__global__ void k_cdf_guide(const float *__restrict__ cmf, int size, float sum, int nb, int *__restrict__ guide) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > nb) return;
+    const float s = ((float) k / (float) nb) * sum;
+    int lo = 0, len = size - 1;                               // first i in [0, size - 1) with !(cmf[i] < s), else size - 1
+    while (len > 0) {
+        const int half = len >> 1;
+        if (cmf[lo + half] < s) { lo += half + 1; len -= half + 1; } else len = half;
+    }
+    guide[k] = lo;
+}
+// buckets build_cdf_guide gives a table of `size` entries (0: no table)
+static int cdf_guide_buckets(int size, int per_bucket) {
+    if (size < 256) return 0;
+    int nb = 1;
+    while (nb * per_bucket <= size) nb <<= 1;
+    return nb;
+}
+// cmf[0..n) and the guide table of pmf[0..n) (device pointers; host_pmf: the same entries on the host; sum: their sequential float sum); scratch sized for `cap` entries.
+// *mode: 1 parallel scan on the device, 2 sequential form on the host (its cmf is sent: counted in info.bytes_uploaded and `bytes`)
+static int cdf_on_device(psdr_hip_scene *sc, const float *pmf, float *cmf, const float *host_pmf, int n, int cap, float sum, const int *range, const std::string &guide_key, const int *&guide,
+                         int &guide_n, int *mode, psdr_update_info &info, int64_t &bytes) {
+    guide = nullptr; guide_n = 0;
+    const int nb = (n + 255) / 256, nb_cap = (std::max(cap, n) + 255) / 256;
+    DevBuf &bs = sc->buf("cdf.bsum"), &md = sc->buf("cdf.mode");
+    if (bs.bytes < sizeof(double) * (size_t) (nb_cap + 1) && bs.ensure(sizeof(double) * (size_t) (nb_cap + 1))) return 1;
+    if (md.ensure(sizeof(int))) return 1;
+    hipLaunchKernelGGL(k_cdf_partial, dim3((unsigned) nb), dim3(256), 0, nullptr, pmf, n, (double *) bs.p);
+    hipLaunchKernelGGL(k_cdf_bases, dim3(1), dim3(256), 0, nullptr, (double *) bs.p, nb, range, n, (int *) md.p);
+    hipLaunchKernelGGL(k_cdf_apply, dim3((unsigned) nb), dim3(256), 0, nullptr, pmf, cmf, (const double *) bs.p, (const int *) md.p, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(mode, md.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (*mode != 1) {
+        std::vector<float> c((size_t) n);
+        double acc = 0.0;
+        for (int i = 0; i < n; ++i) { acc += (double) host_pmf[i]; c[(size_t) i] = (float) acc; }
+        HIPCHK(hipMemcpy(cmf, c.data(), sizeof(float) * (size_t) n, hipMemcpyHostToDevice));
+        info.bytes_uploaded += (int64_t) (4 * (size_t) n); bytes += (int64_t) (4 * (size_t) n);
+        *mode = 2;
+    }
+    const int gb = cdf_guide_buckets(n, 4);
+    if (gb > 0) {
+        DevBuf &g = sc->buf(guide_key);
+        const size_t want = sizeof(int) * (size_t) (cdf_guide_buckets(std::max(cap, n), 4) + 1);          // (sized for the capacity: the table of a later selection fits)
+        if (g.bytes < sizeof(int) * (size_t) (gb + 1) && g.ensure(want)) return 1;
+        hipLaunchKernelGGL(k_cdf_guide, dim3((unsigned) ((gb + 1 + 255) / 256)), dim3(256), 0, nullptr, (const float *) cmf, n, sum, gb, (int *) g.p);
+        HIPCHK(hipGetLastError());
+        guide = g.as<int>(); guide_n = gb;
+    }
+    return 0;
+}
+
+// PMF entries of the secondary-edge distribution (Scene::m_sec_edge_distrb, reference src/scene/scene.cpp:559-563): the edge lengths, in the host's explicit-fmaf arithmetic
+// (edge_select.h::edge_length3).  edges: the [ne][6] list of k_geo_sec
+__global__ void k_se_length(const int *__restrict__ edges, const float *__restrict__ world, float *__restrict__ pmf, int *__restrict__ range, int ne) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= ne) return;
+    const float *a = world + 6 * (size_t) edges[6 * (size_t) r], *b = world + 6 * (size_t) edges[6 * (size_t) r + 1];
+    const float pa[3] = {a[0], a[2], a[4]}, pb[3] = {b[0], b[2], b[4]};
+    const float len = psdr_host::edge_length3(pa, pb);
+    pmf[r] = len;
+    cdf_note_exponent(range, len);
+}
+__global__ void k_cdf_range_reset(int *__restrict__ range) { range[0] = 0x7fffffff; range[1] = 0; }
+
+struct PeEdge { int v0, v1, f0, f1, mf; };          // global vertex / face ids (f1 = -1: boundary), mesh index << 3 | bit 0 uv seam | bit 1 has uv | bit 2 face normals
+struct PeMesh { int mesh_id, v_off; };              // per mesh: Mesh id and first global vertex (the ids of a kept edge are mesh-local)
+struct PeCam { float w2s[16], d_w2s[16], pos[3]; int pe_off, pecdf_off; };
+
+__device__ inline bool pe_keep_edge(const PeEdge &e, const PeCam &cam, const int *__restrict__ faces, const float *__restrict__ world, const float *__restrict__ fnrm, const float *__restrict__ farea) {
+    float t0[6], t1[6];
+    auto face = [&](int f, float *t) {
+        const float *p = world + 6 * (size_t) faces[3 * (size_t) f], *n = fnrm + 6 * (size_t) f;
+        const float a2 = farea[2 * (size_t) f];
+        t[0] = p[0]; t[1] = p[2]; t[2] = p[4];
+        t[3] = psdr_host::canon_nan(n[0] / a2); t[4] = psdr_host::canon_nan(n[2] / a2); t[5] = psdr_host::canon_nan(n[4] / a2);
+    };
+    face(e.f0, t0);
+    if (e.f1 >= 0) face(e.f1, t1);
+    return psdr_host::edge_keep(cam.pos, t0, e.f1 >= 0 ? t1 : nullptr, (e.mf & 4) != 0, (e.mf & 2) != 0, (e.mf & 1) != 0);
+}
+
+__global__ void __launch_bounds__(256) k_pe_flags(const PeEdge *__restrict__ edges, PeCam cam, const int *__restrict__ faces, const float *__restrict__ world, const float *__restrict__ fnrm,
+                                                  const float *__restrict__ farea, unsigned char *__restrict__ flags, int *__restrict__ block_count, int ne) {
+    __shared__ int wc[4];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool keep = i < ne && pe_keep_edge(edges[i], cam, faces, world, fnrm, farea);
+    if (i < ne) flags[i] = keep ? 1 : 0;
+    const unsigned long long b = __ballot(keep);
+    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) block_count[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+}
+
+// counts[0..nb) -> exclusive bases in place, counts[nb] = the total
+__global__ void __launch_bounds__(256) k_pe_bases(int *__restrict__ counts, int nb, int *__restrict__ range) {
+    __shared__ int wsum[4];
+    __shared__ int carry;
+    if (threadIdx.x == 0) { carry = 0; range[0] = 0x7fffffff; range[1] = 0; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int begin = 0; begin < nb; begin += 256) {
+        const int i = begin + threadIdx.x;
+        const int c = i < nb ? counts[i] : 0;
+        int x = c;                                          // inclusive scan inside the wave
+        for (int off = 1; off < 64; off <<= 1) { const int y = __shfl_up(x, off); if (lane >= off) x += y; }
+        if (lane == 63) wsum[wave] = x;
+        __syncthreads();
+        int before = carry;
+        for (int w = 0; w < wave; ++w) before += wsum[w];
+        if (i < nb) counts[i] = before + x - c;
+        __syncthreads();
+        if (threadIdx.x == 255) carry = before + x;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) counts[nb] = carry;
+}
+
+__global__ void __launch_bounds__(256) k_pe_rows(const PeEdge *__restrict__ edges, const PeMesh *__restrict__ meshes, PeCam cam, const float *__restrict__ world, const unsigned char *__restrict__ flags, const int *__restrict__ bases,
+                                                 int *__restrict__ range, float4 *__restrict__ blob, int *__restrict__ ids, int ne) {
+    __shared__ int wc[4];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool keep = i < ne && flags[i] != 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(keep);
+    if (lane == 0) wc[wave] = __popcll(b);
+    __syncthreads();
+    if (!keep) return;
+    int r = bases[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) r += wc[w];
+    const PeEdge e = edges[i];
+    DM4 w2s;
+    for (int a = 0; a < 4; ++a) for (int c = 0; c < 4; ++c) w2s.m[a][c] = DF(cam.w2s[4 * a + c], cam.d_w2s[4 * a + c]);
+    const psdr_host::PrimEdgeRow row = psdr_host::edge_row(w2s, geo_ld(world, (size_t) e.v0), geo_ld(world, (size_t) e.v1));
+    float4 *w = blob + cam.pe_off + 3 * (size_t) r;
+    w[0] = make_float4(row.p0[0], row.p0[1], row.p1[0], row.p1[1]);
+    w[1] = make_float4(row.d_p0[0], row.d_p0[1], row.d_p1[0], row.d_p1[1]);
+    w[2] = make_float4(row.normal[0], row.normal[1], row.length, 0.f);
+    reinterpret_cast<float *>(blob + cam.pecdf_off)[r] = row.length;            // pmf; the cmf follows it at [total + r] (cdf_on_device)
+    const PeMesh m = meshes[e.mf >> 3];
+    ids[3 * (size_t) r] = m.mesh_id; ids[3 * (size_t) r + 1] = e.v0 - m.v_off; ids[3 * (size_t) r + 2] = e.v1 - m.v_off;
+    cdf_note_exponent(range, row.length);
+}
+
+// total number of edges of the meshes with edges: what every sensor's edge arrays are sized to under psdr_hip_scene_update_edges
+static size_t pe_capacity(const psdr_scene_snapshot *s, const psdr_edge_topology *topo) {
+    size_t cap = 0;
+    if (s->sppe > 0) for (int i = 0; i < s->n_meshes; ++i) if (topo[i].enabled) cap += (size_t) std::max(0, topo[i].n_edges);
+    return cap;
+}
+
+// the edge list the kernels read: sent when a mesh's topology version (or a count / flag it is laid out by) changed; -> 1 on error
+static int pe_sync_topology(psdr_hip_scene *sc, const psdr_scene_snapshot *s, const psdr_edge_topology *topo, int64_t &edge_bytes) {
+    const psdr_mesh_geometry *G = s->geometry;
+    const int nm = s->n_meshes;
+    std::vector<uint64_t> key;
+    size_t NE = 0;
+    for (int i = 0; i < nm; ++i) {
+        const bool on = s->sppe > 0 && topo[i].enabled && topo[i].n_edges > 0;
+        for (uint64_t x : {topo[i].topology_version, (uint64_t) (on ? topo[i].n_edges : 0), (uint64_t) G[i].n_vertices, (uint64_t) G[i].n_faces, (uint64_t) G[i].mesh_id,
+                           (uint64_t) ((G[i].use_face_normals ? 4 : 0) | (topo[i].uv_seam ? 2 : 0))}) key.push_back(x);
+        if (on) NE += (size_t) topo[i].n_edges;
+    }
+    if (key == sc->pe_topo_key && sc->pe_n == (int) NE) return 0;
+    sc->pe_topo_key.clear();
+    std::vector<PeEdge> ed(std::max<size_t>(1, NE));
+    std::vector<PeMesh> pm((size_t) std::max(1, nm));
+    size_t vo = 0, fo = 0, k = 0;
+    for (int i = 0; i < nm; ++i) {
+        const bool on = s->sppe > 0 && topo[i].enabled && topo[i].n_edges > 0;
+        if (on && !topo[i].edges) return fail("psdr_edge_topology[" + std::to_string(i) + "]: edges is null");
+        const int nv = G[i].n_vertices, nf = G[i].n_faces;
+        for (int e = 0; on && e < topo[i].n_edges; ++e) {
+            const int32_t *q = topo[i].edges + 5 * (size_t) e;            // v0 v1 f0 f1 opp
+            if (q[0] < 0 || q[0] >= nv || q[1] < 0 || q[1] >= nv || q[2] < 0 || q[2] >= nf || q[3] < -1 || q[3] >= nf)
+                return fail("psdr_edge_topology[" + std::to_string(i) + "]: edge " + std::to_string(e) + " refers outside the mesh's vertices / faces");
+            PeEdge &d = ed[k++];
+            d.v0 = (int) vo + q[0]; d.v1 = (int) vo + q[1]; d.f0 = (int) fo + q[2]; d.f1 = q[3] >= 0 ? (int) fo + q[3] : -1;
+            d.mf = (i << 3) | (topo[i].uv_seam && topo[i].uv_seam[e] ? 1 : 0) | (topo[i].uv_seam ? 2 : 0) | (G[i].use_face_normals ? 4 : 0);
+        }
+        pm[(size_t) i] = PeMesh{G[i].mesh_id, (int) vo};
+        vo += (size_t) nv; fo += (size_t) nf;
+    }
+    const size_t nb = (NE + 255) / 256;
+    DevBuf &be = sc->buf("pe.edges");
+    if (be.ensure(sizeof(PeEdge) * ed.size())) return 1;
+    HIPCHK(hipMemcpy(be.p, ed.data(), sizeof(PeEdge) * ed.size(), hipMemcpyHostToDevice));
+    DevBuf &bm = sc->buf("pe.meshes");
+    if (bm.ensure(sizeof(PeMesh) * pm.size())) return 1;
+    HIPCHK(hipMemcpy(bm.p, pm.data(), sizeof(PeMesh) * pm.size(), hipMemcpyHostToDevice));
+    edge_bytes += (int64_t) (sizeof(PeEdge) * ed.size() + sizeof(PeMesh) * pm.size());
+    if (sc->buf("pe.flags").ensure(std::max<size_t>(1, NE)) || sc->buf("pe.block").ensure(sizeof(int) * (nb + 1)) || sc->buf("pe.ids").ensure(sizeof(int) * 3 * std::max<size_t>(1, NE)) ||
+        sc->buf("pe.range").ensure(2 * sizeof(int))) return 1;
+    sc->pe_n = (int) NE;
+    sc->pe_topo_key = key;
+    return 0;
+}
+
+// selects sensor k's primary edges on the device and completes its distribution; d.pe_off / d.pecdf_off are set.  -> 1 on error
+static int primary_edges_on_device(psdr_hip_scene *sc, const psdr_sensor_rec &r, int k, SensorDev &d, psdr_update_info &info, int64_t &edge_bytes, bool &cdf_sequential) {
+    const int NE = sc->pe_n;
+    std::vector<int32_t> &ids = sc->pe_ids[(size_t) k];
+    ids.clear();
+    d.n_edges = 0; d.edge_sum = 0.f; d.pe_guide = nullptr; d.pe_guide_n = 0;
+    if (NE <= 0) return 0;
+    PeCam cam;
+    std::memcpy(cam.w2s, r.world_to_sample, 64); std::memcpy(cam.d_w2s, r.d_world_to_sample, 64);
+    for (int q = 0; q < 3; ++q) cam.pos[q] = r.cam_pos[q];
+    cam.pe_off = d.pe_off; cam.pecdf_off = d.pecdf_off;
+    const int nb = (NE + 255) / 256;
+    const PeEdge *edges = sc->buf("pe.edges").as<PeEdge>();
+    const float *world = sc->buf("geo.world").as<float>(), *fnrm = sc->buf("geo.fnrm").as<float>(), *farea = sc->buf("geo.farea").as<float>();
+    unsigned char *flags = (unsigned char *) sc->buf("pe.flags").p;
+    int *block = (int *) sc->buf("pe.block").p, *dids = (int *) sc->buf("pe.ids").p;
+    hipLaunchKernelGGL(k_pe_flags, dim3((unsigned) nb), dim3(256), 0, nullptr, edges, cam, sc->buf("geo.faces").as<int>(), world, fnrm, farea, flags, block, NE);
+    int *range = (int *) sc->buf("pe.range").p;
+    hipLaunchKernelGGL(k_pe_bases, dim3(1), dim3(256), 0, nullptr, block, nb, range);
+    hipLaunchKernelGGL(k_pe_rows, dim3((unsigned) nb), dim3(256), 0, nullptr, edges, sc->buf("pe.meshes").as<PeMesh>(), cam, world, (const unsigned char *) flags, (const int *) block, range, (float4 *) sc->blob.p, dids, NE);
+    HIPCHK(hipGetLastError());
+    int total = 0;
+    HIPCHK(hipMemcpy(&total, block + nb, sizeof(int), hipMemcpyDeviceToHost));
+    if (total < 0 || total > NE) return fail("primary edges on the device: kept count out of range");
+    if (total == 0) return 0;
+    std::vector<float> len((size_t) total);
+    ids.resize(3 * (size_t) total);
+    float *pmf = (float *) sc->blob.p + 4 * (size_t) d.pecdf_off;
+    HIPCHK(hipMemcpy(len.data(), pmf, sizeof(float) * (size_t) total, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ids.data(), dids, sizeof(int) * 3 * (size_t) total, hipMemcpyDeviceToHost));
+    // DiscreteDistribution::init (reference src/core/pmf.cpp:6-15): `sum` is a sequential FLOAT sum - from the lengths that came back (4 B per kept edge, device to host); the
+    // cmf and its search table are made on the device (cdf_on_device): nothing proportional to the edge count goes up
+    float sum = 0.f;
+    for (int i = 0; i < total; ++i) sum += len[(size_t) i];
+    d.n_edges = total; d.edge_sum = sum;
+    int mode = 0;
+    if (cdf_on_device(sc, pmf, pmf + total, len.data(), total, NE, sum, range, "sensor." + std::to_string(k) + ".guide", d.pe_guide, d.pe_guide_n, &mode, info, edge_bytes)) return 1;
+    if (mode == 2) cdf_sequential = true;
     return 0;
 }
 
 struct WordRange { size_t b, e; };
+// psdr_hip_scene_update_edges: per mesh the edge topology, per sensor where its primary edges come from (PSDR_EDGES_*)
+struct EdgeRequest { const psdr_edge_topology *topo; const int32_t *mode; };
 
 // Everything between a snapshot and a renderable device scene.  fresh: the handle is new.  same: PSDR_SAME_* bits the caller vouches for
 // (relative to the snapshot of the previous create / update of this handle); force_build: build the tree even if the triangle count fits.
-static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned same, bool fresh, bool force_build, psdr_update_info *info_out) {
+static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned same, bool fresh, bool force_build, psdr_update_info *info_out, const EdgeRequest *ereq = nullptr) {
     const auto t_start = std::chrono::steady_clock::now();
     psdr_update_info info{};
     const psdr_triangles &tr = s->tris;
@@ -521,8 +845,20 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
     E.cdf_off = (int) w;   w += words_for_floats(2 * (size_t) std::max(1, se.n_edges));
     const size_t sec_end = w;
     std::vector<std::pair<int, int>> pe_offs;
+    // (psdr_hip_scene_update_edges: every sensor's edge arrays are sized ONCE, to the number of edges of the meshes with edges - the kept count changes from
+    //  configure to configure, the sections behind it must not move)
+    //  ... and a scene that has been given that size keeps it under psdr_hip_scene_update too: the two calls alternate (a configure that changes nothing about the edges takes the plain one),
+    //  and a section that moved would be written and sent again
+    size_t pe_cap = ereq ? pe_capacity(s, ereq->topo) : (fresh ? 0 : sc->pe_cap);
+    for (int i = 0; !ereq && i < s->n_sensors; ++i) if ((size_t) std::max(0, s->sensors[i].n_edges) > pe_cap) pe_cap = 0;
+    const bool cap_layout = ereq != nullptr || pe_cap > 0;
+    // (... and the secondary-edge distribution: under that call a snapshot without sec_edges.pmf / cmf leaves the lengths and their CDF to the device)
+    const bool sec_dev_any = ereq && se.n_edges > 0 && se.pmf == nullptr;
+    bool dev_edges = sec_dev_any;                // some sensor's edges are selected on the device or kept from an earlier selection: their host copy in H is behind
     for (int i = 0; i < s->n_sensors; ++i) {
-        const int ne = std::max(0, s->sensors[i].n_edges);
+        if (ereq && ereq->mode[i] != PSDR_EDGES_HOST) dev_edges = true;
+        else if (ereq && (size_t) std::max(0, s->sensors[i].n_edges) > pe_cap) return fail("psdr_hip_scene_update_edges: a sensor carries more primary edges than the meshes have edges");
+        const int ne = cap_layout ? (int) pe_cap : std::max(0, s->sensors[i].n_edges);
         const int o1 = (int) w; w += 3 * (size_t) ne;
         const int o2 = (int) w; w += words_for_floats(2 * (size_t) std::max(1, ne));
         pe_offs.emplace_back(o1, o2);
@@ -547,6 +883,18 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
     T.stack_lds = uses_bvh ? std::min(kStackLds, sc->tree_max_stack) : 0;
     T.stack_depth = uses_bvh ? T.stack_lds + kTravRows : kColdRows;   // BVH: + parked rays, best hits and the pair ring of the traversal (trav4.h); brute force: cold path state (paths.h)
 
+    if (dev_edges) {
+        // the device selects (or keeps) primary edges only where nothing else about the scene moves: the tree stays, the blob stays where it is (the host's copy of such a
+        // section is behind), the world vertices of every mesh are resident or about to be computed.  Otherwise: PSDR_HIP_NEED_ROWS, nothing changed - the caller comes back
+        // with PSDR_EDGES_HOST for every sensor
+        bool ok = !fresh && !build && uses_bvh && s->geometry != nullptr && sc->blob.p && sc->blob.bytes >= 16 * w && std::getenv("PSDR_HOST_GEOMETRY") == nullptr;
+        for (int i = 0; ok && i < s->n_sensors; ++i)
+            if (ereq->mode[i] == PSDR_EDGES_KEEP)
+                ok = (size_t) i < sc->sensors.size() && sc->sensors[(size_t) i].pe_off == pe_offs[(size_t) i].first && sc->sensors[(size_t) i].pecdf_off == pe_offs[(size_t) i].second &&
+                     sc->pe_ids.size() == (size_t) s->n_sensors;
+        if (sec_dev_any) ok = ok && E.off == Eold.off && E.cdf_off == Eold.cdf_off && E.n == Eold.n;       // (the section stays where it is: the host's copy of it is behind)
+        if (!ok) { sc->T = Told; sc->E = Eold; return PSDR_HIP_NEED_ROWS; }
+    }
     if (!rows_valid) {
         const bool layout_kept = sc->blob.p && sc->blob.bytes >= 16 * w && T.trav_off == Told.trav_off && T.shade_off == Told.shade_off && T.tan_off == Told.tan_off && T.map_off == Told.map_off &&
                                  (has_tan ? 1 : 0) == Told.has_tangent && E.off == Eold.off && E.cdf_off == Eold.cdf_off && E.n == Eold.n && T.env_emitter >= 0 && Told.env_emitter >= 0 &&
@@ -556,7 +904,14 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
     // ---- the blob: device allocation with head room, pinned host copy
     bool blob_moved = false;
     if (!sc->blob.p || sc->blob.bytes < 16 * w) {
-        const size_t cap = 16 * (w + w / 4 + 64);
+        // (room for the sensors' edge arrays at the size psdr_hip_scene_update_edges gives them - every edge of the meshes with edges - so that the first such update does not move the blob)
+        size_t reserve = 0;
+        if (!ereq && uses_bvh && s->geometry && s->sppe > 0) {
+            size_t ne_all = 0;
+            for (int i = 0; i < s->n_meshes; ++i) ne_all += (size_t) std::max(0, s->geometry[i].n_edges);
+            reserve = (size_t) s->n_sensors * (3 * ne_all + words_for_floats(2 * std::max<size_t>(1, ne_all)));
+        }
+        const size_t cap = 16 * (w + w / 4 + 64 + reserve);
         void *fresh_p = nullptr;
         HIPCHK(hipMalloc(&fresh_p, cap));
         if (sc->blob.p) {
@@ -591,6 +946,10 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
             if (geometry_on_device(sc, s, geo, has_tan && !same_tan, !same_sec, info, dev_geo)) return 1;
             if (!dev_geo && !rows_valid) { sc->T = Told; sc->E = Eold; return PSDR_HIP_NEED_ROWS; }
         }
+        // (triangles the host writes below leave the device's world vertices behind: the next geometry_on_device recomputes every mesh)
+        if (!dev_geo && (geo || !same_tan)) sc->geo_world_current = false;
+        if (dev_edges && !sc->geo_world_current) { sc->T = Told; sc->E = Eold; return PSDR_HIP_NEED_ROWS; }
+        if (sec_dev_any && !same_sec && !dev_geo) { sc->T = Told; sc->E = Eold; return PSDR_HIP_NEED_ROWS; }
     }
     // (the pinned host copy of a section the device wrote is behind the device's; it is only ever sent after the host has rewritten the whole section from the snapshot -
     //  a change of the section itself, or a moved allocation, both of which write it first)
@@ -710,11 +1069,31 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
 
     // ---- secondary edges
     const bool write_sec = !same_sec || blob_moved || E.off != Eold.off || E.cdf_off != Eold.cdf_off || E.n != Eold.n;
-    if (write_sec && se.n_edges > 0 && dev_geo) {
+    if (sec_dev_any && write_sec && !dev_geo) return fail("psdr_hip_scene_update_edges: no secondary-edge distribution in the snapshot and none to compute");
+    int sec_cdf_mode = 0;
+    int64_t sec_bytes = 0;                                          // what goes up for the secondary-edge DISTRIBUTION (pmf, cmf, search table)
+    if (sec_dev_any && !write_sec) E.sum = Eold.sum;               // (the device's distribution stands: its sum is the one it was given then)
+    if (write_sec && se.n_edges > 0 && dev_geo && sec_dev_any) {
+        // the rows are the device's, and so is the distribution over them: lengths, then the cmf and its search table (cdf_on_device); the lengths come back for the float sum
+        const int ne = se.n_edges;
+        DevBuf &rg = sc->buf("sec.range");
+        if (rg.ensure(2 * sizeof(int))) return 1;
+        float *pmf = (float *) sc->blob.p + 4 * (size_t) E.cdf_off;
+        hipLaunchKernelGGL(k_cdf_range_reset, dim3(1), dim3(1), 0, nullptr, (int *) rg.p);
+        hipLaunchKernelGGL(k_se_length, dim3((unsigned) ((ne + 255) / 256)), dim3(256), 0, nullptr, sc->buf("geo.edges").as<int>(), sc->buf("geo.world").as<float>(), pmf, (int *) rg.p, ne);
+        HIPCHK(hipGetLastError());
+        std::vector<float> len((size_t) ne);
+        HIPCHK(hipMemcpy(len.data(), pmf, sizeof(float) * (size_t) ne, hipMemcpyDeviceToHost));
+        float sum = 0.f;
+        for (int i = 0; i < ne; ++i) sum += len[(size_t) i];
+        E.sum = sum;
+        if (cdf_on_device(sc, pmf, pmf + ne, len.data(), ne, ne, sum, (const int *) rg.p, "sec.guide", E.guide, E.guide_n, &sec_cdf_mode, info, sec_bytes)) return 1;
+    } else if (write_sec && se.n_edges > 0 && dev_geo) {
         // (the rows are the device's; the distribution over the edges - a sequential float prefix sum - comes from the host)
         std::memcpy(H + 4 * (size_t) E.cdf_off, se.pmf, sizeof(float) * (size_t) se.n_edges);
         std::memcpy(H + 4 * (size_t) E.cdf_off + (size_t) se.n_edges, se.cmf, sizeof(float) * (size_t) se.n_edges);
         mark((size_t) E.cdf_off, sec_end);
+        sec_bytes += (int64_t) (8 * (size_t) se.n_edges);
     } else if (write_sec && se.n_edges > 0) {
         parallel_for((size_t) se.n_edges, 8192, [&](size_t b0, size_t e0) {
             const float z3[3] = {0.f, 0.f, 0.f};
@@ -733,8 +1112,10 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
             }
         });
         mark((size_t) E.off, sec_end);
+        sec_bytes += (int64_t) (8 * (size_t) se.n_edges);
     }
-    if (write_sec) {
+    if (write_sec && sec_cdf_mode != 0) { /* (cdf_on_device has made the table) */ }
+    else if (write_sec) {
         E.guide = nullptr; E.guide_n = 0;
         if (se.n_edges > 0 && se.cmf) {              // every sample of the secondary-edge term starts with this search (17 dependent loads for config 5's 122 885 edges)
             std::vector<int> guide;
@@ -742,6 +1123,7 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
             if (!guide.empty()) {
                 if (sync_named(sc, "sec.guide", guide.data(), guide.size() * sizeof(int), false, E.guide, info)) return 1;
                 E.guide_n = (int) guide.size() - 1;
+                sec_bytes += (int64_t) (guide.size() * sizeof(int));
             }
         }
     } else { E.guide = Eold.guide; E.guide_n = Eold.guide_n; }
@@ -752,6 +1134,14 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
     sc->sensors.assign((size_t) s->n_sensors, SensorDev{});
     sc->sensor_w2s.assign(16 * (size_t) s->n_sensors, 0.f);
     sc->live_host.resize((size_t) s->n_sensors);
+    sc->pe_ids.resize((size_t) s->n_sensors);
+    int64_t edge_bytes = 0;
+    int edge_path = sec_cdf_mode;
+    bool any_sensor_dev = false;
+    for (int k = 0; ereq && k < s->n_sensors; ++k) any_sensor_dev = any_sensor_dev || ereq->mode[k] == PSDR_EDGES_DEVICE;
+    if (any_sensor_dev && pe_sync_topology(sc, s, ereq->topo, edge_bytes)) return 1;
+    info.bytes_uploaded += edge_bytes;
+    edge_bytes += sec_bytes;
     for (int k = 0; k < s->n_sensors; ++k) {
         const psdr_sensor_rec &r = s->sensors[k];
         SensorDev &d = sc->sensors[(size_t) k];
@@ -762,8 +1152,19 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
         for (int q = 0; q < 3; ++q) { d.cam_pos[q] = r.cam_pos[q]; d.cam_dir[q] = r.cam_dir[q]; }
         d.inv_area = r.inv_area; d.n_edges = r.n_edges; d.edge_sum = r.edge_sum; d.ortho = r.orthographic;
         d.pe_off = pe_offs[(size_t) k].first; d.pecdf_off = pe_offs[(size_t) k].second;
-        const bool write_pe = !same_prim || blob_moved || !od || od->pe_off != d.pe_off || od->pecdf_off != d.pecdf_off || od->n_edges != d.n_edges;
-        if (write_pe) {
+        const int pe_mode = ereq ? ereq->mode[k] : PSDR_EDGES_HOST;
+        // (a sensor without edges before and after, where it was: nothing to write)
+        const bool still_empty = r.n_edges <= 0 && od && od->n_edges <= 0 && !blob_moved && od->pe_off == d.pe_off && od->pecdf_off == d.pecdf_off;
+        const bool write_pe = pe_mode == PSDR_EDGES_HOST && !still_empty && (!same_prim || blob_moved || !od || od->pe_off != d.pe_off || od->pecdf_off != d.pecdf_off || od->n_edges != d.n_edges);
+        if (pe_mode == PSDR_EDGES_DEVICE) {
+            bool sequential = false;
+            if (primary_edges_on_device(sc, r, k, d, info, edge_bytes, sequential)) return 1;
+            edge_path = std::max(edge_path, sequential ? 2 : 1);
+        } else if (pe_mode == PSDR_EDGES_KEEP) {
+            d.n_edges = od->n_edges; d.edge_sum = od->edge_sum; d.pe_guide = od->pe_guide; d.pe_guide_n = od->pe_guide_n;
+        } else if (write_pe) {
+            sc->pe_ids[(size_t) k].clear();
+            edge_bytes += (int64_t) (16 * (3 * (size_t) std::max(0, r.n_edges) + words_for_floats(2 * (size_t) std::max(1, r.n_edges))));
             parallel_for((size_t) std::max(0, r.n_edges), 8192, [&](size_t ib, size_t ie) {
               for (size_t i = ib; i < ie; ++i) {
                 const size_t pw = (size_t) d.pe_off + 3 * (size_t) i;
@@ -775,7 +1176,9 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
                 H[4 * (size_t) d.pecdf_off + (size_t) r.n_edges + (size_t) i] = r.edge_cmf[i];
               }
             });
-            mark((size_t) d.pe_off, (size_t) d.pecdf_off + words_for_floats(2 * (size_t) std::max(1, r.n_edges)));
+            // (two ranges: under psdr_hip_scene_update_edges the section has room for every edge and the CDF starts behind that room)
+            mark((size_t) d.pe_off, (size_t) d.pe_off + 3 * (size_t) std::max(0, r.n_edges));
+            mark((size_t) d.pecdf_off, (size_t) d.pecdf_off + words_for_floats(2 * (size_t) std::max(1, r.n_edges)));
             d.pe_guide = nullptr; d.pe_guide_n = 0;
             if (r.n_edges > 0 && r.edge_cmf) {       // a sample of the primary-edge term starts with this search (15 dependent loads for config 5's 26 592 edges)
                 std::vector<int> guide;
@@ -783,6 +1186,7 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
                 if (!guide.empty()) {
                     if (sync_named(sc, "sensor." + std::to_string(k) + ".guide", guide.data(), guide.size() * sizeof(int), false, d.pe_guide, info)) return 1;
                     d.pe_guide_n = (int) guide.size() - 1;
+                    edge_bytes += (int64_t) (guide.size() * sizeof(int));
                 }
             }
         } else { d.pe_guide = od->pe_guide; d.pe_guide_n = od->pe_guide_n; }
@@ -990,7 +1394,7 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
         // the topology no longer fits the geometry: build again (everything that depends on the triangle order is rewritten)
         if (!(cost <= kRebuildFactor * sc->cost_built)) {
             if (!rows_valid) return PSDR_HIP_NEED_ROWS;         // (the rows on the device are this state's, the tables are complete: the caller comes back with its rows and the tree is built then)
-            return scene_sync(sc, s, 0, false, true, info_out);
+            return scene_sync(sc, s, 0, false, true, info_out, ereq);
         }
     }
 
@@ -1035,6 +1439,8 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
     }
     HIPCHK(hipStreamSynchronize(nullptr));
     info.ms_total = ms_since(t_start);
+    sc->edge_path = edge_path; sc->edge_bytes = edge_bytes;
+    sc->pe_cap = cap_layout ? pe_cap : 0;
     sc->last_info = info;
     if (info_out) *info_out = info;
     return 0;
@@ -1063,6 +1469,100 @@ int psdr_hip_scene_update(psdr_hip_scene *scene, const psdr_scene_snapshot *s, u
     scene->poisoned = rc != 0;
     if (rc) scene->tree_tris = -1;
     return rc;
+}
+
+int psdr_hip_scene_update_edges(psdr_hip_scene *scene, const psdr_scene_snapshot *s, uint32_t same, const psdr_edge_topology *topo, const int32_t *sensor_mode, psdr_update_info *info) {
+    if (!scene || !s || !topo || !sensor_mode) return fail("psdr_hip_scene_update_edges: null argument");
+    if (s->abi_version != PSDR_HIP_ABI_VERSION) return fail("psdr_hip_scene_update_edges: ABI version mismatch");
+    for (int i = 0; i < s->n_sensors; ++i)
+        if (sensor_mode[i] < PSDR_EDGES_HOST || sensor_mode[i] > PSDR_EDGES_KEEP) return fail("psdr_hip_scene_update_edges: unknown sensor mode");
+    const EdgeRequest er{topo, sensor_mode};
+    const bool was_poisoned = scene->poisoned;               // (as psdr_hip_scene_update)
+    const int rc = scene_sync(scene, s, was_poisoned ? 0u : same, false, was_poisoned, info, &er);
+    if (rc == PSDR_HIP_NEED_ROWS) return rc;
+    scene->poisoned = rc != 0;
+    if (rc) scene->tree_tris = -1;
+    return rc;
+}
+
+int psdr_hip_scene_primary_edges(const psdr_hip_scene *sc, int32_t sensor_id, int32_t *count, int32_t *ids, int32_t cap, float *edge_sum) {
+    if (!sc || !count) return fail("null argument");
+    if (sensor_id < 0 || sensor_id >= (int) sc->sensors.size()) return fail("Invalid sensor id!");
+    const int n = sc->sensors[(size_t) sensor_id].n_edges;
+    *count = n;
+    if (edge_sum) *edge_sum = sc->sensors[(size_t) sensor_id].edge_sum;
+    if (ids) {
+        const std::vector<int32_t> *v = (size_t) sensor_id < sc->pe_ids.size() ? &sc->pe_ids[(size_t) sensor_id] : nullptr;
+        if (!v || v->size() != 3 * (size_t) n) return fail("psdr_hip_scene_primary_edges: this sensor's edges were not selected on the device");
+        if (cap < n) return fail("psdr_hip_scene_primary_edges: ids has room for fewer edges than the sensor keeps");
+        if (n > 0) std::memcpy(ids, v->data(), sizeof(int32_t) * 3 * (size_t) n);
+    }
+    return 0;
+}
+
+int psdr_hip_scene_edge_path(const psdr_hip_scene *sc, int32_t *path, int64_t *edge_bytes) {
+    if (!sc) return fail("null scene");
+    if (path) *path = sc->edge_path;
+    if (edge_bytes) *edge_bytes = sc->edge_bytes;
+    return 0;
+}
+
+// Test aid (synchronises, downloads the sections): every sensor's primary-edge rows and distribution and the secondary-edge distribution of the device blob against
+// what the host path would write from `snapshot`.  -> number of 32-bit words that differ (a count or a sum that differs counts too).
+int psdr_hip_scene_check_edges(const psdr_hip_scene *sc, const psdr_scene_snapshot *s, int64_t *mismatches) {
+    if (!sc || !s || !mismatches) return fail("null argument");
+    *mismatches = 0;
+    if ((size_t) s->n_sensors != sc->sensors.size()) return fail("psdr_hip_scene_check_edges: another sensor count than the device scene's");
+    HIPCHK(hipDeviceSynchronize());
+    long long bad = 0;
+    auto fetch = [&](size_t off_floats, size_t n, std::vector<float> &dst) -> int {
+        dst.resize(n);
+        if (n) HIPCHK(hipMemcpy(dst.data(), (const float *) sc->blob.p + off_floats, sizeof(float) * n, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    auto diff = [&](const float *dev, const float *host, size_t n) { for (size_t i = 0; i < n; ++i) bad += std::memcmp(dev + i, host + i, 4) != 0 ? 1 : 0; };
+    // the search table of a distribution against the one the host path builds from the host's cmf (scene_obj.h::build_cdf_guide)
+    auto guide_diff = [&](const float *cmf, int n, float sum, const int *dev_guide, int dev_n) -> int {
+        std::vector<int> want, got;
+        build_cdf_guide(cmf, n, sum, want, 4);
+        const int want_n = want.empty() ? 0 : (int) want.size() - 1;
+        if (want_n != dev_n || (want_n > 0 && !dev_guide)) { bad += 1 + std::abs(want_n - dev_n); return 0; }
+        if (want_n == 0) return 0;
+        got.resize(want.size());
+        HIPCHK(hipMemcpy(got.data(), dev_guide, sizeof(int) * got.size(), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < want.size(); ++i) bad += want[i] != got[i] ? 1 : 0;
+        return 0;
+    };
+    std::vector<float> rows, cdf;
+    for (int k = 0; k < s->n_sensors; ++k) {
+        const psdr_sensor_rec &r = s->sensors[k];
+        const SensorDev &d = sc->sensors[(size_t) k];
+        const int n = std::max(0, r.n_edges);
+        if (d.n_edges != n) { bad += 1 + std::abs(d.n_edges - n); continue; }
+        if (n == 0) continue;
+        bad += std::memcmp(&d.edge_sum, &r.edge_sum, 4) != 0 ? 1 : 0;
+        if (fetch(4 * (size_t) d.pe_off, 12 * (size_t) n, rows) || fetch(4 * (size_t) d.pecdf_off, 2 * (size_t) n, cdf)) return 1;
+        const float z2[2] = {0.f, 0.f};
+        for (size_t i = 0; i < (size_t) n; ++i) {
+            const float *q = &rows[12 * i];
+            const float *dp0 = r.d_edge_p0 ? r.d_edge_p0 + 2 * i : z2, *dp1 = r.d_edge_p1 ? r.d_edge_p1 + 2 * i : z2;
+            const float h[12] = {r.edge_p0[2 * i], r.edge_p0[2 * i + 1], r.edge_p1[2 * i], r.edge_p1[2 * i + 1], dp0[0], dp0[1], dp1[0], dp1[1],
+                                 r.edge_normal[2 * i], r.edge_normal[2 * i + 1], r.edge_length[i], 0.f};
+            diff(q, h, 12);
+        }
+        diff(cdf.data(), r.edge_pmf, (size_t) n); diff(cdf.data() + n, r.edge_cmf, (size_t) n);
+        if (guide_diff(r.edge_cmf, n, r.edge_sum, d.pe_guide, d.pe_guide_n)) return 1;
+    }
+    const psdr_sec_edges &se = s->sec_edges;
+    if (std::max(0, se.n_edges) != std::max(0, sc->E.n)) bad += 1 + std::abs(se.n_edges - sc->E.n);
+    else if (se.n_edges > 0) {
+        bad += std::memcmp(&sc->E.sum, &se.sum, 4) != 0 ? 1 : 0;
+        if (fetch(4 * (size_t) sc->E.cdf_off, 2 * (size_t) se.n_edges, cdf)) return 1;
+        diff(cdf.data(), se.pmf, (size_t) se.n_edges); diff(cdf.data() + se.n_edges, se.cmf, (size_t) se.n_edges);
+        if (guide_diff(se.cmf, se.n_edges, se.sum, sc->E.guide, sc->E.guide_n)) return 1;
+    }
+    *mismatches = bad;
+    return 0;
 }
 
 int psdr_hip_scene_destroy(psdr_hip_scene *scene) { delete scene; return 0; }

@@ -139,6 +139,15 @@ struct psdr_hip_scene {
     // geometry on the device (scene_build.hip::geometry_on_device): the topology version and the counts of every mesh at the last topology upload
     std::vector<uint64_t> geo_versions;
     std::vector<int> geo_counts;
+    bool geo_world_current = false;                    // geo.world / geo.fnrm / geo.farea hold the state of EVERY mesh the device scene holds (false after the host wrote triangle rows)
+    // primary edges selected on the device (scene_build.hip::primary_edges_on_device): the edge list's key (versions, counts, flags per mesh) and length, per sensor the
+    // (mesh, v0, v1) ids of the kept edges in their order (empty: the host's arrays), what the last update did
+    std::vector<uint64_t> pe_topo_key;
+    int pe_n = 0;
+    size_t pe_cap = 0;                                 // edges every sensor's edge arrays have room for (0: sized to what each sensor keeps), psdr_hip_scene_update_edges
+    std::vector<std::vector<int32_t>> pe_ids;
+    int edge_path = 0;
+    int64_t edge_bytes = 0;
     bool poisoned = false;                             // a psdr_hip_scene_update failed midway: no rendering until an update has gone through (scene_build.hip)
 
     // The launches of one scene share mutable device scratch - the work-queue ring, the counters, the traversal-stack overflow

@@ -276,6 +276,7 @@ PYBIND11_MODULE(_psdr_core, m) {
         .def("_primary_edge_ids", [](const PerspectiveCamera &c) { return from_ivec(c.m_edges.ids, 3); })
         .def("_camera_params", [](const PerspectiveCamera &c) { return py::make_tuple(c.m_fov_x, c.m_near_clip, c.m_far_clip); })
         .def("_primary_edges", [](const PerspectiveCamera &c, bool tangent) {
+            if ((c.m_edges_on_device || c.m_edges_pending) && c.m_owner) c.m_owner->ensure_host_edges();      // (selected on the device: the host's copy on demand)
             const PrimaryEdges &e = c.m_edges;
             const size_t n = e.length.size();
             farr a({(ssize_t) n, (ssize_t) 7});
@@ -430,6 +431,7 @@ PYBIND11_MODULE(_psdr_core, m) {
         .def("_snapshot_counts", [](const Scene &s) { return py::make_tuple((int64_t) s.snap.area.size(), (int64_t) s.snap.n_sec_edges); })
         .def("_hip_handle", [](const Scene &s) { return (uintptr_t) s.m_hip; })
         .def("_check_device_rows", &Scene::check_device_rows)
+        .def("_check_device_edges", &Scene::check_device_edges)
         // test aid: psdr_hip_scene_update with this state's snapshot, except that psdr_mesh_geometry[mesh] carries a new topology version, raw vertices scaled by 2
         // (rows computed from them differ from the snapshot's) and ONE list broken as `fault` names -> (return code, psdr_hip_last_error()).  The scene object's
         // own bookkeeping is untouched: a failed update poisons the device handle, and the next configure() sends everything again
@@ -469,6 +471,8 @@ PYBIND11_MODULE(_psdr_core, m) {
             const psdr_update_info &u = s.m_last_update;
             d["tree"] = u.tree == 2 ? "built" : (u.tree == 1 ? "refitted" : "kept");
             d["reallocated"] = u.reallocated; d["bytes_uploaded"] = u.bytes_uploaded; d["sah_cost"] = u.sah_cost; d["sah_cost_built"] = u.sah_cost_built;
+            d["edge_path"] = s.m_edge_path >= 1 ? "device" : "host"; d["edge_bytes"] = s.m_edge_bytes;
+            d["edge_cdf"] = s.m_edge_path == 1 ? "scan" : (s.m_edge_path == 2 ? "sequential" : "host");
             d["ms_host"] = s.m_ms_host; d["ms_tree"] = u.ms_tree; d["ms_fill"] = u.ms_fill; d["ms_upload"] = u.ms_upload; d["ms_total"] = u.ms_total;
             return d; })
         .def_readwrite("_always_rebuild", &Scene::m_always_rebuild)

@@ -1,6 +1,7 @@
 // scene_host.cpp — host scene model: OBJ loading, Mesh/Camera/Scene::configure, snapshot assembly and
 // the render drivers that call libpsdr_hip.so.  Reference sites are cited per function.
 #include "scene_host.h"
+#include "edge_select.h"
 #include "../common/envmath.h"
 #include "../common/threads.h"
 
@@ -444,34 +445,47 @@ void PerspectiveCamera::configure(const Scene &scene, bool keep_edges) {
 
     m_edges = PrimaryEdges();
     m_enable_edges = false;
+    m_edges_on_device = false; m_edges_pending = false;
     if (o.sppe <= 0) return;
+    // the device selects this sensor's edges in the next upload (Scene::upload, psdr_hip_scene_update_edges): nothing proportional to an edge count is computed here
+    if (scene.device_edges() && keep_edges) { m_edges_pending = true; return; }          // (sppe > 0 here)
+    select_edges(scene, keep_edges);
+}
+
+// one byte per edge: the uv-seam mask of the keep test (edge_select.h), a function of the topology alone
+const std::vector<uint8_t> &Mesh::edge_uv_seams() const {
+    if (uv_seam_topo == m_topo_version && uv_seam.size() == edges.size()) return uv_seam;
+    uv_seam.assign(edges.size(), 0);
+    if (m_has_uv)
+        for (size_t i = 0; i < edges.size(); ++i) {
+            const MeshEdge &e = edges[i];
+            uv_seam[i] = edge_uv_seam(&face_uv_indices[3 * (size_t) e.f0], e.f1 >= 0 ? &face_uv_indices[3 * (size_t) e.f1] : nullptr) ? 1 : 0;
+        }
+    uv_seam_topo = m_topo_version;
+    return uv_seam;
+}
+
+// the primary edges on the host (perspective.cpp:52-151): the keep test and the rows are edge_select.h's, shared with the device
+void PerspectiveCamera::select_edges(const Scene &scene, bool keep_edges) {
+    m_edges = PrimaryEdges();
+    m_enable_edges = false;
+    m_edges_on_device = false; m_edges_pending = false;
+    if (scene.m_opts.sppe <= 0) return;
+    DM4 w2s;               // (world_to_sample as configure() split it into the record: the very values and tangents)
+    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) w2s.m[i][j] = DF(rec.world_to_sample[4 * i + j], rec.d_world_to_sample[4 * i + j]);
     PrimaryEdges pe;
-    const D3 cpos = {DF(pos.x.v), DF(pos.y.v), DF(pos.z.v)};
     for (const Mesh *mesh : scene.m_meshes) {
         if (!mesh->m_enable_edges) continue;
         // pass 1 (parallel): which edges are kept; pass 2 (parallel): their rows at the positions an in-order walk would give them
         const int ne = (int) mesh->edges.size();
         std::vector<uint8_t> keep_flag((size_t) ne, 0);
+        const std::vector<uint8_t> &seam = mesh->edge_uv_seams();
         psdr::parallel_for((size_t) ne, 4096, [&](size_t eb, size_t ee) {
           for (size_t i = eb; i < ee; ++i) {
             const MeshEdge &e = mesh->edges[i];
-            const bool valid = e.f1 >= 0;
-            const float *t0 = &mesh->face_p0n[6 * (size_t) e.f0];          // (first vertex and unit normal of the face: Mesh::configure keeps them whether or not it wrote the full rows)
-            const D3 e0 = dnormalize(cpos - fvec(t0)), n0 = fvec(t0 + 3);
-            D3 e1 = dnormalize(cpos), n1 = {DF(0.f), DF(0.f), DF(0.f)};        // masked gathers return zeros
-            if (valid) { const float *t1 = &mesh->face_p0n[6 * (size_t) e.f1]; e1 = dnormalize(cpos - fvec(t1)); n1 = fvec(t1 + 3); }
-            bool uv_mask = false;
-            if (mesh->m_has_uv) {
-                int b[3] = {0, 0, 0}, cut = 0;
-                if (valid) for (int k = 0; k < 3; ++k) b[k] = mesh->face_uv_indices[3 * e.f1 + k];
-                for (int k = 0; k < 3; ++k) { const int a = mesh->face_uv_indices[3 * e.f0 + k]; if (a == b[0] || a == b[1] || a == b[2]) ++cut; }
-                uv_mask = cut != 2;
-            }
-            bool keep;
-            if (mesh->m_use_face_normals) keep = !(valid && ((fdot(e0, n0) < Epsilon && fdot(e1, n1) < Epsilon) || fdot(n0, n1) > 1.f - Epsilon));
-            else keep = !valid || ((fdot(e0, n0) > Epsilon) != (fdot(e1, n1) > Epsilon));
-            if (mesh->m_has_uv) keep = keep || uv_mask;
-            keep_flag[i] = keep ? 1 : 0;
+            // (first vertex and unit normal of the face: Mesh::configure keeps them whether or not it wrote the full rows)
+            keep_flag[i] = edge_keep(rec.cam_pos, &mesh->face_p0n[6 * (size_t) e.f0], e.f1 >= 0 ? &mesh->face_p0n[6 * (size_t) e.f1] : nullptr, mesh->m_use_face_normals,
+                                     mesh->m_has_uv, seam[i] != 0) ? 1 : 0;
           }
         });
         std::vector<int> kept_ids;
@@ -485,15 +499,13 @@ void PerspectiveCamera::configure(const Scene &scene, bool keep_edges) {
           for (size_t j = jb; j < je; ++j) {
             const MeshEdge &e = mesh->edges[(size_t) kept_ids[j]];
             const size_t r = base + j;
-            const D3 q0 = xform_pos(w2s, dvec(&mesh->vertex_positions[3 * e.v0], &mesh->d_vertex_positions[3 * e.v0])),
-                     q1 = xform_pos(w2s, dvec(&mesh->vertex_positions[3 * e.v1], &mesh->d_vertex_positions[3 * e.v1]));
-            float ex = q1.x.v - q0.x.v, ey = q1.y.v - q0.y.v;
-            const float len = std::sqrt(std::fmaf(ey, ey, ex * ex));
-            ex /= len; ey /= len;
-            pe.p0[2 * r] = q0.x.v; pe.p0[2 * r + 1] = q0.y.v; pe.p1[2 * r] = q1.x.v; pe.p1[2 * r + 1] = q1.y.v;
-            pe.d_p0[2 * r] = q0.x.d; pe.d_p0[2 * r + 1] = q0.y.d; pe.d_p1[2 * r] = q1.x.d; pe.d_p1[2 * r + 1] = q1.y.d;
-            pe.normal[2 * r] = -ey; pe.normal[2 * r + 1] = ex;
-            pe.length[r] = len;
+            const PrimEdgeRow row = edge_row(w2s, dvec(&mesh->vertex_positions[3 * e.v0], &mesh->d_vertex_positions[3 * e.v0]),
+                                             dvec(&mesh->vertex_positions[3 * e.v1], &mesh->d_vertex_positions[3 * e.v1]));
+            for (int k = 0; k < 2; ++k) {
+                pe.p0[2 * r + k] = row.p0[k]; pe.p1[2 * r + k] = row.p1[k]; pe.d_p0[2 * r + k] = row.d_p0[k]; pe.d_p1[2 * r + k] = row.d_p1[k];
+                pe.normal[2 * r + k] = row.normal[k];
+            }
+            pe.length[r] = row.length;
             pe.ids[3 * r] = mesh->m_mesh_id; pe.ids[3 * r + 1] = e.v0; pe.ids[3 * r + 2] = e.v1;
           }
         });
@@ -535,6 +547,7 @@ void Scene::add_Sensor(const Sensor *sensor) {       // scene.cpp:107-126 (the s
     const PerspectiveCamera *pc = dynamic_cast<const PerspectiveCamera *>(sensor);
     PSDR_ASSERT_MSG(pc != nullptr, "Unknown sensor type!");
     m_sensors.push_back(new PerspectiveCamera(*pc));
+    m_sensors.back()->m_owner = this;          // (the copy lives and dies with this scene)
     m_num_sensors = (int) m_sensors.size();
     rebuild_param_map();
 }
@@ -686,6 +699,15 @@ void Scene::configure_host(const std::vector<int> &active_sensor) {
         // (scenes of at most 64 triangles are traced by brute force: their device scene always takes the host's rows)
         m_lean = m_hip != nullptr && !m_always_rebuild && m_device_rows_ok && has_env && total_faces > 64 && keys_now == m_snap_keys && std::getenv("PSDR_HOST_GEOMETRY") == nullptr;
     }
+    // ... and, with the world vertices resident on the device, leaves the primary edges of the sensors it configures to the upload (psdr_hip_scene_update_edges)
+    // GATE (measured, LABNOTES: one MI355X, the blob of config 5 at four sizes, configure() alone, median of 20): with 1920 edges the selection on the device LOSES to the host loop -
+    // 0.35 against 0.29 ms after a vertex move, 0.12 against 0.07 ms after a camera move: three launches, the distribution's and two read-backs per sensor cost more than walking so few
+    // edges - with 7680 it wins (0.43 / 0.54, 0.11 / 0.20), with 30 720 and 122 885 by a factor of two to three.  The crossover lies between 1920 and 7680 edges; the gate sits at their
+    // geometric mean.  PSDR_DEVICE_EDGES_MIN = n (test knob, read per configure) moves it.
+    size_t edges_min = 3840, edges_all = 0;
+    if (const char *e = std::getenv("PSDR_DEVICE_EDGES_MIN")) edges_min = (size_t) std::max(0, std::atoi(e));
+    for (const Mesh *mesh : m_meshes) if (mesh->m_enable_edges) edges_all += (size_t) 3 * (size_t) mesh->m_num_faces / 2;        // (~ the edge count of a closed mesh; the list itself may not be built yet)
+    m_device_edges = m_lean && edges_all >= edges_min;
     for (Mesh *mesh : m_meshes) { mesh->m_lean = m_lean; mesh->configure(); }          // (does nothing for a mesh whose inputs are those of its previous run)
     auto key_of = [](const Mesh *m) { return MeshKey{m, m->m_topo_version, m->m_num_faces, m->m_bsdf_id, m->m_emitter_id, m->m_has_uv, m->m_use_face_normals, m->m_enable_edges}; };
     // rows [face_offset, face_offset + n_faces) of the triangle arrays for one mesh: the values and / or the tangents
@@ -762,6 +784,8 @@ void Scene::configure_host(const std::vector<int> &active_sensor) {
 
     // sensors: only the active ones keep their primary-edge list (scene.cpp:381-416)
     std::vector<size_t> num_edges;
+    m_log_sensors.clear();
+    bool log_after_upload = false;
     for (int sid = 0; sid < m_num_sensors; ++sid) {
         const bool active = std::find(active_sensor.begin(), active_sensor.end(), sid) != active_sensor.end();
         PerspectiveCamera *cam = static_cast<PerspectiveCamera *>(m_sensors[sid]);
@@ -783,13 +807,18 @@ void Scene::configure_host(const std::vector<int> &active_sensor) {
         }
         if (!cam->m_orthographic)      // only PerspectiveCamera positions extend the scene box (scene.cpp:383-387, 410-414)
             for (int k = 0; k < 3; ++k) { m_lower[k] = std::min(m_lower[k], cam->rec.cam_pos[k]); m_upper[k] = std::max(m_upper[k], cam->rec.cam_pos[k]); }
-        if (m_opts.sppe > 0 && (active || active_sensor.empty())) num_edges.push_back(cam->m_enable_edges ? cam->m_edges.length.size() : 1);
+        if (m_opts.sppe > 0 && (active || active_sensor.empty())) {
+            num_edges.push_back(cam->m_enable_edges ? cam->m_edges.ids.size() / 3 : 1);
+            m_log_sensors.push_back(sid);
+            log_after_upload = log_after_upload || cam->m_edges_pending;       // (the device counts them: Scene::upload writes the line)
+        }
     }
+    if (!log_after_upload) m_log_sensors.clear();
     if (m_opts.log_level > 0) {
         std::ostringstream oss;
         oss << "AABB: [lower = [[" << m_lower[0] << ", " << m_lower[1] << ", " << m_lower[2] << "]], upper = [[" << m_upper[0] << ", " << m_upper[1] << ", " << m_upper[2] << "]]]";
         log(oss.str());
-        if (m_opts.sppe > 0 && !num_edges.empty()) {
+        if (m_opts.sppe > 0 && !num_edges.empty() && !log_after_upload) {
             std::ostringstream o2; o2 << "(" << num_edges[0];
             for (size_t i = 1; i < num_edges.size(); ++i) o2 << ", " << num_edges[i];
             o2 << ") primary edges initialized.";
@@ -999,27 +1028,12 @@ void Scene::configure_host(const std::vector<int> &active_sensor) {
         m_sec_geo = geo_sum; m_sec_tan = tan_sum; m_sec_sppse = m_opts.sppse; m_sec_layout = m_layout_version;
     }
     if (m_opts.sppse > 0 && !sec_same) {
-        std::vector<float> pmf;
         size_t total_edges = 0;
         for (const Mesh *mesh : m_meshes) if (mesh->m_enable_edges) total_edges += mesh->edges.size();
-        pmf.resize(total_edges);
-        size_t base = 0;
-        for (const Mesh *mesh : m_meshes) {          // the distribution over the edges (~ their lengths): always
-            if (!mesh->m_enable_edges) continue;
-            const int ne = (int) mesh->edges.size();
-            const float *P = mesh->vertex_positions.data();
-            psdr::parallel_for((size_t) ne, 4096, [&](size_t eb, size_t ee) {
-              for (size_t i = eb; i < ee; ++i) {
-                const MeshEdge &e = mesh->edges[i];
-                float e1[3];
-                for (int k = 0; k < 3; ++k) e1[k] = P[3 * e.v1 + k] - P[3 * e.v0 + k];
-                pmf[base + i] = std::sqrt(std::fmaf(e1[2], e1[2], std::fmaf(e1[1], e1[1], e1[0] * e1[0])));
-              }
-            });
-            base += (size_t) ne;
-        }
-        S.n_sec_edges = (int) pmf.size();
-        if (!pmf.empty()) S.sec_edge_distrb.init(pmf);
+        S.n_sec_edges = (int) total_edges;
+        // the distribution over the edges (~ their lengths): a lean configure leaves it to the device as well (psdr_hip_scene_update_edges) - and to ensure_full_snapshot
+        m_sec_distrb_stale = true;
+        if (!m_device_edges) fill_sec_distrb();
         m_sec_rows_stale = true;
         if (!m_lean) fill_sec_rows();                 // (a lean configure leaves the row arrays to ensure_full_snapshot: the device computes its rows itself)
         if (m_opts.log_level > 0) { std::ostringstream oss; oss << S.n_sec_edges << " secondary edges initialized."; log(oss.str()); }
@@ -1069,6 +1083,28 @@ void Scene::configure_host(const std::vector<int> &active_sensor) {
     if (env_cells_rebuilt) same &= ~PSDR_SAME_ENV_TEXELS;
     m_same &= same;              // (several configure_host() calls may pass before the next upload)
     m_host_ready = true;
+}
+
+// Scene::m_sec_edge_distrb (scene.cpp:559-563): the edge lengths (edge_select.h::edge_length3, shared with the device) and their DiscreteDistribution
+void Scene::fill_sec_distrb() {
+    Snapshot &S = snap;
+    std::vector<float> pmf((size_t) S.n_sec_edges);
+    size_t base = 0;
+    for (const Mesh *mesh : m_meshes) {
+        if (!mesh->m_enable_edges || pmf.empty()) continue;
+        const int ne = (int) mesh->edges.size();
+        const float *P = mesh->vertex_positions.data();
+        psdr::parallel_for((size_t) ne, 4096, [&](size_t eb, size_t ee) {
+          for (size_t i = eb; i < ee; ++i) {
+            const MeshEdge &e = mesh->edges[i];
+            pmf[base + i] = edge_length3(P + 3 * (size_t) e.v0, P + 3 * (size_t) e.v1);
+          }
+        });
+        base += (size_t) ne;
+    }
+    S.sec_edge_distrb = Distrb();
+    if (!pmf.empty()) S.sec_edge_distrb.init(pmf);
+    m_sec_distrb_stale = false;
 }
 
 // SecondaryEdgeInfo rows of the snapshot (mesh.cpp:355-369, scene.cpp:546-571): every edge of every mesh with edges, in mesh order
@@ -1129,6 +1165,7 @@ void Scene::ensure_full_snapshot() {
         face_offset += (size_t) mesh->m_num_faces;
     }
     if (m_sec_rows_stale) fill_sec_rows();
+    if (m_sec_distrb_stale && S.n_sec_edges > 0) fill_sec_distrb();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1283,7 +1320,7 @@ Scene::GeometryAdjoint Scene::chain_geometry(int sensor_id, const float *g_tri, 
 // the configured snapshot as the C ABI's struct (pointers into `snap`, the sensors' edge lists and the meshes)
 void Scene::fill_snapshot(psdr_scene_snapshot &sn, bool full) {
     PSDR_ASSERT_MSG(m_host_ready, "configure_host() first");
-    if (full) ensure_full_snapshot();
+    if (full) { ensure_full_snapshot(); ensure_host_edges(); }
     Snapshot &S = snap;
     S.sensors.clear();
     sn = psdr_scene_snapshot{};
@@ -1307,12 +1344,14 @@ void Scene::fill_snapshot(psdr_scene_snapshot &sn, bool full) {
     if (S.n_sec_edges > 0) {
         se.p0 = S.se_p0.data(); se.e1 = S.se_e1.data(); se.n0 = S.se_n0.data(); se.n1 = S.se_n1.data(); se.p2 = S.se_p2.data();
         se.is_boundary = S.se_boundary.data(); se.d_p0 = S.se_d_p0.data(); se.d_e1 = S.se_d_e1.data();
-        se.pmf = S.sec_edge_distrb.pmf.data(); se.cmf = S.sec_edge_distrb.cmf.data(); se.sum = S.sec_edge_distrb.sum;
+        // (a lean configure left the distribution to the device: no pmf / cmf - psdr_hip_scene_update_edges computes them, or answers PSDR_HIP_NEED_ROWS)
+        if (!m_sec_distrb_stale) { se.pmf = S.sec_edge_distrb.pmf.data(); se.cmf = S.sec_edge_distrb.cmf.data(); se.sum = S.sec_edge_distrb.sum; }
     }
     for (Sensor *s : m_sensors) {
         PerspectiveCamera *cam = static_cast<PerspectiveCamera *>(s);
         psdr_sensor_rec r = cam->rec;
-        r.n_edges = cam->m_enable_edges ? (int) cam->m_edges.length.size() : 0;
+        // (edges the device selected, or will select in this upload, are not held here: psdr_hip_scene_update_edges ignores the record's edge fields of such a sensor)
+        r.n_edges = cam->m_enable_edges && !cam->m_edges_on_device && !cam->m_edges_pending ? (int) cam->m_edges.length.size() : 0;
         if (r.n_edges > 0) {
             const PrimaryEdges &pe = cam->m_edges;
             r.edge_p0 = pe.p0.data(); r.edge_p1 = pe.p1.data(); r.d_edge_p0 = pe.d_p0.data(); r.d_edge_p1 = pe.d_p1.data();
@@ -1354,6 +1393,33 @@ void Scene::fill_snapshot(psdr_scene_snapshot &sn, bool full) {
     if (stale) PSDR_ASSERT_MSG(sn.geometry != nullptr, "lean snapshot without geometry");
 }
 
+// the host's copy of the primary edges the device selected (or was about to): the same keep test and rows (edge_select.h) on the same world vertices and face normals
+void Scene::ensure_host_edges() {
+    for (Sensor *s : m_sensors) {
+        if (!s->m_edges_on_device && !s->m_edges_pending) continue;
+        const std::vector<int> ids = s->m_edges.ids;
+        const bool selected = s->m_edges_on_device;
+        s->select_edges(*this, true);
+        if (selected) PSDR_ASSERT_MSG(ids == s->m_edges.ids, "the device selected other primary edges than the host");
+    }
+}
+
+// test aid: words in which the device's primary-edge arrays and both edge distributions differ from what the host path writes (psdr_hip_scene_check_edges)
+int64_t Scene::check_device_edges() {
+    PSDR_ASSERT_MSG(m_hip != nullptr && m_configured, "configure() first");
+    // (the host's selection for this state, without giving up the device's: the next configure() keeps or selects on the device as before)
+    std::vector<std::pair<bool, bool>> flags;
+    for (Sensor *s : m_sensors) flags.emplace_back(s->m_edges_on_device, s->m_edges_pending);
+    psdr_scene_snapshot sn;
+    fill_snapshot(sn);
+    int64_t bad = -1;
+    const int rc = psdr_hip_scene_check_edges(m_hip, &sn, &bad);
+    for (size_t i = 0; i < m_sensors.size(); ++i)
+        if (flags[i].first) { Sensor *s = m_sensors[i]; PrimaryEdges ids_only; ids_only.ids = s->m_edges.ids; s->m_edges = std::move(ids_only); s->m_edges_on_device = true; }
+    hip_check(rc);
+    return bad;
+}
+
 // test aid: words of the device's triangle / secondary-edge rows that differ from the rows the host path would write (psdr_hip_scene_check_rows)
 int64_t Scene::check_device_rows() {
     PSDR_ASSERT_MSG(m_hip != nullptr && m_configured, "configure() first");
@@ -1368,7 +1434,36 @@ void Scene::upload() {
     psdr_scene_snapshot sn;
     // a lean configure_host left the rows out: the device is asked first whether it can do without them
     const bool try_lean = m_lean && m_hip != nullptr && !m_always_rebuild;
+    // ... and the sensors' primary edges: selected on the device (pending), kept from an earlier selection, or the host's arrays
+    std::vector<int32_t> edge_mode(m_sensors.size(), PSDR_EDGES_HOST);
+    bool device_edges = false;
+    for (size_t i = 0; try_lean && i < m_sensors.size(); ++i) {
+        const Sensor *s = m_sensors[i];
+        if (s->m_edges_pending) edge_mode[i] = PSDR_EDGES_DEVICE;
+        else if (s->m_edges_on_device) edge_mode[i] = PSDR_EDGES_KEEP;
+        device_edges = device_edges || edge_mode[i] != PSDR_EDGES_HOST;
+    }
+    device_edges = device_edges || (try_lean && m_sec_distrb_stale && snap.n_sec_edges > 0);
+    if (!try_lean) ensure_host_edges();
     fill_snapshot(sn, !try_lean);
+    if (device_edges) {
+        m_edge_topology.assign(m_meshes.size(), psdr_edge_topology{});
+        for (size_t i = 0; i < m_meshes.size(); ++i) {
+            const Mesh *mesh = m_meshes[i];
+            psdr_edge_topology &t = m_edge_topology[i];
+            t.enabled = mesh->m_enable_edges ? 1 : 0;
+            t.n_edges = t.enabled ? (int) mesh->edges.size() : 0;
+            t.edges = t.n_edges > 0 ? reinterpret_cast<const int32_t *>(mesh->edges.data()) : nullptr;
+            t.uv_seam = t.n_edges > 0 && mesh->m_has_uv ? mesh->edge_uv_seams().data() : nullptr;
+            t.topology_version = mesh->m_topo_version;
+        }
+        device_edges = sn.geometry != nullptr;
+        if (!device_edges) {       // (without the geometry records the device cannot select: the host's arrays)
+            ensure_host_edges();
+            if (m_sec_distrb_stale && snap.n_sec_edges > 0) fill_sec_distrb();
+            fill_snapshot(sn, !try_lean);
+        }
+    }
     // the device copy: created once, then updated in place - only what changed since the previous upload is rewritten and sent, the tree is kept
     // (refitted on the device when triangles moved); psdr_hip_scene_update, include/psdr_hip.h
     if (m_hip != nullptr && m_always_rebuild) release_device();
@@ -1378,10 +1473,14 @@ void Scene::upload() {
     } else {
         // a failed update leaves the device scene half-written (and poisoned, scene_build.hip): the PSDR_SAME_* bits of the NEXT configure() would be relative to a
         // snapshot the device never received, so the handle is dropped and the next upload creates the scene again
-        int rc = psdr_hip_scene_update(m_hip, &sn, m_same, &m_last_update);
-        if (rc == PSDR_HIP_NEED_ROWS) {            // (the device scene is as it was: compute the rows after all and send the complete snapshot)
+        int rc = device_edges ? psdr_hip_scene_update_edges(m_hip, &sn, m_same, m_edge_topology.data(), edge_mode.data(), &m_last_update)
+                              : psdr_hip_scene_update(m_hip, &sn, m_same, &m_last_update);
+        if (rc == PSDR_HIP_NEED_ROWS) {            // (the device scene is as it was: compute the rows - and the edges - after all and send the complete snapshot)
             fill_snapshot(sn, true);
-            rc = psdr_hip_scene_update(m_hip, &sn, m_same, &m_last_update);
+            if (device_edges) {                    // (the same call, so that the sensors' edge arrays keep the size a later selection on the device needs)
+                edge_mode.assign(m_sensors.size(), PSDR_EDGES_HOST);
+                rc = psdr_hip_scene_update_edges(m_hip, &sn, m_same, m_edge_topology.data(), edge_mode.data(), &m_last_update);
+            } else rc = psdr_hip_scene_update(m_hip, &sn, m_same, &m_last_update);
         }
         if (rc) {
             const std::string why = psdr_hip_last_error();
@@ -1395,6 +1494,45 @@ void Scene::upload() {
     for (size_t i = 0; i < m_meshes.size() && i < m_up_geo.size(); ++i) { m_up_geo[i] = m_meshes[i]->m_geo_version; m_up_tan[i] = m_meshes[i]->m_tan_version; }
     m_device_rows_ok = sn.geometry != nullptr;        // (the next configure_host may be lean: the device has the topology or will take it with the next update)
     m_configured = true;
+    hip_check(psdr_hip_scene_edge_path(m_hip, &m_edge_path, &m_edge_bytes));
+    // the edges the device selected: their number and ids come back (the log line, chain_geometry, the reference's slices(info) > 0 per mesh)
+    bool mesh_without_edges = false;
+    for (size_t i = 0; i < m_sensors.size(); ++i) {
+        Sensor *s = m_sensors[i];
+        if (edge_mode[i] != PSDR_EDGES_DEVICE || !s->m_edges_pending) continue;
+        int32_t count = 0;
+        hip_check(psdr_hip_scene_primary_edges(m_hip, (int) i, &count, nullptr, 0, nullptr));
+        PrimaryEdges pe;
+        pe.ids.resize(3 * (size_t) count);
+        if (count > 0) hip_check(psdr_hip_scene_primary_edges(m_hip, (int) i, &count, pe.ids.data(), count, nullptr));
+        std::unordered_map<int, int> kept;                 // Mesh id -> kept edges
+        for (int k = 0; k < count; ++k) kept[pe.ids[3 * (size_t) k]]++;
+        bool empty_mesh = false;
+        for (const Mesh *mesh : m_meshes) empty_mesh = empty_mesh || (mesh->m_enable_edges && kept.find(mesh->m_mesh_id) == kept.end());
+        s->m_edges_pending = false;
+        if (empty_mesh) {                           // (the host's loop throws here and leaves the sensor without edges: the next configure() selects again)
+            s->m_edges = PrimaryEdges(); s->m_enable_edges = false; s->m_edges_on_device = false; s->cfg_key.clear();
+            mesh_without_edges = true;
+            continue;
+        }
+        s->m_edges = std::move(pe);
+        s->m_enable_edges = count > 0;
+        s->m_edges_on_device = count > 0;
+    }
+    if (!m_log_sensors.empty() && m_opts.log_level > 0 && !mesh_without_edges) {
+        std::ostringstream o2;
+        for (size_t i = 0; i < m_log_sensors.size(); ++i) {
+            const Sensor *s = m_sensors[(size_t) m_log_sensors[i]];
+            o2 << (i ? ", " : "(") << (s->m_enable_edges ? s->m_edges.ids.size() / 3 : 1);
+        }
+        o2 << ") primary edges initialized.";
+        log(o2.str());
+    }
+    m_log_sensors.clear();
+    // The reference's assertion (perspective.cpp:112-118), with the text the host loop raises.  ORDER: the host loop throws in configure_host, before any upload; here the count is
+    // only known after the update, so the device scene already holds this state (the sensor with the edges of the meshes that kept some) and m_configured is set - deliberately:
+    // the scene stays renderable and consistent, the sensor is left without edges on the host side with its configure key cleared, and the next configure() selects again.
+    if (mesh_without_edges) throw Exception("Assertion failed in " + std::string(__FILE__) + ":" + std::to_string(__LINE__) + " : kept > 0 (slices(info) > 0)");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -221,6 +221,7 @@ struct Mesh : Object, Transformable {
     uint64_t m_topo_version = 1;               // bumped by load / load_raw (faces, uv indices, vertex count)
     uint64_t m_geo_version = 0, m_tan_version = 0;
     float m_lower[3] = {0, 0, 0}, m_upper[3] = {0, 0, 0};       // box of the world-space vertices
+    const std::vector<uint8_t> &edge_uv_seams() const;          // [edges.size()] uv-seam mask of the primary-edge keep test (edge_select.h), cached per topology version
     float m_tw[16] = {0}, m_d_tw[16] = {0};                     // to_world() of the last configure(), value and tangent (psdr_mesh_geometry: the device computes a moved mesh's rows from it)
 private:
     void build_edges();
@@ -236,6 +237,8 @@ private:
     bool cfg_valid = false, raw_normals_valid = false;
     std::vector<int> vf_begin, vf_item;        // per vertex: its (corner, face) incidences as corner * num_faces + face, ascending = the order process_mesh sums them in
     uint64_t vf_topo = 0;
+    mutable std::vector<uint8_t> uv_seam;
+    mutable uint64_t uv_seam_topo = 0;
 };
 
 struct PrimaryEdges {
@@ -253,11 +256,18 @@ struct Sensor : Object, Transformable {
     // (Scene::configure_host skips a sensor whose inputs are the same; m_edges_version counts the runs that rebuilt the primary edges)
     std::vector<float> cfg_key;
     uint64_t m_edges_version = 0;
+    // PRIMARY EDGES ON THE DEVICE (Scene::upload, psdr_hip_scene_update_edges): m_edges_pending - configure() left the selection to the next upload;
+    // m_edges_on_device - the device selected them: of m_edges only `ids` is held here (read back after the upload), the arrays and the distribution are
+    // computed on demand (Scene::ensure_host_edges)
+    bool m_edges_pending = false, m_edges_on_device = false;
+    Scene *m_owner = nullptr;          // the scene this sensor belongs to (Scene::add_Sensor stores a copy it owns and deletes: the pointer cannot outlive the sensor); asked for the host's copy
+    virtual void select_edges(const Scene &scene, bool keep_edges) = 0;
 };
 struct PerspectiveCamera : Sensor {
     PerspectiveCamera(float fov_x, float near_, float far_) : m_fov_x(fov_x), m_near_clip(near_), m_far_clip(far_) {}
     std::string type_name() const override { return "PerspectiveCamera"; }
     void configure(const Scene &scene, bool keep_edges) override;
+    void select_edges(const Scene &scene, bool keep_edges) override;
     float m_fov_x, m_near_clip, m_far_clip;
     int m_width = 0, m_height = 0;
     bool m_orthographic = false;   // OrthographicCamera(near, far), reference src/sensor/orthographic.cpp (same class here: it differs from
@@ -289,7 +299,11 @@ struct Scene : Object {
     void fill_snapshot(psdr_scene_snapshot &sn, bool full = true);
     void ensure_full_snapshot();                                        // computes what a lean configure_host left out (rows of moved meshes, secondary-edge rows)
     void fill_sec_rows();
+    void fill_sec_distrb();
+    void ensure_host_edges();                                           // the host's copy of the primary edges the device selected (Sensor::m_edges_on_device)
+    bool device_edges() const { return m_device_edges; }               // the configure_host in progress leaves the primary edges to the device
     int64_t check_device_rows();
+    int64_t check_device_edges();
     bool is_ready() const;
     size_t get_num_emitters() const { return m_emitters.size(); }
     // Reverse-mode chain rule of the differentiable part of configure() (Mesh::configure / process_mesh, the secondary-edge rows, the primary-edge projection:
@@ -339,6 +353,8 @@ struct Scene : Object {
     uint32_t m_same = 0;
     psdr_update_info m_last_update{};
     double m_ms_host = 0.0;            // wall clock of the host half (configure_host) of the last configure()
+    int m_edge_path = 0;               // psdr_hip_scene_edge_path of the last upload: 0 the host's arrays, 1 / 2 selected on the device (cmf by the parallel scan / the sequential form)
+    int64_t m_edge_bytes = 0;          // ... and the bytes it sent for the primary edges
     bool m_always_rebuild = false;     // test / measurement aid: destroy and create the device scene in every configure() (what rounds 1-4 did)
 private:
     void rebuild_param_map();
@@ -347,8 +363,12 @@ private:
     std::vector<MeshKey> m_snap_keys;                      // the meshes the snapshot's rows were laid out for
     std::vector<uint64_t> m_seen_geo, m_seen_tan;          // per mesh: the versions its snapshot rows hold
     std::vector<uint64_t> m_bits_geo, m_bits_tan;          // per mesh: the versions the PSDR_SAME_* bits were last derived from
+    std::vector<int> m_log_sensors;                        // configure_host: the sensors of the "primary edges initialized" line when upload() has to write it
+    bool m_device_edges = false;                           // the configure_host in progress / last run left the primary edges to the device (lean configures only)
+    std::vector<psdr_edge_topology> m_edge_topology;       // upload(): per mesh, what the device's edge selection reads
     bool m_lean = false;                                   // the configure_host in progress / last run was lean (see scene_host.cpp)
     std::vector<uint64_t> m_up_geo, m_up_tan;              // per mesh: the versions the device scene holds (psdr_mesh_geometry.moved)
+    bool m_sec_distrb_stale = false;                       // lean configure: the secondary-edge distribution of the snapshot is behind too (the device computes its own)
     bool m_sec_rows_stale = false;                         // lean configure: the secondary-edge row arrays of the snapshot are behind (their CDF is not)
     bool m_device_rows_ok = false;                         // the last upload went through with the device computing the moved meshes' rows: the next configure_host may be lean
     std::vector<psdr_mesh_geometry> m_geometry;            // upload(): the per-mesh inputs of the device's row computation
