@@ -475,6 +475,30 @@ int psdr_hip_guiding_mass(const psdr_hip_guiding *g, float *out_host, int32_t ca
 int psdr_hip_guiding_num_cells(const psdr_hip_guiding *g);
 int psdr_hip_guiding_destroy(psdr_hip_guiding *g);
 
+/* LAPLACIAN VERTEX PRECONDITIONER ("Large Steps in Inverse Rendering", Nicolet et al. 2021; the reference's users get it from the CUDA-only largesteps / cholespy packages).
+ * M = I + lambda L, L the combinatorial Laplacian of a mesh: L_ii = number of distinct neighbours of vertex i, L_ij = -1 once per distinct undirected edge.  Only the CSR
+ * pattern is given and kept (row_begin[n + 1], col[row_begin[n]], HOST arrays, copied): row i of M x is (1 + lambda deg_i) x_i - lambda sum_j x_j with
+ * deg_i = row_begin[i + 1] - row_begin[i].  The create call validates the host arrays BEFORE any device call (n > 0, row_begin[0] == 0, row_begin monotonic, every col in
+ * [0, n), no col equal to its row; lambda finite and >= 0) and returns non-zero for a bad list: no bad index reaches a kernel.  x, y, b are DEVICE [n, 3] row-major float32
+ * (a contiguous torch [n, 3]); the three columns are independent systems solved at once.  Added under ABI 16 like the batch entry points: nothing existing changed. */
+typedef struct psdr_hip_precond psdr_hip_precond;
+typedef struct psdr_precond_info {
+    int32_t iterations;              /* iterations enqueued (a multiple of the chunk between two looks at the residual, or max_iter) */
+    int32_t converged;               /* 1: every column's recomputed residual |b - M x|_2 <= rtol |b|_2 */
+    int32_t launches;                /* kernels launched by the call */
+    float rel_residual[3];           /* |b - M x|_2 / |b|_2 per column, from r = b - M x recomputed from x (0 for a zero column of b) */
+} psdr_precond_info;
+int psdr_hip_precond_create(int32_t n, const int32_t *row_begin, const int32_t *col, float lambda, psdr_hip_precond **out, void *stream);
+int psdr_hip_precond_destroy(psdr_hip_precond *precond);
+/* y = M x (x and y different arrays); no synchronisation */
+int psdr_hip_precond_apply(const psdr_hip_precond *precond, const float *x, float *y, void *stream);
+/* M x = b by Jacobi-preconditioned conjugate gradients in float32 from x0 = 0, each column with its own scalars: plain launches on `stream` (two per iteration, every scalar
+ * in device memory, dot products as per-workgroup partials added in a fixed order by the next launch: no atomics, no grid barrier, the same b gives the same bits).  After every
+ * chunk of iterations r = b - M x is recomputed from x, its norms reach the host in one small copy (the call's only synchronisations) and the iteration goes on from that
+ * residual; convergence is declared on it alone.  max_iter reached: converged = 0, x as it stands, return 0.  A column with |b| = 0, r.z = 0 or p.q <= 0 is frozen
+ * (alpha = beta = 0) for the rest of the solve; a zero column of b gives exactly zero.  The handle holds the work arrays: one solve at a time per handle. */
+int psdr_hip_precond_solve(psdr_hip_precond *precond, const float *b, float *x, float rtol, int32_t max_iter, psdr_precond_info *info, void *stream);
+
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);
 int psdr_hip_sampler_floats(uint64_t seed_value, uint64_t lane, uint64_t skip, int32_t n, float *out_dev, void *stream);

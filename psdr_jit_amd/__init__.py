@@ -1567,3 +1567,7 @@ def render_d_fwd(integrator, scene, sensor_id=0, seed=-1, batch_pix=-1, terms=TE
         _sync_params(scene, {id(k): v for k, v in tangents.items()})
         scene._configure(scene.__dict__.get("_psdr_active", []))
     return _render_d_raw(integrator, scene, sensor_id, seed, batch_pix, terms, **_batch_kw(batch_edges))
+
+
+# the Laplacian vertex preconditioner and its optimiser (precond.py; kernels: csrc/hip/precond.hip)
+from .precond import laplacian_csr, LaplacianPreconditioner, AdamUniform  # noqa: E402,F401

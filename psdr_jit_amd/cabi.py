@@ -11,6 +11,7 @@ SYMBOLS = [
     "psdr_hip_render_c", "psdr_hip_render_d_fwd", "psdr_hip_render_d_bwd", "psdr_hip_render_d_fwd_batch", "psdr_hip_render_d_bwd_batch", "psdr_hip_render_c_counted", "psdr_hip_render_d_fwd_counted",
     "psdr_hip_li_lanes", "psdr_hip_guiding_build", "psdr_hip_guiding_mass", "psdr_hip_guiding_num_cells",
     "psdr_hip_guiding_destroy", "psdr_hip_tea64", "psdr_hip_sampler_floats",
+    "psdr_hip_precond_create", "psdr_hip_precond_destroy", "psdr_hip_precond_apply", "psdr_hip_precond_solve",
 ]
 
 
@@ -39,6 +40,10 @@ class Counters(C.Structure):
 class UpdateInfo(C.Structure):      # psdr_update_info
     _fields_ = [("tree", C.c_int32), ("reallocated", C.c_int32), ("bytes_uploaded", C.c_int64), ("sah_cost", C.c_double), ("sah_cost_built", C.c_double),
                 ("ms_tree", C.c_double), ("ms_fill", C.c_double), ("ms_upload", C.c_double), ("ms_total", C.c_double)]
+
+
+class PrecondInfo(C.Structure):     # psdr_precond_info
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("launches", C.c_int32), ("rel_residual", C.c_float * 3)]
 
 
 _lib = None
@@ -72,6 +77,10 @@ def lib():
         L.psdr_hip_scene_last_update.argtypes = [C.c_void_p, C.POINTER(UpdateInfo)]
         L.psdr_hip_scene_check_tree.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.psdr_hip_scene_live_pixels.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
+        L.psdr_hip_precond_create.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_void_p), C.c_void_p]
+        L.psdr_hip_precond_destroy.argtypes = [C.c_void_p]
+        L.psdr_hip_precond_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.psdr_hip_precond_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.POINTER(PrecondInfo), C.c_void_p]
         _lib = L
     return _lib
 
