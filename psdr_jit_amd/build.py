@@ -23,7 +23,7 @@ CORE_LIB = os.path.join(HERE, "_psdr_core" + (sysconfig.get_config_var("EXT_SUFF
 
 API_SRC = os.path.join(CSRC, "hip", "api.hip")                  # the host unit: the render entry points (C ABI) and the small kernels
 UNITS_SRC = os.path.join(CSRC, "hip", "render_units.hip")       # the eight kernel units: the heavy kernel templates of render_kernels.h, one list of instantiations each (see hip_units)
-SCENE_SRC = os.path.join(CSRC, "hip", "scene_build.hip")        # psdr_hip_scene_create / _update: tree build and refit, blob layout, uploads
+SCENE_SRC = os.path.join(CSRC, "hip", "scene_build.hip")        # psdr_hip_scene_create / _update: tree build and refit, uploads (blob_layout.h, blob_rows.h: the blob's layout and row formats)
 PRECOND_SRC = os.path.join(CSRC, "hip", "precond.hip")         # psdr_hip_precond_*: the Laplacian vertex preconditioner, its matrix-vector product and CG solver
 HIP_SRCS = [API_SRC, UNITS_SRC, SCENE_SRC, PRECOND_SRC]
 BUILD_DEPS = [os.path.join(HERE, "isa_lint.py")]          # part of the recipe: a change of the lint re-builds (and re-lints) the library
@@ -33,7 +33,7 @@ DEVICE_DEPS = _H("scene_dev.h", "dmath.h", "trav4.h")
 COMMON_DEPS = DEVICE_DEPS + _H("scene_obj.h") + [os.path.join(ROOT, "include", "psdr_hip.h"), os.path.join(CSRC, "common", "threads.h")]
 KERNEL_DEPS = DEVICE_DEPS + _H("render_kernels.h", "sampler.h", "shade.h", "edges.h", "paths.h", "adjoint.h", "adjoint_mat.h", "isect_ad.h", "microfacet.h") + [os.path.join(CSRC, "common", "envmath.h")] + BUILD_DEPS
 API_DEPS = sorted(set(COMMON_DEPS + KERNEL_DEPS))      # the host unit launches the heavy kernels: it sees their header, they do not see api.hip
-SCENE_DEPS = COMMON_DEPS + _H("bvh.h", "filter.h") + [os.path.join(CSRC, "host", "hnum.h"), os.path.join(CSRC, "host", "edge_select.h")] + BUILD_DEPS
+SCENE_DEPS = COMMON_DEPS + _H("bvh.h", "filter.h", "blob_rows.h", "blob_layout.h") + [os.path.join(CSRC, "host", "hnum.h"), os.path.join(CSRC, "host", "edge_select.h")] + BUILD_DEPS
 PRECOND_DEPS = [os.path.join(ROOT, "include", "psdr_hip.h")] + BUILD_DEPS
 HIP_DEPS = sorted(set(API_DEPS + SCENE_DEPS + PRECOND_DEPS))
 HOST_SRCS = [os.path.join(CSRC, "host", f) for f in ("scene_host.cpp", "bindings.cpp", "exr_piz.cpp")]

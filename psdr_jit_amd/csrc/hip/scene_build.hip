@@ -20,6 +20,8 @@
 #include "scene_obj.h"
 #include "bvh.h"
 #include "filter.h"
+#include "blob_rows.h"
+#include "blob_layout.h"
 #include "../host/hnum.h"
 #include "../host/edge_select.h"
 
@@ -29,9 +31,6 @@ static int fail(const std::string &msg) { return psdr::api_fail(msg); }
 
 constexpr double kRebuildFactor = 1.4;          // a refitted tree whose SAH cost exceeds this multiple of the cost it was built with is built again
 
-static inline void put4(float *b, size_t word, float x, float y, float z, float w) { float *q = b + 4 * word; q[0] = x; q[1] = y; q[2] = z; q[3] = w; }
-static inline float ibits(int32_t v) { float f; std::memcpy(&f, &v, 4); return f; }
-static inline size_t words_for_floats(size_t n) { return (n + 3) / 4; }
 static inline double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 // Conservative screen-space coverage of the scene for one sensor: bit (y * width + x) = some triangle's projection (world_to_sample, a projective map: the
@@ -773,385 +772,355 @@ struct WordRange { size_t b, e; };
 // psdr_hip_scene_update_edges: per mesh the edge topology, per sensor where its primary edges come from (PSDR_EDGES_*)
 struct EdgeRequest { const psdr_edge_topology *topo; const int32_t *mode; };
 
-// Everything between a snapshot and a renderable device scene.  fresh: the handle is new.  same: PSDR_SAME_* bits the caller vouches for
-// (relative to the snapshot of the previous create / update of this handle); force_build: build the tree even if the triangle count fits.
-static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned same, bool fresh, bool force_build, psdr_update_info *info_out, const EdgeRequest *ereq = nullptr) {
-    const auto t_start = std::chrono::steady_clock::now();
-    psdr_update_info info{};
-    const psdr_triangles &tr = s->tris;
-    const int n = tr.n_triangles;
-    if (n <= 0) return fail("Missing meshes!");
+// ---------------------------------------------------------------------------------------------------------------------------
+// FROM A SNAPSHOT TO A RENDERABLE DEVICE SCENE: scene_sync (below) is the list of SceneSync's steps.  Up to and including plan_layout nothing of the handle
+// is written except by tree_build, and every step that can answer PSDR_HIP_NEED_ROWS there runs only when no tree is built: such an answer leaves the handle as it was.
+// commit_tables is the first write of sc->T / sc->E; the three later PSDR_HIP_NEED_ROWS answers (geometry: they need what geometry_on_device found) go
+// through SceneSync::need_rows, which puts both back.  Any other non-zero return leaves old and new sections mixed: the caller poisons the handle (update_entry).
+static int sync_validate(const psdr_scene_snapshot *s) {
+    if (s->tris.n_triangles <= 0) return fail("Missing meshes!");
     if (s->n_sensors <= 0) return fail("Missing sensor!");
     for (int i = 0; i < s->n_bsdfs; ++i) {
         const psdr_bsdf_rec &b = s->bsdfs[i];
         if (b.type < 0 || b.type > 5) return fail("Unknown BSDF type!");
         if (b.type == 5 && (b.nested_bsdf < 0 || b.nested_bsdf >= s->n_bsdfs || s->bsdfs[b.nested_bsdf].type == 5)) return fail("NormalMap: invalid nested BSDF");
     }
-    const bool build = fresh || force_build || n != sc->tree_tris;
-    // rows_valid = 0 (updates only; psdr_scene_snapshot): the caller relies on the device computing the moved meshes' rows.  Whatever needs the rows themselves - a tree to
-    // build, a section that moves, a live-pixel mask to rebuild - answers PSDR_HIP_NEED_ROWS before anything has been changed
-    const bool rows_valid = fresh || s->rows_valid != 0;
-    if (!rows_valid && (build || s->geometry == nullptr || n <= kBruteForceMax)) return PSDR_HIP_NEED_ROWS;
-    if (build) same = 0;
-    if (!fresh) {
-        // the previous calls on this scene read what is about to be overwritten: wait for the last of them (configure() is a synchronisation point in the reference as well)
-        std::lock_guard<std::mutex> lk(sc->mu);
-        if (sc->ev && sc->have_last) HIPCHK(hipEventSynchronize(sc->ev));
-    }
-    const bool same_tris = (same & PSDR_SAME_TRIANGLES) != 0, same_tan = (same & PSDR_SAME_TRI_TANGENTS) != 0, same_sec = (same & PSDR_SAME_SEC_EDGES) != 0,
-               same_prim = (same & PSDR_SAME_PRIM_EDGES) != 0, same_env = (same & PSDR_SAME_ENV_TEXELS) != 0, same_env_tan = (same & PSDR_SAME_ENV_TANGENT) != 0,
-               same_bitmaps = (same & PSDR_SAME_BITMAPS) != 0;
+    return 0;
+}
 
+// the search table of a distribution (scene_obj.h::build_cdf_guide), built on the host and sent under `key`: ptr / count (none: NULL / 0), its bytes added to *bytes
+static int sync_guide(psdr_hip_scene *sc, const std::string &key, const float *cmf, int n, float sum, int per_bucket, const int *&ptr, int &count, int64_t *bytes, psdr_update_info &info) {
+    ptr = nullptr; count = 0;
+    if (n <= 0 || !cmf) return 0;
+    std::vector<int> guide;
+    build_cdf_guide(cmf, n, sum, guide, per_bucket);
+    if (guide.empty()) return 0;
+    if (sync_named(sc, key, guide.data(), guide.size() * sizeof(int), false, ptr, info)) return 1;
+    count = (int) guide.size() - 1;
+    if (bytes) *bytes += (int64_t) (guide.size() * sizeof(int));
+    return 0;
+}
+
+struct SceneSync {
+    psdr_hip_scene *sc;
+    const psdr_scene_snapshot *s;
+    const EdgeRequest *ereq;
+    bool fresh;                          // the handle is new
+    const psdr_triangles &tr;
+    SceneTables &T;                      // sc->T / sc->E: the old tables up to commit_tables, then this snapshot's
+    SecEdgeTables &E;
+    // what the caller vouches for (PSDR_SAME_* relative to the snapshot of the previous create / update of this handle; all false when a tree is built)
+    bool same_tris = false, same_tan = false, same_sec = false, same_prim = false, same_env = false, same_env_tan = false, same_bitmaps = false;
+    bool build = false, rows_valid = true, uses_bvh = false, has_tan = false;
+    bool geo = false;                    // the triangle sections are rewritten: moved triangles, or tangent arrays gained or lost (every section behind them shifts)
+    // the edge request: room per sensor, who makes the secondary-edge distribution, whether any edge section is the device's
+    size_t pe_cap = 0;
+    bool cap_layout = false, sec_dev_any = false, dev_edges = false;
+    int env_emitter = -1;
     std::vector<float> new_nodes;
-    auto t_tree = std::chrono::steady_clock::now();
-    if (build) {
-        if (tree_build(sc, tr, new_nodes)) return 1;
-        info.tree = 2;
-    }
-    info.ms_tree = ms_since(t_tree);
-    const auto t_fill = std::chrono::steady_clock::now();
-    const bool uses_bvh = n > kBruteForceMax;
-    const bool has_tan = tr.d_p0 != nullptr;
-    const std::vector<int32_t> &order = sc->order;
+    std::vector<FilterPrim> filt;        // filter primitives of the brute-force tracer (their number depends on the geometry: coplanar neighbours become quads)
+    int n_filt = 0;
+    BlobLayout L;
+    SceneTables Told{};
+    SecEdgeTables Eold{};
+    float *H = nullptr;                  // the pinned host copy of the blob
+    std::vector<WordRange> dirty;        // sections of H that were written and have to be sent
+    bool blob_moved = false, dev_geo = false;
+    int sec_cdf_mode = 0, edge_path = 0;
+    int64_t sec_bytes = 0, edge_bytes = 0;          // sec_bytes: what goes up for the secondary-edge DISTRIBUTION (pmf, cmf, search table)
+    psdr_update_info info{};
 
-    // ---- filter primitives of the brute-force tracer (their number depends on the geometry: coplanar neighbours become quads)
-    std::vector<FilterPrim> filt;
-    // (a snapshot that gains or loses its tangent arrays shifts every section behind them: treated like moved triangles)
-    const bool geo = !same_tris || (has_tan ? 1 : 0) != sc->T.has_tangent;
-    if (geo) build_filter_prims(tr.p0, tr.e1, tr.e2, order.data(), n, filt);
+    SceneSync(psdr_hip_scene *sc_, const psdr_scene_snapshot *s_, const EdgeRequest *ereq_, bool fresh_) : sc(sc_), s(s_), ereq(ereq_), fresh(fresh_), tr(s_->tris), T(sc_->T), E(sc_->E) {}
+    void mark(size_t b, size_t e) { if (e > b) dirty.push_back({b, e}); }
+    int need_rows() { T = Told; E = Eold; return PSDR_HIP_NEED_ROWS; }       // (the only rollback: the tables as they were)
 
-    // ---- layout (float4-word offsets); a section keeps its content only when the caller vouches for it AND it stays where it was
-    const SceneTables Told = sc->T;
-    const SecEdgeTables Eold = sc->E;
-    SceneTables &T = sc->T;
-    SecEdgeTables &E = sc->E;
-    const psdr_sec_edges &se = s->sec_edges;
-    size_t w = 0;
-    T.nodes_off = (int) w; w += (size_t) (kNodeFloats / 4) * (size_t) T.n_nodes;      // nodes of the 4-wide tree (bvh.h: 64 bytes each)
-    T.trav_off = (int) w;  w += 3 * (size_t) n;
-    T.shade_off = (int) w; w += 6 * (size_t) n;
-    T.tan_off = (int) w;   w += has_tan ? 6 * (size_t) n : 0;
-    T.map_off = (int) w;   w += words_for_floats((size_t) n);
-    T.filt_off = (int) w;  T.n_filt = geo ? (int) filt.size() : Told.n_filt; w += 6 * (size_t) T.n_filt;
-    const size_t small_begin = w;
-    T.mesh_off = (int) w;  w += 2 * (size_t) s->n_meshes;
-    T.bsdf_off = (int) w;  w += 2 * (size_t) std::max(1, s->n_bsdfs);
-    T.emit_off = (int) w;  w += 2 * (size_t) std::max(1, s->n_emitters);
-    T.ecdf_off = (int) w;  w += words_for_floats(2 * (size_t) std::max(1, s->n_emitters));
-    T.fcdf_off = (int) w;  w += words_for_floats(2 * (size_t) std::max(1, s->n_face_distrb));
-    const size_t small_end = w;
-    E.n = se.n_edges; E.sum = se.sum;
-    E.off = (int) w;       w += 6 * (size_t) std::max(0, se.n_edges);
-    E.cdf_off = (int) w;   w += words_for_floats(2 * (size_t) std::max(1, se.n_edges));
-    const size_t sec_end = w;
-    std::vector<std::pair<int, int>> pe_offs;
-    // (psdr_hip_scene_update_edges: every sensor's edge arrays are sized ONCE, to the number of edges of the meshes with edges - the kept count changes from
-    //  configure to configure, the sections behind it must not move)
-    //  ... and a scene that has been given that size keeps it under psdr_hip_scene_update too: the two calls alternate (a configure that changes nothing about the edges takes the plain one),
-    //  and a section that moved would be written and sent again
-    size_t pe_cap = ereq ? pe_capacity(s, ereq->topo) : (fresh ? 0 : sc->pe_cap);
-    for (int i = 0; !ereq && i < s->n_sensors; ++i) if ((size_t) std::max(0, s->sensors[i].n_edges) > pe_cap) pe_cap = 0;
-    const bool cap_layout = ereq != nullptr || pe_cap > 0;
-    // (... and the secondary-edge distribution: under that call a snapshot without sec_edges.pmf / cmf leaves the lengths and their CDF to the device)
-    const bool sec_dev_any = ereq && se.n_edges > 0 && se.pmf == nullptr;
-    bool dev_edges = sec_dev_any;                // some sensor's edges are selected on the device or kept from an earlier selection: their host copy in H is behind
-    for (int i = 0; i < s->n_sensors; ++i) {
-        if (ereq && ereq->mode[i] != PSDR_EDGES_HOST) dev_edges = true;
-        else if (ereq && (size_t) std::max(0, s->sensors[i].n_edges) > pe_cap) return fail("psdr_hip_scene_update_edges: a sensor carries more primary edges than the meshes have edges");
-        const int ne = cap_layout ? (int) pe_cap : std::max(0, s->sensors[i].n_edges);
-        const int o1 = (int) w; w += 3 * (size_t) ne;
-        const int o2 = (int) w; w += words_for_floats(2 * (size_t) std::max(1, ne));
-        pe_offs.emplace_back(o1, o2);
-    }
-    if (w > 0x7fffffffull / 4) return fail("scene too large for 32-bit blob offsets");
-    T.blob_words = (int) w;
-    T.n_tris = n; T.n_meshes = s->n_meshes; T.n_bsdfs = s->n_bsdfs; T.n_emitters = s->n_emitters;
-    T.n_fcdf = s->n_face_distrb; T.has_tangent = has_tan ? 1 : 0;
-    T.emitter_sum = s->emitter_sum;
-    T.width = s->width; T.height = s->height; T.spp = s->spp; T.sppe = s->sppe; T.sppse = s->sppse;
-    T.env_emitter = -1;
-    for (int i = 0; i < s->n_emitters; ++i) if (s->emitters[i].type == 1) T.env_emitter = i;
-    // traversal stack: the first kStackLds entries of a lane in LDS, deeper ones in a per-lane global array (trav4.h);
-    // scenes that are traced by brute force (<= kBruteForceMax triangles) need neither
-    // kStackLdsMax + kTravRows = 40 KB per workgroup: four workgroups per CU (round 6: 12 stack rows + 2 rows of tree top, until then 8 + 6 - trav4.h).  Round 5 measured both sides of that choice on config 5 (LABNOTES): FEWER workgroups cost a lot
-    // (3 per CU: +17 %, 2: +55 %), a FIFTH brings nothing (a 30 KB layout - no hit rows, 4 stack rows - lost exactly what its shorter stack costs at equal
-    // occupancy), and stack rows going to the global tail cost 1.2 % (6 rows), 6.8 % (4), 9.5 % (2).
-    // PSDR_STACK_LDS = 2 ... kStackLdsMax (test knob, read when a scene is created or rebuilt): fewer rows, so that small test scenes reach the global tail too
-    // (tests/test_gpu_configs.py: the forked terms of a renderD against the serial call)
-    int kStackLds = kStackLdsMax;
-    if (const char *e = std::getenv("PSDR_STACK_LDS")) kStackLds = std::max(2, std::min(kStackLdsMax, std::atoi(e)));
-    T.stack_lds = uses_bvh ? std::min(kStackLds, sc->tree_max_stack) : 0;
-    T.stack_depth = uses_bvh ? T.stack_lds + kTravRows : kColdRows;   // BVH: + parked rays, best hits and the pair ring of the traversal (trav4.h); brute force: cold path state (paths.h)
-
-    if (dev_edges) {
-        // the device selects (or keeps) primary edges only where nothing else about the scene moves: the tree stays, the blob stays where it is (the host's copy of such a
-        // section is behind), the world vertices of every mesh are resident or about to be computed.  Otherwise: PSDR_HIP_NEED_ROWS, nothing changed - the caller comes back
-        // with PSDR_EDGES_HOST for every sensor
-        bool ok = !fresh && !build && uses_bvh && s->geometry != nullptr && sc->blob.p && sc->blob.bytes >= 16 * w && std::getenv("PSDR_HOST_GEOMETRY") == nullptr;
-        for (int i = 0; ok && i < s->n_sensors; ++i)
-            if (ereq->mode[i] == PSDR_EDGES_KEEP)
-                ok = (size_t) i < sc->sensors.size() && sc->sensors[(size_t) i].pe_off == pe_offs[(size_t) i].first && sc->sensors[(size_t) i].pecdf_off == pe_offs[(size_t) i].second &&
-                     sc->pe_ids.size() == (size_t) s->n_sensors;
-        if (sec_dev_any) ok = ok && E.off == Eold.off && E.cdf_off == Eold.cdf_off && E.n == Eold.n;       // (the section stays where it is: the host's copy of it is behind)
-        if (!ok) { sc->T = Told; sc->E = Eold; return PSDR_HIP_NEED_ROWS; }
-    }
-    if (!rows_valid) {
-        const bool layout_kept = sc->blob.p && sc->blob.bytes >= 16 * w && T.trav_off == Told.trav_off && T.shade_off == Told.shade_off && T.tan_off == Told.tan_off && T.map_off == Told.map_off &&
-                                 (has_tan ? 1 : 0) == Told.has_tangent && E.off == Eold.off && E.cdf_off == Eold.cdf_off && E.n == Eold.n && T.env_emitter >= 0 && Told.env_emitter >= 0 &&
-                                 std::getenv("PSDR_HOST_GEOMETRY") == nullptr;
-        if (!layout_kept) { sc->T = Told; sc->E = Eold; return PSDR_HIP_NEED_ROWS; }
-    }
-    // ---- the blob: device allocation with head room, pinned host copy
-    bool blob_moved = false;
-    if (!sc->blob.p || sc->blob.bytes < 16 * w) {
-        // (room for the sensors' edge arrays at the size psdr_hip_scene_update_edges gives them - every edge of the meshes with edges - so that the first such update does not move the blob)
-        size_t reserve = 0;
-        if (!ereq && uses_bvh && s->geometry && s->sppe > 0) {
-            size_t ne_all = 0;
-            for (int i = 0; i < s->n_meshes; ++i) ne_all += (size_t) std::max(0, s->geometry[i].n_edges);
-            reserve = (size_t) s->n_sensors * (3 * ne_all + words_for_floats(2 * std::max<size_t>(1, ne_all)));
+    // build / refit / keep, what the caller vouches for, the edge request - from the snapshot, the request and the old handle alone, and what they already refuse
+    int plan_request(unsigned same, bool force_build) {
+        const int n = s->tris.n_triangles;
+        build = fresh || force_build || n != sc->tree_tris;
+        uses_bvh = n > kBruteForceMax;
+        has_tan = s->tris.d_p0 != nullptr;
+        // rows_valid = 0 (updates only; psdr_scene_snapshot): the caller relies on the device computing the moved meshes' rows.  Whatever needs the rows themselves - a tree to
+        // build, a section that moves, a live-pixel mask to rebuild - answers PSDR_HIP_NEED_ROWS before anything has been changed
+        rows_valid = fresh || s->rows_valid != 0;
+        if (!rows_valid && (build || s->geometry == nullptr || n <= kBruteForceMax)) return PSDR_HIP_NEED_ROWS;
+        if (build) same = 0;
+        same_tris = (same & PSDR_SAME_TRIANGLES) != 0; same_tan = (same & PSDR_SAME_TRI_TANGENTS) != 0; same_sec = (same & PSDR_SAME_SEC_EDGES) != 0;
+        same_prim = (same & PSDR_SAME_PRIM_EDGES) != 0; same_env = (same & PSDR_SAME_ENV_TEXELS) != 0; same_env_tan = (same & PSDR_SAME_ENV_TANGENT) != 0;
+        same_bitmaps = (same & PSDR_SAME_BITMAPS) != 0;
+        // (a snapshot that gains or loses its tangent arrays shifts every section behind them: treated like moved triangles)
+        geo = !same_tris || (has_tan ? 1 : 0) != T.has_tangent;
+        for (int i = 0; i < s->n_emitters; ++i) if (s->emitters[i].type == 1) env_emitter = i;
+        // (psdr_hip_scene_update_edges: every sensor's edge arrays are sized ONCE, to the number of edges of the meshes with edges - the kept count changes from
+        //  configure to configure, the sections behind it must not move)
+        //  ... and a scene that has been given that size keeps it under psdr_hip_scene_update too: the two calls alternate (a configure that changes nothing about the edges takes the plain one),
+        //  and a section that moved would be written and sent again
+        pe_cap = ereq ? pe_capacity(s, ereq->topo) : (fresh ? 0 : sc->pe_cap);
+        for (int i = 0; !ereq && i < s->n_sensors; ++i) if ((size_t) std::max(0, s->sensors[i].n_edges) > pe_cap) pe_cap = 0;
+        cap_layout = ereq != nullptr || pe_cap > 0;
+        // (... and the secondary-edge distribution: under that call a snapshot without sec_edges.pmf / cmf leaves the lengths and their CDF to the device)
+        sec_dev_any = ereq && s->sec_edges.n_edges > 0 && s->sec_edges.pmf == nullptr;
+        dev_edges = sec_dev_any;         // some sensor's edges are selected on the device or kept from an earlier selection: their host copy in H is behind
+        for (int i = 0; i < s->n_sensors; ++i) {
+            if (ereq && ereq->mode[i] != PSDR_EDGES_HOST) dev_edges = true;
+            else if (ereq && (size_t) std::max(0, s->sensors[i].n_edges) > pe_cap) return fail("psdr_hip_scene_update_edges: a sensor carries more primary edges than the meshes have edges");
         }
-        const size_t cap = 16 * (w + w / 4 + 64 + reserve);
-        void *fresh_p = nullptr;
-        HIPCHK(hipMalloc(&fresh_p, cap));
-        if (sc->blob.p) {
-            // the nodes a refit has written exist on the device only: they move with the allocation
-            if (!build && uses_bvh) HIPCHK(hipMemcpy((char *) fresh_p + 16 * (size_t) T.nodes_off, (const char *) sc->blob.p + 16 * (size_t) Told.nodes_off, 16 * (size_t) (kNodeFloats / 4) * (size_t) T.n_nodes, hipMemcpyDeviceToDevice));
-            HIPCHK(hipFree(sc->blob.p));
-            info.reallocated++;
-        }
-        sc->blob.p = fresh_p; sc->blob.bytes = cap;
-        blob_moved = true;
+        // the device selects (or keeps) primary edges only where nothing else about the scene moves - first of all the tree: refused before one is built (plan_layout
+        // refuses the rest, once the layout is known)
+        if (dev_edges && (fresh || build)) return PSDR_HIP_NEED_ROWS;
+        return 0;
     }
-    if (sc->hblob.ensure(sc->blob.bytes)) return 1;
-    float *H = (float *) sc->hblob.p;
-    std::vector<WordRange> dirty;
-    auto mark = [&](size_t b, size_t e) { if (e > b) dirty.push_back({b, e}); };
 
-    if (build) {
-        std::memcpy(H + 4 * (size_t) T.nodes_off, new_nodes.data(), sizeof(float) * new_nodes.size());
-        mark((size_t) T.nodes_off, (size_t) T.nodes_off + new_nodes.size() / 4);
+    // the layout of the blob for this snapshot, and every PSDR_HIP_NEED_ROWS answer that follows from it and the old tables: sc->T / sc->E are still the old ones
+    int plan_layout() {
+        if (geo) build_filter_prims(tr.p0, tr.e1, tr.e2, sc->order.data(), tr.n_triangles, filt);
+        n_filt = geo ? (int) filt.size() : T.n_filt;
+        BlobCounts k;
+        k.n_tris = tr.n_triangles; k.n_nodes = T.n_nodes; k.node_words = kNodeFloats / 4; k.has_tan = has_tan; k.n_filt = n_filt;
+        k.n_meshes = s->n_meshes; k.n_bsdfs = s->n_bsdfs; k.n_emitters = s->n_emitters; k.n_face_distrb = s->n_face_distrb; k.n_sec_edges = s->sec_edges.n_edges;
+        for (int i = 0; i < s->n_sensors; ++i) k.sensor_edges.push_back(s->sensors[i].n_edges);
+        k.pe_cap = pe_cap; k.capped = cap_layout;
+        // a section keeps its content only when the caller vouches for it AND it stays where it was
+        if (!blob_layout(k, L)) return fail("scene too large for 32-bit blob offsets");
+        const bool blob_fits = sc->blob.p && sc->blob.bytes >= 16 * L.words, forced_host = std::getenv("PSDR_HOST_GEOMETRY") != nullptr;
+        if (dev_edges) {
+            // ... the blob stays where it is (the host's copy of such a section is behind), the world vertices of every mesh are resident or about to be computed.
+            // Otherwise: PSDR_HIP_NEED_ROWS, nothing changed - the caller comes back with PSDR_EDGES_HOST for every sensor
+            bool ok = uses_bvh && s->geometry != nullptr && blob_fits && !forced_host;
+            for (int i = 0; ok && i < s->n_sensors; ++i)
+                if (ereq->mode[i] == PSDR_EDGES_KEEP)
+                    ok = (size_t) i < sc->sensors.size() && sc->sensors[(size_t) i].pe_off == L.pe[(size_t) i].first && sc->sensors[(size_t) i].pecdf_off == L.pe[(size_t) i].second &&
+                         sc->pe_ids.size() == (size_t) s->n_sensors;
+            if (sec_dev_any) ok = ok && sec_section_kept(L, E);       // (the section stays where it is: the host's copy of it is behind)
+            if (!ok) return PSDR_HIP_NEED_ROWS;
+        }
+        if (!rows_valid && !(blob_fits && layout_kept(L, T, E, has_tan) && env_emitter >= 0 && T.env_emitter >= 0 && !forced_host)) return PSDR_HIP_NEED_ROWS;
+        return 0;
     }
-    if (build || blob_moved || T.map_off != Told.map_off) {
-        for (int i = 0; i < n; ++i) H[4 * (size_t) T.map_off + (size_t) i] = ibits(sc->orig2slot[(size_t) i]);
-        mark((size_t) T.map_off, (size_t) T.map_off + words_for_floats((size_t) n));
+
+    // the first write of the tables: offsets from the layout, counts and frame from the snapshot, the traversal stack's split
+    void commit_tables() {
+        Told = T; Eold = E;
+        assign_offsets(L, T, E);
+        E.sum = s->sec_edges.sum;
+        T.n_filt = n_filt;
+        T.n_tris = s->tris.n_triangles; T.n_meshes = s->n_meshes; T.n_bsdfs = s->n_bsdfs; T.n_emitters = s->n_emitters;
+        T.n_fcdf = s->n_face_distrb; T.has_tangent = has_tan ? 1 : 0;
+        T.emitter_sum = s->emitter_sum;
+        T.width = s->width; T.height = s->height; T.spp = s->spp; T.sppe = s->sppe; T.sppse = s->sppse;
+        T.env_emitter = env_emitter;
+        // traversal stack: the first kStackLds entries of a lane in LDS, deeper ones in a per-lane global array (trav4.h);
+        // scenes that are traced by brute force (<= kBruteForceMax triangles) need neither
+        // kStackLdsMax + kTravRows = 40 KB per workgroup: four workgroups per CU (round 6: 12 stack rows + 2 rows of tree top, until then 8 + 6 - trav4.h).  Round 5 measured both sides of that choice on config 5 (LABNOTES): FEWER workgroups cost a lot
+        // (3 per CU: +17 %, 2: +55 %), a FIFTH brings nothing (a 30 KB layout - no hit rows, 4 stack rows - lost exactly what its shorter stack costs at equal
+        // occupancy), and stack rows going to the global tail cost 1.2 % (6 rows), 6.8 % (4), 9.5 % (2).
+        // PSDR_STACK_LDS = 2 ... kStackLdsMax (test knob, read when a scene is created or rebuilt): fewer rows, so that small test scenes reach the global tail too
+        // (tests/test_gpu_configs.py: the forked terms of a renderD against the serial call)
+        int kStackLds = kStackLdsMax;
+        if (const char *e = std::getenv("PSDR_STACK_LDS")) kStackLds = std::max(2, std::min(kStackLdsMax, std::atoi(e)));
+        T.stack_lds = uses_bvh ? std::min(kStackLds, sc->tree_max_stack) : 0;
+        T.stack_depth = uses_bvh ? T.stack_lds + kTravRows : kColdRows;   // BVH: + parked rays, best hits and the pair ring of the traversal (trav4.h); brute force: cold path state (paths.h)
     }
-    // ---- moved meshes: their rows computed on the device (geometry_on_device above) when nothing else about the layout changed; the host then writes none of them
-    bool dev_geo = false;
-    {
-        const bool layout_same = !fresh && !build && !blob_moved && uses_bvh && T.trav_off == Told.trav_off && T.shade_off == Told.shade_off && T.tan_off == Told.tan_off &&
-                                 T.map_off == Told.map_off && (has_tan ? 1 : 0) == Told.has_tangent && E.off == Eold.off && E.cdf_off == Eold.cdf_off && E.n == Eold.n;
+
+    // the blob: device allocation with head room, pinned host copy; the nodes of a new tree and the slot map go into the copy
+    int blob() {
+        const size_t w = L.words;
+        const int n = T.n_tris;
+        if (!sc->blob.p || sc->blob.bytes < 16 * w) {
+            // (room for the sensors' edge arrays at the size psdr_hip_scene_update_edges gives them - every edge of the meshes with edges - so that the first such update does not move the blob)
+            size_t reserve = 0;
+            if (!ereq && uses_bvh && s->geometry && s->sppe > 0) {
+                size_t ne_all = 0;
+                for (int i = 0; i < s->n_meshes; ++i) ne_all += (size_t) std::max(0, s->geometry[i].n_edges);
+                reserve = (size_t) s->n_sensors * (3 * ne_all + words_for_floats(2 * std::max<size_t>(1, ne_all)));
+            }
+            const size_t cap = 16 * (w + w / 4 + 64 + reserve);
+            void *fresh_p = nullptr;
+            HIPCHK(hipMalloc(&fresh_p, cap));
+            if (sc->blob.p) {
+                // the nodes a refit has written exist on the device only: they move with the allocation
+                if (!build && uses_bvh) HIPCHK(hipMemcpy((char *) fresh_p + 16 * (size_t) T.nodes_off, (const char *) sc->blob.p + 16 * (size_t) Told.nodes_off, 16 * (size_t) (kNodeFloats / 4) * (size_t) T.n_nodes, hipMemcpyDeviceToDevice));
+                HIPCHK(hipFree(sc->blob.p));
+                info.reallocated++;
+            }
+            sc->blob.p = fresh_p; sc->blob.bytes = cap;
+            blob_moved = true;
+        }
+        if (sc->hblob.ensure(sc->blob.bytes)) return 1;
+        H = (float *) sc->hblob.p;
+        if (build) {
+            std::memcpy(H + 4 * (size_t) T.nodes_off, new_nodes.data(), sizeof(float) * new_nodes.size());
+            mark((size_t) T.nodes_off, (size_t) T.nodes_off + new_nodes.size() / 4);
+        }
+        if (build || blob_moved || T.map_off != Told.map_off) {
+            for (int i = 0; i < n; ++i) H[4 * (size_t) T.map_off + (size_t) i] = ibits(sc->orig2slot[(size_t) i]);
+            mark((size_t) T.map_off, (size_t) T.map_off + words_for_floats((size_t) n));
+        }
+        return 0;
+    }
+
+    // moved meshes: their rows computed on the device (geometry_on_device above) when nothing else about the layout changed; the host then writes none of them
+    int geometry() {
+        const bool layout_same = !fresh && !build && !blob_moved && uses_bvh && layout_kept(L, Told, Eold, has_tan);
         const bool forced_host = std::getenv("PSDR_HOST_GEOMETRY") != nullptr;         // test knob, read per call: the host writes the rows (what psdr_hip_scene_check_rows compares with)
         if (layout_same && !forced_host && s->geometry != nullptr && (geo || !same_tan || !same_sec)) {
             if (geometry_on_device(sc, s, geo, has_tan && !same_tan, !same_sec, info, dev_geo)) return 1;
-            if (!dev_geo && !rows_valid) { sc->T = Told; sc->E = Eold; return PSDR_HIP_NEED_ROWS; }
+            if (!dev_geo && !rows_valid) return need_rows();
         }
         // (triangles the host writes below leave the device's world vertices behind: the next geometry_on_device recomputes every mesh)
         if (!dev_geo && (geo || !same_tan)) sc->geo_world_current = false;
-        if (dev_edges && !sc->geo_world_current) { sc->T = Told; sc->E = Eold; return PSDR_HIP_NEED_ROWS; }
-        if (sec_dev_any && !same_sec && !dev_geo) { sc->T = Told; sc->E = Eold; return PSDR_HIP_NEED_ROWS; }
+        if (dev_edges && !sc->geo_world_current) return need_rows();
+        if (sec_dev_any && !same_sec && !dev_geo) return need_rows();
+        return 0;
     }
+
     // (the pinned host copy of a section the device wrote is behind the device's; it is only ever sent after the host has rewritten the whole section from the snapshot -
     //  a change of the section itself, or a moved allocation, both of which write it first)
-    const bool write_geo = !dev_geo && (geo || blob_moved || T.trav_off != Told.trav_off || T.shade_off != Told.shade_off);
-    if (write_geo) {
-        parallel_for((size_t) n, 8192, [&](size_t b0, size_t e0) {
-            for (size_t slot = b0; slot < e0; ++slot) {
-                const size_t o = (size_t) order[slot];
-                const float *p0 = tr.p0 + 3 * o, *e1 = tr.e1 + 3 * o, *e2 = tr.e2 + 3 * o;
-                put4(H, T.trav_off + 3 * slot, p0[0], p0[1], p0[2], e1[0]);
-                put4(H, T.trav_off + 3 * slot + 1, e1[1], e1[2], e2[0], e2[1]);
-                put4(H, T.trav_off + 3 * slot + 2, e2[2], ibits((int32_t) o), 0.f, 0.f);
-                const float *n0 = tr.n0 + 3 * o, *n1 = tr.n1 + 3 * o, *n2 = tr.n2 + 3 * o, *fn = tr.face_normal + 3 * o;
-                const size_t sw = T.shade_off + 6 * slot;
-                put4(H, sw, n0[0], n0[1], n0[2], tr.face_area[o]);
-                put4(H, sw + 1, n1[0], n1[1], n1[2], ibits(tr.mesh_id[o]));
-                put4(H, sw + 2, n2[0], n2[1], n2[2], ibits(tr.use_face_normal && tr.use_face_normal[o] ? 1 : 0));
-                put4(H, sw + 3, fn[0], fn[1], fn[2], ibits((int32_t) o));
-                if (tr.uv) {
-                    const float *uv = tr.uv + 6 * o;
-                    put4(H, sw + 4, uv[0], uv[1], uv[2], uv[3]);
-                    put4(H, sw + 5, uv[4], uv[5], 0.f, 0.f);
-                } else { put4(H, sw + 4, 0.f, 0.f, 0.f, 0.f); put4(H, sw + 5, 0.f, 0.f, 0.f, 0.f); }
-            }
-        });
-        mark((size_t) T.trav_off, (size_t) T.trav_off + 9 * (size_t) n);
+    void tri_rows() {
+        const size_t n = (size_t) tr.n_triangles;
+        if (!dev_geo && (geo || blob_moved || T.trav_off != Told.trav_off || T.shade_off != Told.shade_off)) {
+            parallel_for(n, 8192, [&](size_t b0, size_t e0) {
+                for (size_t slot = b0; slot < e0; ++slot)
+                    pack_tri_rows(tr, (size_t) sc->order[slot], H + 4 * ((size_t) T.trav_off + kTravWords * slot), H + 4 * ((size_t) T.shade_off + kShadeWords * slot));
+            });
+            mark((size_t) T.trav_off, (size_t) T.trav_off + (kTravWords + kShadeWords) * n);
+        }
+        if (has_tan && !dev_geo && (!same_tan || blob_moved || T.tan_off != Told.tan_off || !Told.has_tangent)) {
+            parallel_for(n, 8192, [&](size_t b0, size_t e0) {
+                for (size_t slot = b0; slot < e0; ++slot) pack_tan_row(tr, (size_t) sc->order[slot], H + 4 * ((size_t) T.tan_off + kTanWords * slot));
+            });
+            mark((size_t) T.tan_off, (size_t) T.tan_off + kTanWords * n);
+        }
     }
-    if (has_tan && !dev_geo && (!same_tan || blob_moved || T.tan_off != Told.tan_off || !Told.has_tangent)) {
-        parallel_for((size_t) n, 8192, [&](size_t b0, size_t e0) {
-            for (size_t slot = b0; slot < e0; ++slot) {
-                const size_t o = (size_t) order[slot];
-                const float *a = tr.d_p0 + 3 * o, *b = tr.d_e1 + 3 * o, *c = tr.d_e2 + 3 * o, *d0 = tr.d_n0 + 3 * o, *d1 = tr.d_n1 + 3 * o,
-                            *d2 = tr.d_n2 + 3 * o, *df = tr.d_face_normal + 3 * o;
-                const size_t tw = T.tan_off + 6 * slot;
-                put4(H, tw, a[0], a[1], a[2], b[0]);
-                put4(H, tw + 1, b[1], b[2], c[0], c[1]);
-                put4(H, tw + 2, c[2], d0[0], d0[1], d0[2]);
-                put4(H, tw + 3, d1[0], d1[1], d1[2], d2[0]);
-                put4(H, tw + 4, d2[1], d2[2], df[0], df[1]);
-                put4(H, tw + 5, df[2], tr.d_face_area[o], 0.f, 0.f);
-            }
-        });
-        mark((size_t) T.tan_off, (size_t) T.tan_off + 6 * (size_t) n);
-    }
-    if (geo && uses_bvh) {
-        // (the bounding sphere and the filter primitives belong to the brute-force tracer, scene_dev.h::trace2: a BVH scene has neither - and the serial pass over its
-        //  triangles' vertices was 0.5 ms of every moved-vertex update of config 5)
-        T.center[0] = T.center[1] = T.center[2] = 0.f; T.radius = 0.f; T.filt_kmax = 0.f; T.filt_hasb[0] = T.filt_hasb[1] = 0u;
-    } else if (geo) {
-        // bounding sphere of the scene (for the absolute slack of the quad filter)
-        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-        for (int i = 0; i < n; ++i)
-            for (int v = 0; v < 3; ++v)
-                for (int k = 0; k < 3; ++k) {
-                    const double x = (double) tr.p0[3 * (size_t) i + k] + (v == 1 ? (double) tr.e1[3 * (size_t) i + k] : v == 2 ? (double) tr.e2[3 * (size_t) i + k] : 0.0);
-                    lo[k] = std::min(lo[k], x); hi[k] = std::max(hi[k], x);
+
+    // filter primitives and bounding sphere of the brute-force tracer
+    void filter() {
+        const int n = tr.n_triangles;
+        if (geo && uses_bvh) {
+            // (the bounding sphere and the filter primitives belong to the brute-force tracer, scene_dev.h::trace2: a BVH scene has neither - and the serial pass over its
+            //  triangles' vertices was 0.5 ms of every moved-vertex update of config 5)
+            T.center[0] = T.center[1] = T.center[2] = 0.f; T.radius = 0.f; T.filt_kmax = 0.f; T.filt_hasb[0] = T.filt_hasb[1] = 0u;
+        } else if (geo) {
+            // bounding sphere of the scene (for the absolute slack of the quad filter)
+            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+            for (int i = 0; i < n; ++i)
+                for (int v = 0; v < 3; ++v)
+                    for (int k = 0; k < 3; ++k) {
+                        const double x = (double) tr.p0[3 * (size_t) i + k] + (v == 1 ? (double) tr.e1[3 * (size_t) i + k] : v == 2 ? (double) tr.e2[3 * (size_t) i + k] : 0.0);
+                        lo[k] = std::min(lo[k], x); hi[k] = std::max(hi[k], x);
+                    }
+            double r2 = 0.0;
+            for (int k = 0; k < 3; ++k) { T.center[k] = (float) (0.5 * (lo[k] + hi[k])); r2 += 0.25 * (hi[k] - lo[k]) * (hi[k] - lo[k]); }
+            T.radius = (float) (std::sqrt(r2) * 1.0001);
+            T.filt_kmax = 0.f;
+            T.filt_hasb[0] = T.filt_hasb[1] = 0u;
+            for (size_t i = 0; i < filt.size(); ++i) {
+                // dot-product form of the filter (scene_dev.h::trace2): with oc = o - centre, m = oc x d and p = p0 - centre
+                //   u-numerator = m.e2 + d.(p x e2)   v-numerator = d.(e1 x p) - m.e1   -det = d.(e1 x e2)   t-numerator = oc.(e1 x e2) - p.(e1 x e2)
+                const FilterPrim &f = filt[i];
+                const size_t fw = T.filt_off + 6 * i;
+                {
+                    const size_t base = i & ~(size_t) 31, cnt = std::min<size_t>(32, filt.size() - base);
+                    if (f.slot_b >= 0) T.filt_hasb[i >> 5] |= 1u << (cnt - 1 - (i - base));
                 }
-        double r2 = 0.0;
-        for (int k = 0; k < 3; ++k) { T.center[k] = (float) (0.5 * (lo[k] + hi[k])); r2 += 0.25 * (hi[k] - lo[k]) * (hi[k] - lo[k]); }
-        T.radius = (float) (std::sqrt(r2) * 1.0001);
-        T.filt_kmax = 0.f;
-        T.filt_hasb[0] = T.filt_hasb[1] = 0u;
-        for (size_t i = 0; i < filt.size(); ++i) {
-            // dot-product form of the filter (scene_dev.h::trace2): with oc = o - centre, m = oc x d and p = p0 - centre
-            //   u-numerator = m.e2 + d.(p x e2)   v-numerator = d.(e1 x p) - m.e1   -det = d.(e1 x e2)   t-numerator = oc.(e1 x e2) - p.(e1 x e2)
-            const FilterPrim &f = filt[i];
-            const size_t fw = T.filt_off + 6 * i;
-            {
-                const size_t base = i & ~(size_t) 31, cnt = std::min<size_t>(32, filt.size() - base);
-                if (f.slot_b >= 0) T.filt_hasb[i >> 5] |= 1u << (cnt - 1 - (i - base));
+                const double p[3] = {(double) f.p0[0] - (double) T.center[0], (double) f.p0[1] - (double) T.center[1], (double) f.p0[2] - (double) T.center[2]};
+                const double e1[3] = {f.e1[0], f.e1[1], f.e1[2]}, e2[3] = {f.e2[0], f.e2[1], f.e2[2]};
+                auto crs = [](const double *a, const double *b, double *c) { c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0]; };
+                double A[3], B[3], N[3];
+                crs(p, e2, A); crs(e1, p, B); crs(e1, e2, N);
+                const double npn = -(p[0] * N[0] + p[1] * N[1] + p[2] * N[2]);
+                const double K = std::max({std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), std::sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]), (double) f.k16 * 32768.0});
+                T.filt_kmax = std::max(T.filt_kmax, (float) (K * 1.0001));
+                put4(H, fw, f.e2[0], f.e2[1], f.e2[2], (float) A[0]);
+                put4(H, fw + 1, (float) A[1], (float) A[2], f.e1[0], f.e1[1]);
+                put4(H, fw + 2, f.e1[2], (float) B[0], (float) B[1], (float) B[2]);
+                put4(H, fw + 3, (float) N[0], (float) N[1], (float) N[2], (float) npn);
+                put4(H, fw + 4, f.umax, f.vmax, f.smax, f.da);
+                put4(H, fw + 5, f.db, f.da + f.db, (float) (K * (1.0001 / 32768.0)), ibits(f.slot_a | ((f.slot_b < 0 ? 0xff : f.slot_b) << 8)));
             }
-            const double p[3] = {(double) f.p0[0] - (double) T.center[0], (double) f.p0[1] - (double) T.center[1], (double) f.p0[2] - (double) T.center[2]};
-            const double e1[3] = {f.e1[0], f.e1[1], f.e1[2]}, e2[3] = {f.e2[0], f.e2[1], f.e2[2]};
-            auto crs = [](const double *a, const double *b, double *c) { c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0]; };
-            double A[3], B[3], N[3];
-            crs(p, e2, A); crs(e1, p, B); crs(e1, e2, N);
-            const double npn = -(p[0] * N[0] + p[1] * N[1] + p[2] * N[2]);
-            const double K = std::max({std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), std::sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]), (double) f.k16 * 32768.0});
-            T.filt_kmax = std::max(T.filt_kmax, (float) (K * 1.0001));
-            put4(H, fw, f.e2[0], f.e2[1], f.e2[2], (float) A[0]);
-            put4(H, fw + 1, (float) A[1], (float) A[2], f.e1[0], f.e1[1]);
-            put4(H, fw + 2, f.e1[2], (float) B[0], (float) B[1], (float) B[2]);
-            put4(H, fw + 3, (float) N[0], (float) N[1], (float) N[2], (float) npn);
-            put4(H, fw + 4, f.umax, f.vmax, f.smax, f.da);
-            put4(H, fw + 5, f.db, f.da + f.db, (float) (K * (1.0001 / 32768.0)), ibits(f.slot_a | ((f.slot_b < 0 ? 0xff : f.slot_b) << 8)));
+            mark((size_t) T.filt_off, (size_t) T.filt_off + 6 * filt.size());
+        } else if (blob_moved) mark((size_t) T.filt_off, (size_t) T.filt_off + 6 * (size_t) T.n_filt);       // (same triangles: same offset, the host copy is current)
+    }
+
+    // the small tables - mesh, BSDF and emitter records, emitter and face distributions: always written
+    void small_tables() {
+        std::memset(H + 4 * L.small_begin, 0, 16 * (L.small_end - L.small_begin));
+        for (int i = 0; i < s->n_meshes; ++i) {
+            const psdr_mesh_rec &m = s->meshes[i];
+            put4(H, T.mesh_off + 2 * (size_t) i, ibits(m.bsdf_id), ibits(m.emitter_id), ibits(m.face_offset), ibits(m.n_faces));
+            put4(H, T.mesh_off + 2 * (size_t) i + 1, m.inv_total_area, ibits(m.distrb_offset), m.distrb_sum, 0.f);
         }
-        mark((size_t) T.filt_off, (size_t) T.filt_off + 6 * filt.size());
-    } else if (blob_moved) mark((size_t) T.filt_off, (size_t) T.filt_off + 6 * (size_t) T.n_filt);       // (same triangles: same offset, the host copy is current)
-
-    // ---- the small tables: always written
-    std::memset(H + 4 * small_begin, 0, 16 * (small_end - small_begin));
-    for (int i = 0; i < s->n_meshes; ++i) {
-        const psdr_mesh_rec &m = s->meshes[i];
-        put4(H, T.mesh_off + 2 * (size_t) i, ibits(m.bsdf_id), ibits(m.emitter_id), ibits(m.face_offset), ibits(m.n_faces));
-        put4(H, T.mesh_off + 2 * (size_t) i + 1, m.inv_total_area, ibits(m.distrb_offset), m.distrb_sum, 0.f);
-    }
-    sc->simple_mats = true; sc->has_nmap = false;
-    for (int i = 0; i < s->n_bsdfs; ++i) {
-        const psdr_bsdf_rec &b = s->bsdfs[i];
-        // (a NormalMap, type 5, is its nested BSDF seen through the map: the nested record is an entry of its own and decides)
-        if (b.type == 5) sc->has_nmap = true;
-        put4(H, T.bsdf_off + 2 * (size_t) i, b.reflectance[0], b.reflectance[1], b.reflectance[2], ibits((b.two_sided ? 1 : 0) | (b.tex_data ? 2 : 0) | (b.type == 1 ? 4 : 0) | (b.type == 2 ? 8 : 0) | (b.type == 3 ? 16 : 0) | (b.spec_tex_data ? 32 : 0) | (b.rough_tex_data ? 64 : 0) | (b.type == 4 ? 128 : 0) | (b.type == 5 ? 256 : 0)));
-        put4(H, T.bsdf_off + 2 * (size_t) i + 1, b.d_reflectance[0], b.d_reflectance[1], b.d_reflectance[2], ibits(b.type == 5 ? b.nested_bsdf : -1));
-    }
-    for (int i = 0; i < s->n_emitters; ++i) {
-        const psdr_emitter_rec &e = s->emitters[i];
-        put4(H, T.emit_off + 2 * (size_t) i, e.radiance[0], e.radiance[1], e.radiance[2], e.sampling_weight);
-        put4(H, T.emit_off + 2 * (size_t) i + 1, e.d_radiance[0], e.d_radiance[1], e.d_radiance[2], ibits(e.mesh_id));
-        H[4 * (size_t) T.ecdf_off + (size_t) i] = s->emitter_pmf ? s->emitter_pmf[i] : 1.f;
-        H[4 * (size_t) T.ecdf_off + (size_t) s->n_emitters + (size_t) i] = s->emitter_cmf ? s->emitter_cmf[i] : 1.f;
-    }
-    for (int i = 0; i < s->n_face_distrb; ++i) {
-        H[4 * (size_t) T.fcdf_off + (size_t) i] = s->face_pmf[i];
-        H[4 * (size_t) T.fcdf_off + (size_t) s->n_face_distrb + (size_t) i] = s->face_cmf[i];
-    }
-    mark(small_begin, small_end);
-
-    // ---- secondary edges
-    const bool write_sec = !same_sec || blob_moved || E.off != Eold.off || E.cdf_off != Eold.cdf_off || E.n != Eold.n;
-    if (sec_dev_any && write_sec && !dev_geo) return fail("psdr_hip_scene_update_edges: no secondary-edge distribution in the snapshot and none to compute");
-    int sec_cdf_mode = 0;
-    int64_t sec_bytes = 0;                                          // what goes up for the secondary-edge DISTRIBUTION (pmf, cmf, search table)
-    if (sec_dev_any && !write_sec) E.sum = Eold.sum;               // (the device's distribution stands: its sum is the one it was given then)
-    if (write_sec && se.n_edges > 0 && dev_geo && sec_dev_any) {
-        // the rows are the device's, and so is the distribution over them: lengths, then the cmf and its search table (cdf_on_device); the lengths come back for the float sum
-        const int ne = se.n_edges;
-        DevBuf &rg = sc->buf("sec.range");
-        if (rg.ensure(2 * sizeof(int))) return 1;
-        float *pmf = (float *) sc->blob.p + 4 * (size_t) E.cdf_off;
-        hipLaunchKernelGGL(k_cdf_range_reset, dim3(1), dim3(1), 0, nullptr, (int *) rg.p);
-        hipLaunchKernelGGL(k_se_length, dim3((unsigned) ((ne + 255) / 256)), dim3(256), 0, nullptr, sc->buf("geo.edges").as<int>(), sc->buf("geo.world").as<float>(), pmf, (int *) rg.p, ne);
-        HIPCHK(hipGetLastError());
-        std::vector<float> len((size_t) ne);
-        HIPCHK(hipMemcpy(len.data(), pmf, sizeof(float) * (size_t) ne, hipMemcpyDeviceToHost));
-        float sum = 0.f;
-        for (int i = 0; i < ne; ++i) sum += len[(size_t) i];
-        E.sum = sum;
-        if (cdf_on_device(sc, pmf, pmf + ne, len.data(), ne, ne, sum, (const int *) rg.p, "sec.guide", E.guide, E.guide_n, &sec_cdf_mode, info, sec_bytes)) return 1;
-    } else if (write_sec && se.n_edges > 0 && dev_geo) {
-        // (the rows are the device's; the distribution over the edges - a sequential float prefix sum - comes from the host)
-        std::memcpy(H + 4 * (size_t) E.cdf_off, se.pmf, sizeof(float) * (size_t) se.n_edges);
-        std::memcpy(H + 4 * (size_t) E.cdf_off + (size_t) se.n_edges, se.cmf, sizeof(float) * (size_t) se.n_edges);
-        mark((size_t) E.cdf_off, sec_end);
-        sec_bytes += (int64_t) (8 * (size_t) se.n_edges);
-    } else if (write_sec && se.n_edges > 0) {
-        parallel_for((size_t) se.n_edges, 8192, [&](size_t b0, size_t e0) {
-            const float z3[3] = {0.f, 0.f, 0.f};
-            for (size_t i = b0; i < e0; ++i) {
-                const float *p0 = se.p0 + 3 * i, *e1 = se.e1 + 3 * i, *n0 = se.n0 + 3 * i, *n1 = se.n1 + 3 * i, *p2 = se.p2 + 3 * i;
-                const float *dp0 = se.d_p0 ? se.d_p0 + 3 * i : z3, *de1 = se.d_e1 ? se.d_e1 + 3 * i : z3;
-                const size_t ew = E.off + 6 * i;
-                put4(H, ew, p0[0], p0[1], p0[2], e1[0]);
-                put4(H, ew + 1, e1[1], e1[2], n0[0], n0[1]);
-                put4(H, ew + 2, n0[2], n1[0], n1[1], n1[2]);
-                put4(H, ew + 3, p2[0], p2[1], p2[2], ibits(se.is_boundary[i] ? 1 : 0));
-                put4(H, ew + 4, dp0[0], dp0[1], dp0[2], de1[0]);
-                put4(H, ew + 5, de1[1], de1[2], 0.f, 0.f);
-                H[4 * (size_t) E.cdf_off + i] = se.pmf[i];
-                H[4 * (size_t) E.cdf_off + (size_t) se.n_edges + i] = se.cmf[i];
-            }
-        });
-        mark((size_t) E.off, sec_end);
-        sec_bytes += (int64_t) (8 * (size_t) se.n_edges);
-    }
-    if (write_sec && sec_cdf_mode != 0) { /* (cdf_on_device has made the table) */ }
-    else if (write_sec) {
-        E.guide = nullptr; E.guide_n = 0;
-        if (se.n_edges > 0 && se.cmf) {              // every sample of the secondary-edge term starts with this search (17 dependent loads for config 5's 122 885 edges)
-            std::vector<int> guide;
-            build_cdf_guide(se.cmf, se.n_edges, se.sum, guide, 4);
-            if (!guide.empty()) {
-                if (sync_named(sc, "sec.guide", guide.data(), guide.size() * sizeof(int), false, E.guide, info)) return 1;
-                E.guide_n = (int) guide.size() - 1;
-                sec_bytes += (int64_t) (guide.size() * sizeof(int));
-            }
+        sc->simple_mats = true; sc->has_nmap = false;
+        for (int i = 0; i < s->n_bsdfs; ++i) {
+            const psdr_bsdf_rec &b = s->bsdfs[i];
+            // (a NormalMap, type 5, is its nested BSDF seen through the map: the nested record is an entry of its own and decides)
+            if (b.type == 5) sc->has_nmap = true;
+            put4(H, T.bsdf_off + 2 * (size_t) i, b.reflectance[0], b.reflectance[1], b.reflectance[2], ibits((b.two_sided ? 1 : 0) | (b.tex_data ? 2 : 0) | (b.type == 1 ? 4 : 0) | (b.type == 2 ? 8 : 0) | (b.type == 3 ? 16 : 0) | (b.spec_tex_data ? 32 : 0) | (b.rough_tex_data ? 64 : 0) | (b.type == 4 ? 128 : 0) | (b.type == 5 ? 256 : 0)));
+            put4(H, T.bsdf_off + 2 * (size_t) i + 1, b.d_reflectance[0], b.d_reflectance[1], b.d_reflectance[2], ibits(b.type == 5 ? b.nested_bsdf : -1));
         }
-    } else { E.guide = Eold.guide; E.guide_n = Eold.guide_n; }
+        for (int i = 0; i < s->n_emitters; ++i) {
+            const psdr_emitter_rec &e = s->emitters[i];
+            put4(H, T.emit_off + 2 * (size_t) i, e.radiance[0], e.radiance[1], e.radiance[2], e.sampling_weight);
+            put4(H, T.emit_off + 2 * (size_t) i + 1, e.d_radiance[0], e.d_radiance[1], e.d_radiance[2], ibits(e.mesh_id));
+            pack_distrb(H + 4 * (size_t) T.ecdf_off, (size_t) s->n_emitters, (size_t) i, s->emitter_pmf ? s->emitter_pmf[i] : 1.f, s->emitter_cmf ? s->emitter_cmf[i] : 1.f);
+        }
+        for (int i = 0; i < s->n_face_distrb; ++i) pack_distrb(H + 4 * (size_t) T.fcdf_off, (size_t) s->n_face_distrb, (size_t) i, s->face_pmf[i], s->face_cmf[i]);
+        mark(L.small_begin, L.small_end);
+    }
 
-    // ---- sensors: matrices, primary edges, live-pixel masks
-    const std::vector<SensorDev> sensors_old = sc->sensors;
-    const std::vector<float> w2s_old = sc->sensor_w2s;
-    sc->sensors.assign((size_t) s->n_sensors, SensorDev{});
-    sc->sensor_w2s.assign(16 * (size_t) s->n_sensors, 0.f);
-    sc->live_host.resize((size_t) s->n_sensors);
-    sc->pe_ids.resize((size_t) s->n_sensors);
-    int64_t edge_bytes = 0;
-    int edge_path = sec_cdf_mode;
-    bool any_sensor_dev = false;
-    for (int k = 0; ereq && k < s->n_sensors; ++k) any_sensor_dev = any_sensor_dev || ereq->mode[k] == PSDR_EDGES_DEVICE;
-    if (any_sensor_dev && pe_sync_topology(sc, s, ereq->topo, edge_bytes)) return 1;
-    info.bytes_uploaded += edge_bytes;
-    edge_bytes += sec_bytes;
-    for (int k = 0; k < s->n_sensors; ++k) {
+    // secondary edges: rows and distribution from the host, rows from the device and the distribution from the host, or both from the device
+    int sec_edges() {
+        const psdr_sec_edges &se = s->sec_edges;
+        const bool write_sec = !same_sec || blob_moved || !sec_section_kept(L, Eold);
+        if (sec_dev_any && write_sec && !dev_geo) return fail("psdr_hip_scene_update_edges: no secondary-edge distribution in the snapshot and none to compute");
+        if (sec_dev_any && !write_sec) E.sum = Eold.sum;               // (the device's distribution stands: its sum is the one it was given then)
+        if (write_sec && se.n_edges > 0 && dev_geo && sec_dev_any) {
+            // the rows are the device's, and so is the distribution over them: lengths, then the cmf and its search table (cdf_on_device); the lengths come back for the float sum
+            const int ne = se.n_edges;
+            DevBuf &rg = sc->buf("sec.range");
+            if (rg.ensure(2 * sizeof(int))) return 1;
+            float *pmf = (float *) sc->blob.p + 4 * (size_t) E.cdf_off;
+            hipLaunchKernelGGL(k_cdf_range_reset, dim3(1), dim3(1), 0, nullptr, (int *) rg.p);
+            hipLaunchKernelGGL(k_se_length, dim3((unsigned) ((ne + 255) / 256)), dim3(256), 0, nullptr, sc->buf("geo.edges").as<int>(), sc->buf("geo.world").as<float>(), pmf, (int *) rg.p, ne);
+            HIPCHK(hipGetLastError());
+            std::vector<float> len((size_t) ne);
+            HIPCHK(hipMemcpy(len.data(), pmf, sizeof(float) * (size_t) ne, hipMemcpyDeviceToHost));
+            float sum = 0.f;
+            for (int i = 0; i < ne; ++i) sum += len[(size_t) i];
+            E.sum = sum;
+            if (cdf_on_device(sc, pmf, pmf + ne, len.data(), ne, ne, sum, (const int *) rg.p, "sec.guide", E.guide, E.guide_n, &sec_cdf_mode, info, sec_bytes)) return 1;
+        } else if (write_sec && se.n_edges > 0 && dev_geo) {
+            // (the rows are the device's; the distribution over the edges - a sequential float prefix sum - comes from the host)
+            std::memcpy(H + 4 * (size_t) E.cdf_off, se.pmf, sizeof(float) * (size_t) se.n_edges);
+            std::memcpy(H + 4 * (size_t) E.cdf_off + (size_t) se.n_edges, se.cmf, sizeof(float) * (size_t) se.n_edges);
+            mark((size_t) E.cdf_off, L.sec_end);
+            sec_bytes += (int64_t) (8 * (size_t) se.n_edges);
+        } else if (write_sec && se.n_edges > 0) {
+            parallel_for((size_t) se.n_edges, 8192, [&](size_t b0, size_t e0) {
+                for (size_t i = b0; i < e0; ++i) {
+                    pack_sec_row(se, i, H + 4 * ((size_t) E.off + kSecWords * i));
+                    pack_distrb(H + 4 * (size_t) E.cdf_off, (size_t) se.n_edges, i, se.pmf[i], se.cmf[i]);
+                }
+            });
+            mark((size_t) E.off, L.sec_end);
+            sec_bytes += (int64_t) (8 * (size_t) se.n_edges);
+        }
+        if (write_sec && sec_cdf_mode != 0) return 0;              // (cdf_on_device has made the table)
+        if (!write_sec) { E.guide = Eold.guide; E.guide_n = Eold.guide_n; return 0; }
+        // every sample of the secondary-edge term starts with this search (17 dependent loads for config 5's 122 885 edges)
+        return sync_guide(sc, "sec.guide", se.cmf, se.n_edges, se.sum, 4, E.guide, E.guide_n, &sec_bytes, info);
+    }
+
+    // sensor k: matrices, primary edges (the host's arrays, selected on the device, or kept), live-pixel mask.  od: the sensor as it was (NULL: there was none)
+    int sensor(int k, const SensorDev *od, const std::vector<float> &w2s_old) {
         const psdr_sensor_rec &r = s->sensors[k];
         SensorDev &d = sc->sensors[(size_t) k];
-        const SensorDev *od = (size_t) k < sensors_old.size() ? &sensors_old[(size_t) k] : nullptr;
         std::memcpy(d.sample_to_camera.m, r.sample_to_camera, 64); std::memcpy(d.to_world.m, r.to_world, 64);
         std::memcpy(d.d_to_world.m, r.d_to_world, 64); std::memcpy(d.world_to_sample.m, r.world_to_sample, 64);
         std::memcpy(d.d_world_to_sample.m, r.d_world_to_sample, 64);
         for (int q = 0; q < 3; ++q) { d.cam_pos[q] = r.cam_pos[q]; d.cam_dir[q] = r.cam_dir[q]; }
         d.inv_area = r.inv_area; d.n_edges = r.n_edges; d.edge_sum = r.edge_sum; d.ortho = r.orthographic;
-        d.pe_off = pe_offs[(size_t) k].first; d.pecdf_off = pe_offs[(size_t) k].second;
+        d.pe_off = L.pe[(size_t) k].first; d.pecdf_off = L.pe[(size_t) k].second;
         const int pe_mode = ereq ? ereq->mode[k] : PSDR_EDGES_HOST;
         // (a sensor without edges before and after, where it was: nothing to write)
         const bool still_empty = r.n_edges <= 0 && od && od->n_edges <= 0 && !blob_moved && od->pe_off == d.pe_off && od->pecdf_off == d.pecdf_off;
@@ -1163,57 +1132,63 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
         } else if (pe_mode == PSDR_EDGES_KEEP) {
             d.n_edges = od->n_edges; d.edge_sum = od->edge_sum; d.pe_guide = od->pe_guide; d.pe_guide_n = od->pe_guide_n;
         } else if (write_pe) {
+            const size_t ne = (size_t) std::max(0, r.n_edges);
             sc->pe_ids[(size_t) k].clear();
-            edge_bytes += (int64_t) (16 * (3 * (size_t) std::max(0, r.n_edges) + words_for_floats(2 * (size_t) std::max(1, r.n_edges))));
-            parallel_for((size_t) std::max(0, r.n_edges), 8192, [&](size_t ib, size_t ie) {
-              for (size_t i = ib; i < ie; ++i) {
-                const size_t pw = (size_t) d.pe_off + 3 * (size_t) i;
-                put4(H, pw, r.edge_p0[2 * i], r.edge_p0[2 * i + 1], r.edge_p1[2 * i], r.edge_p1[2 * i + 1]);
-                put4(H, pw + 1, r.d_edge_p0 ? r.d_edge_p0[2 * i] : 0.f, r.d_edge_p0 ? r.d_edge_p0[2 * i + 1] : 0.f,
-                     r.d_edge_p1 ? r.d_edge_p1[2 * i] : 0.f, r.d_edge_p1 ? r.d_edge_p1[2 * i + 1] : 0.f);
-                put4(H, pw + 2, r.edge_normal[2 * i], r.edge_normal[2 * i + 1], r.edge_length[i], 0.f);
-                H[4 * (size_t) d.pecdf_off + (size_t) i] = r.edge_pmf[i];
-                H[4 * (size_t) d.pecdf_off + (size_t) r.n_edges + (size_t) i] = r.edge_cmf[i];
-              }
+            edge_bytes += (int64_t) (16 * (kPeWords * ne + words_for_floats(2 * (size_t) std::max(1, r.n_edges))));
+            parallel_for(ne, 8192, [&](size_t ib, size_t ie) {
+                for (size_t i = ib; i < ie; ++i) {
+                    pack_pe_row(r, i, H + 4 * ((size_t) d.pe_off + kPeWords * i));
+                    pack_distrb(H + 4 * (size_t) d.pecdf_off, ne, i, r.edge_pmf[i], r.edge_cmf[i]);
+                }
             });
             // (two ranges: under psdr_hip_scene_update_edges the section has room for every edge and the CDF starts behind that room)
-            mark((size_t) d.pe_off, (size_t) d.pe_off + 3 * (size_t) std::max(0, r.n_edges));
+            mark((size_t) d.pe_off, (size_t) d.pe_off + kPeWords * ne);
             mark((size_t) d.pecdf_off, (size_t) d.pecdf_off + words_for_floats(2 * (size_t) std::max(1, r.n_edges)));
-            d.pe_guide = nullptr; d.pe_guide_n = 0;
-            if (r.n_edges > 0 && r.edge_cmf) {       // a sample of the primary-edge term starts with this search (15 dependent loads for config 5's 26 592 edges)
-                std::vector<int> guide;
-                build_cdf_guide(r.edge_cmf, r.n_edges, r.edge_sum, guide, 4);
-                if (!guide.empty()) {
-                    if (sync_named(sc, "sensor." + std::to_string(k) + ".guide", guide.data(), guide.size() * sizeof(int), false, d.pe_guide, info)) return 1;
-                    d.pe_guide_n = (int) guide.size() - 1;
-                    edge_bytes += (int64_t) (guide.size() * sizeof(int));
-                }
-            }
+            // a sample of the primary-edge term starts with this search (15 dependent loads for config 5's 26 592 edges)
+            if (sync_guide(sc, "sensor." + std::to_string(k) + ".guide", r.edge_cmf, r.n_edges, r.edge_sum, 4, d.pe_guide, d.pe_guide_n, &edge_bytes, info)) return 1;
         } else { d.pe_guide = od->pe_guide; d.pe_guide_n = od->pe_guide_n; }
         // live-pixel mask: a function of the triangles, this sensor's world_to_sample and the frame size
         std::memcpy(&sc->sensor_w2s[16 * (size_t) k], r.world_to_sample, 64);
         const bool same_view = od && !geo && 16 * (size_t) k + 16 <= w2s_old.size() && std::memcmp(&w2s_old[16 * (size_t) k], r.world_to_sample, 64) == 0 &&
                                Told.width == T.width && Told.height == T.height && (Told.env_emitter >= 0) == (T.env_emitter >= 0) &&
                                ((long long) Told.width * Told.height * std::max(1, Told.spp) < (1ll << 31)) == ((long long) T.width * T.height * std::max(1, T.spp) < (1ll << 31));
-        if (same_view) d.live = od->live;
-        else {
-            d.live = nullptr;
-            std::vector<unsigned> live;
-            static const bool no_live = std::getenv("PSDR_NO_LIVE_MASK") != nullptr;       // documented switch (include/psdr_hip.h): render the provably-zero samples as well
-            bool use = !no_live && T.env_emitter < 0 && (long long) s->width * s->height * std::max(1, s->spp) < (1ll << 31) && build_live_mask(s->tris, r.world_to_sample, s->width, s->height, live);
-            if (use) {       // worth a window of bit tests per regeneration only when a good part of the frame is dead (the sphere box, all of it live: +1.7 % with the mask)
-                long long n_set = 0;
-                for (unsigned x : live) n_set += __builtin_popcount(x);
-                use = n_set * 4 <= (long long) s->width * s->height * 3;
-            }
-            if (use) { if (sync_named(sc, "sensor." + std::to_string(k) + ".live", live.data(), live.size() * sizeof(unsigned), false, d.live, info)) return 1; }
-            else live.clear();
-            sc->live_host[(size_t) k].swap(live);
+        if (same_view) { d.live = od->live; return 0; }
+        d.live = nullptr;
+        std::vector<unsigned> live;
+        static const bool no_live = std::getenv("PSDR_NO_LIVE_MASK") != nullptr;       // documented switch (include/psdr_hip.h): render the provably-zero samples as well
+        bool use = !no_live && T.env_emitter < 0 && (long long) s->width * s->height * std::max(1, s->spp) < (1ll << 31) && build_live_mask(s->tris, r.world_to_sample, s->width, s->height, live);
+        if (use) {       // worth a window of bit tests per regeneration only when a good part of the frame is dead (the sphere box, all of it live: +1.7 % with the mask)
+            long long n_set = 0;
+            for (unsigned x : live) n_set += __builtin_popcount(x);
+            use = n_set * 4 <= (long long) s->width * s->height * 3;
         }
+        if (use) { if (sync_named(sc, "sensor." + std::to_string(k) + ".live", live.data(), live.size() * sizeof(unsigned), false, d.live, info)) return 1; }
+        else live.clear();
+        sc->live_host[(size_t) k].swap(live);
+        return 0;
     }
 
-    // ---- environment map (global memory, outside the blob)
-    if (T.env_emitter >= 0) {
+    int sensors() {
+        const std::vector<SensorDev> sensors_old = sc->sensors;
+        const std::vector<float> w2s_old = sc->sensor_w2s;
+        sc->sensors.assign((size_t) s->n_sensors, SensorDev{});
+        sc->sensor_w2s.assign(16 * (size_t) s->n_sensors, 0.f);
+        sc->live_host.resize((size_t) s->n_sensors);
+        sc->pe_ids.resize((size_t) s->n_sensors);
+        edge_path = sec_cdf_mode;
+        bool any_sensor_dev = false;
+        for (int k = 0; ereq && k < s->n_sensors; ++k) any_sensor_dev = any_sensor_dev || ereq->mode[k] == PSDR_EDGES_DEVICE;
+        if (any_sensor_dev && pe_sync_topology(sc, s, ereq->topo, edge_bytes)) return 1;
+        info.bytes_uploaded += edge_bytes;
+        edge_bytes += sec_bytes;
+        for (int k = 0; k < s->n_sensors; ++k)
+            if (sensor(k, (size_t) k < sensors_old.size() ? &sensors_old[(size_t) k] : nullptr, w2s_old)) return 1;
+        return 0;
+    }
+
+    // environment map (global memory, outside the blob)
+    int environment() {
+        if (T.env_emitter < 0) { T.env = EnvDev{}; return 0; }
         const psdr_envmap_rec *er = s->envmap;
         if (!er || !er->radiance || !er->cell_pmf || !er->cell_cmf || er->width < 2 || er->height < 2) return fail("EnvironmentMap emitter without a configured psdr_envmap_rec");
         EnvDev &ED = T.env;
@@ -1226,119 +1201,117 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
         if (sync_named(sc, "env.cell_cmf", er->cell_cmf, cells * sizeof(float), keep, ED.cell_cmf, info)) return 1;
         if (sync_named(sc, "env.d_radiance", er->d_radiance, texels * sizeof(float), keep && same_env_tan && had_d, ED.d_radiance, info)) return 1;
         if (keep) { ED.cell_guide = old_guide; ED.guide_n = old_guide_n; }
-        else {
-            ED.cell_guide = nullptr; ED.guide_n = 0;
-            std::vector<int> guide;
-            build_cdf_guide(er->cell_cmf, (int) cells, er->cell_sum, guide);
-            if (!guide.empty()) {
-                if (sync_named(sc, "env.guide", guide.data(), guide.size() * sizeof(int), false, ED.cell_guide, info)) return 1;
-                ED.guide_n = (int) guide.size() - 1;
-            }
-        }
+        else if (sync_guide(sc, "env.guide", er->cell_cmf, (int) cells, er->cell_sum, 32, ED.cell_guide, ED.guide_n, nullptr, info)) return 1;
         ED.width = er->width; ED.height = er->height; ED.reso0 = er->reso[0]; ED.reso1 = er->reso[1]; ED.num_cells = (int) cells;
         ED.scale = er->scale; ED.cell_sum = er->cell_sum;
         std::memcpy(ED.to_world.m, er->to_world, 64); std::memcpy(ED.from_world.m, er->from_world, 64);
         std::memcpy(ED.d_from_world.m, er->d_from_world, 64); ED.d_scale = er->d_scale;
         for (int k = 0; k < 3; ++k) { ED.lower[k] = er->lower[k]; ED.upper[k] = er->upper[k]; }
         for (int k = 0; k < 4; ++k) { ED.xf[k] = er->radiance_xf[k]; ED.d_xf[k] = er->d_radiance_xf[k]; }
-    } else T.env = EnvDev{};
+        return 0;
+    }
 
-    // ---- bitmap parameters: three slots per BSDF - [0] reflectance / diffuse reflectance (rgb), [1] specular (rgb), [2] roughness (1 channel)
-    T.tex = nullptr;
-    sc->tex_total = 0;
-    sc->tex_layout.clear();
-    {
+    // bitmap parameters: three slots per BSDF - [0] reflectance / diffuse reflectance (rgb), [1] specular (rgb), [2] roughness (1 channel)
+    int bitmaps() {
+        T.tex = nullptr;
+        sc->tex_total = 0;
+        sc->tex_layout.clear();
         bool any_tex = false;
         for (int i = 0; i < s->n_bsdfs; ++i) any_tex |= s->bsdfs[i].tex_data != nullptr || s->bsdfs[i].spec_tex_data != nullptr || s->bsdfs[i].rough_tex_data != nullptr;
-        if (any_tex) {
-            std::vector<TexDev> td((size_t) 3 * s->n_bsdfs, TexDev{nullptr, nullptr, 0, 0, -1, {0.f, 1.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}});
-            for (int i = 0; i < s->n_bsdfs; ++i) {
-                const psdr_bsdf_rec &b = s->bsdfs[i];
-                const float *src[3] = {b.tex_data, b.spec_tex_data, b.rough_tex_data}, *dsrc[3] = {b.d_tex_data, b.d_spec_tex_data, b.d_rough_tex_data};
-                const int tw[3] = {b.tex_width, b.spec_tex_width, b.rough_tex_width}, th[3] = {b.tex_height, b.spec_tex_height, b.rough_tex_height};
-                for (int k = 0; k < 3; ++k) {
-                    if (!src[k]) continue;
-                    if (k > 0 && b.type != 1 && b.type != 2 && !(b.type == 3 && k == 2)) return fail("this BSDF type has no second / third bitmap parameter");
-                    if (tw[k] < 2 || th[k] < 2) return fail("Bitmap: invalid resolution!");
-                    const size_t nt = (size_t) (k == 2 ? 1 : 3) * tw[k] * th[k];
-                    const std::string key = "tex." + std::to_string(i) + "." + std::to_string(k);
-                    TexDev &t = td[3 * (size_t) i + k];
-                    const bool had = sc->named.count(key) != 0, had_d = sc->named.count(key + ".d") != 0;
-                    if (sync_named(sc, key, src[k], nt * sizeof(float), same_bitmaps && had, t.data, info)) return 1;
-                    if (sync_named(sc, key + ".d", dsrc[k], nt * sizeof(float), same_bitmaps && had_d, t.d_data, info)) return 1;
-                    t.w = tw[k]; t.h = th[k];
-                    t.g_off = sc->tex_total; sc->tex_total += (long long) nt;
-                    for (int q = 0; q < 4; ++q) { t.xf[q] = b.tex_xf[k][q]; t.d_xf[q] = b.d_tex_xf[k][q]; }
-                }
+        if (!any_tex) return 0;
+        std::vector<TexDev> td((size_t) 3 * s->n_bsdfs, TexDev{nullptr, nullptr, 0, 0, -1, {0.f, 1.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}});
+        for (int i = 0; i < s->n_bsdfs; ++i) {
+            const psdr_bsdf_rec &b = s->bsdfs[i];
+            const float *src[3] = {b.tex_data, b.spec_tex_data, b.rough_tex_data}, *dsrc[3] = {b.d_tex_data, b.d_spec_tex_data, b.d_rough_tex_data};
+            const int tw[3] = {b.tex_width, b.spec_tex_width, b.rough_tex_width}, th[3] = {b.tex_height, b.spec_tex_height, b.rough_tex_height};
+            for (int k = 0; k < 3; ++k) {
+                if (!src[k]) continue;
+                if (k > 0 && b.type != 1 && b.type != 2 && !(b.type == 3 && k == 2)) return fail("this BSDF type has no second / third bitmap parameter");
+                if (tw[k] < 2 || th[k] < 2) return fail("Bitmap: invalid resolution!");
+                const size_t nt = (size_t) (k == 2 ? 1 : 3) * tw[k] * th[k];
+                const std::string key = "tex." + std::to_string(i) + "." + std::to_string(k);
+                TexDev &t = td[3 * (size_t) i + k];
+                const bool had = sc->named.count(key) != 0, had_d = sc->named.count(key + ".d") != 0;
+                if (sync_named(sc, key, src[k], nt * sizeof(float), same_bitmaps && had, t.data, info)) return 1;
+                if (sync_named(sc, key + ".d", dsrc[k], nt * sizeof(float), same_bitmaps && had_d, t.d_data, info)) return 1;
+                t.w = tw[k]; t.h = th[k];
+                t.g_off = sc->tex_total; sc->tex_total += (long long) nt;
+                for (int q = 0; q < 4; ++q) { t.xf[q] = b.tex_xf[k][q]; t.d_xf[q] = b.d_tex_xf[k][q]; }
             }
-            if (sync_named(sc, "tex.table", td.data(), td.size() * sizeof(TexDev), false, T.tex, info)) return 1;
-            sc->tex_layout.resize(td.size());
-            for (size_t i = 0; i < td.size(); ++i) sc->tex_layout[i] = td[i].g_off;
         }
+        if (sync_named(sc, "tex.table", td.data(), td.size() * sizeof(TexDev), false, T.tex, info)) return 1;
+        sc->tex_layout.resize(td.size());
+        for (size_t i = 0; i < td.size(); ++i) sc->tex_layout[i] = td[i].g_off;
+        return 0;
     }
-    T.mat = nullptr;
-    {
+
+    int materials() {
+        T.mat = nullptr;
         bool any = false;
         for (int i = 0; i < s->n_bsdfs; ++i) any |= s->bsdfs[i].type != 0;
-        if (any) {
-            std::vector<MatDev> md((size_t) s->n_bsdfs);
-            for (int i = 0; i < s->n_bsdfs; ++i) {
-                const psdr_bsdf_rec &b = s->bsdfs[i];
-                MatDev &m = md[(size_t) i];
-                for (int k = 0; k < 3; ++k) { m.specular[k] = b.specular[k]; m.d_specular[k] = b.d_specular[k]; }
-                m.roughness = b.roughness; m.d_roughness = b.d_roughness;
-                m.alpha_u = b.alpha_u; m.alpha_v = b.alpha_v; m.d_alpha_u = b.d_alpha_u; m.d_alpha_v = b.d_alpha_v;
-                for (int k = 0; k < 3; ++k) { m.eta[k] = b.eta[k]; m.d_eta[k] = b.d_eta[k]; m.k[k] = b.k[k]; m.d_k[k] = b.d_k[k]; }
-            }
-            if (sync_named(sc, "mat.table", md.data(), md.size() * sizeof(MatDev), false, T.mat, info)) return 1;
+        if (!any) return 0;
+        std::vector<MatDev> md((size_t) s->n_bsdfs);
+        for (int i = 0; i < s->n_bsdfs; ++i) {
+            const psdr_bsdf_rec &b = s->bsdfs[i];
+            MatDev &m = md[(size_t) i];
+            for (int k = 0; k < 3; ++k) { m.specular[k] = b.specular[k]; m.d_specular[k] = b.d_specular[k]; }
+            m.roughness = b.roughness; m.d_roughness = b.d_roughness;
+            m.alpha_u = b.alpha_u; m.alpha_v = b.alpha_v; m.d_alpha_u = b.d_alpha_u; m.d_alpha_v = b.d_alpha_v;
+            for (int k = 0; k < 3; ++k) { m.eta[k] = b.eta[k]; m.d_eta[k] = b.d_eta[k]; m.k[k] = b.k[k]; m.d_k[k] = b.d_k[k]; }
         }
+        return sync_named(sc, "mat.table", md.data(), md.size() * sizeof(MatDev), false, T.mat, info);
     }
-    T.pv = nullptr; T.tri_fi = nullptr;
-    {   // MicrofacetPerVertex: parameter arrays per BSDF + the mesh-local vertex ids of every triangle slot
+
+    // MicrofacetPerVertex: parameter arrays per BSDF + the mesh-local vertex ids of every triangle slot
+    int per_vertex() {
+        const int n = tr.n_triangles;
+        T.pv = nullptr; T.tri_fi = nullptr;
         bool any_pv = false;
         for (int i = 0; i < s->n_bsdfs; ++i) any_pv |= s->bsdfs[i].type == 4;
-        if (any_pv) {
-            if (!tr.face_indices) return fail("MicrofacetPerVertex needs psdr_triangles.face_indices");
-            std::vector<PvDev> pd((size_t) s->n_bsdfs, PvDev{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, {-1, -1, -1}});
-            if (sc->tex_layout.size() < (size_t) 3 * s->n_bsdfs) sc->tex_layout.resize((size_t) 3 * s->n_bsdfs, -1);
-            for (int i = 0; i < s->n_bsdfs; ++i) {
-                const psdr_bsdf_rec &b = s->bsdfs[i];
-                if (b.type != 4) continue;
-                if (b.pv_count <= 0 || !b.pv_specular || !b.pv_diffuse || !b.pv_roughness) return fail("MicrofacetPerVertex: missing per-vertex data");
-                const size_t nv = (size_t) b.pv_count;
-                const std::string key = "pv." + std::to_string(i) + ".";
-                PvDev &p = pd[(size_t) i];
-                const float *srcs[6] = {b.pv_specular, b.d_pv_specular, b.pv_diffuse, b.d_pv_diffuse, b.pv_roughness, b.d_pv_roughness};
-                const float **dsts[6] = {&p.spec, &p.d_spec, &p.diff, &p.d_diff, &p.rough, &p.d_rough};
-                const size_t lens[6] = {3 * nv, 3 * nv, 3 * nv, 3 * nv, nv, nv};
-                for (int q = 0; q < 6; ++q) {
-                    const std::string kq = key + std::to_string(q);
-                    const bool had = sc->named.count(kq) != 0;
-                    if (sync_named(sc, kq, srcs[q], lens[q] * sizeof(float), same_bitmaps && had, *dsts[q], info)) return 1;
-                }
-                p.n = b.pv_count;
-                // adjoint blocks in psdr_grads.g_tex, numbered like Microfacet's maps: 0 diffuse, 1 specular, 2 roughness
-                const size_t sizes[3] = {3 * nv, 3 * nv, nv};
-                for (int k = 0; k < 3; ++k) { p.g_off[k] = sc->tex_total; sc->tex_layout[3 * (size_t) i + k] = sc->tex_total; sc->tex_total += (long long) sizes[k]; }
+        if (!any_pv) return 0;
+        if (!tr.face_indices) return fail("MicrofacetPerVertex needs psdr_triangles.face_indices");
+        std::vector<PvDev> pd((size_t) s->n_bsdfs, PvDev{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, {-1, -1, -1}});
+        if (sc->tex_layout.size() < (size_t) 3 * s->n_bsdfs) sc->tex_layout.resize((size_t) 3 * s->n_bsdfs, -1);
+        for (int i = 0; i < s->n_bsdfs; ++i) {
+            const psdr_bsdf_rec &b = s->bsdfs[i];
+            if (b.type != 4) continue;
+            if (b.pv_count <= 0 || !b.pv_specular || !b.pv_diffuse || !b.pv_roughness) return fail("MicrofacetPerVertex: missing per-vertex data");
+            const size_t nv = (size_t) b.pv_count;
+            const std::string key = "pv." + std::to_string(i) + ".";
+            PvDev &p = pd[(size_t) i];
+            const float *srcs[6] = {b.pv_specular, b.d_pv_specular, b.pv_diffuse, b.d_pv_diffuse, b.pv_roughness, b.d_pv_roughness};
+            const float **dsts[6] = {&p.spec, &p.d_spec, &p.diff, &p.d_diff, &p.rough, &p.d_rough};
+            const size_t lens[6] = {3 * nv, 3 * nv, 3 * nv, 3 * nv, nv, nv};
+            for (int q = 0; q < 6; ++q) {
+                const std::string kq = key + std::to_string(q);
+                const bool had = sc->named.count(kq) != 0;
+                if (sync_named(sc, kq, srcs[q], lens[q] * sizeof(float), same_bitmaps && had, *dsts[q], info)) return 1;
             }
-            // every mesh that uses a per-vertex BSDF must index inside its arrays
-            for (int i = 0; i < n; ++i) {
-                const int bid = s->meshes[tr.mesh_id[i]].bsdf_id;
-                if (bid >= 0 && s->bsdfs[bid].type == 4)
-                    for (int k = 0; k < 3; ++k)
-                        if (tr.face_indices[3 * (size_t) i + k] < 0 || tr.face_indices[3 * (size_t) i + k] >= s->bsdfs[bid].pv_count) return fail("MicrofacetPerVertex: fewer values than mesh vertices");
-            }
-            const bool had_fi = sc->named.count("tri_fi") != 0;
-            if (geo || !had_fi) {
-                std::vector<int> fi((size_t) 3 * n);
-                for (int slot = 0; slot < n; ++slot)
-                    for (int k = 0; k < 3; ++k) fi[3 * (size_t) slot + k] = tr.face_indices[3 * (size_t) order[(size_t) slot] + k];
-                if (sync_named(sc, "tri_fi", fi.data(), fi.size() * sizeof(int), false, T.tri_fi, info)) return 1;
-            } else T.tri_fi = sc->buf("tri_fi").as<int>();
-            if (sync_named(sc, "pv.table", pd.data(), pd.size() * sizeof(PvDev), false, T.pv, info)) return 1;
+            p.n = b.pv_count;
+            // adjoint blocks in psdr_grads.g_tex, numbered like Microfacet's maps: 0 diffuse, 1 specular, 2 roughness
+            const size_t sizes[3] = {3 * nv, 3 * nv, nv};
+            for (int k = 0; k < 3; ++k) { p.g_off[k] = sc->tex_total; sc->tex_layout[3 * (size_t) i + k] = sc->tex_total; sc->tex_total += (long long) sizes[k]; }
         }
+        // every mesh that uses a per-vertex BSDF must index inside its arrays
+        for (int i = 0; i < n; ++i) {
+            const int bid = s->meshes[tr.mesh_id[i]].bsdf_id;
+            if (bid >= 0 && s->bsdfs[bid].type == 4)
+                for (int k = 0; k < 3; ++k)
+                    if (tr.face_indices[3 * (size_t) i + k] < 0 || tr.face_indices[3 * (size_t) i + k] >= s->bsdfs[bid].pv_count) return fail("MicrofacetPerVertex: fewer values than mesh vertices");
+        }
+        const bool had_fi = sc->named.count("tri_fi") != 0;
+        if (geo || !had_fi) {
+            std::vector<int> fi((size_t) 3 * n);
+            for (int slot = 0; slot < n; ++slot)
+                for (int k = 0; k < 3; ++k) fi[3 * (size_t) slot + k] = tr.face_indices[3 * (size_t) sc->order[(size_t) slot] + k];
+            if (sync_named(sc, "tri_fi", fi.data(), fi.size() * sizeof(int), false, T.tri_fi, info)) return 1;
+        } else T.tri_fi = sc->buf("tri_fi").as<int>();
+        return sync_named(sc, "pv.table", pd.data(), pd.size() * sizeof(PvDev), false, T.pv, info);
     }
-    if (build) {   // hot triangles of the reverse-mode accumulators: emitter meshes first, then by area, at most kHotMax (an update keeps the choice of the build: it only decides which rows accumulate in LDS)
+
+    // hot triangles of the reverse-mode accumulators: emitter meshes first, then by area, at most kHotMax (an update keeps the choice of the build: it only decides which rows accumulate in LDS)
+    int hot_triangles() {
+        const int n = tr.n_triangles;
         constexpr int kHotMax = 720;                                   // 720 x 22 floats = 62 KB of LDS
         std::vector<int> ord((size_t) n);
         std::vector<float> key((size_t) n);
@@ -1355,77 +1328,61 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
         std::partial_sort(ord.begin(), ord.begin() + sc->n_hot, ord.end(), before);
         std::vector<int> hmap((size_t) std::max(1, n), -1), hinv((size_t) std::max(1, sc->n_hot), 0);
         for (int h = 0; h < sc->n_hot; ++h) { hmap[(size_t) ord[(size_t) h]] = h; hinv[(size_t) h] = ord[(size_t) h]; }
-        if (sc->hot_map.upload(hmap.data(), hmap.size() * sizeof(int)) || sc->hot_inv.upload(hinv.data(), hinv.size() * sizeof(int))) return 1;
+        return sc->hot_map.upload(hmap.data(), hmap.size() * sizeof(int)) || sc->hot_inv.upload(hinv.data(), hinv.size() * sizeof(int)) ? 1 : 0;
     }
-    info.ms_fill = ms_since(t_fill);
 
-    // ---- send the sections that were written (adjacent ones as one copy)
-    const auto t_up = std::chrono::steady_clock::now();
-    if (blob_moved) { dirty.clear(); dirty.push_back({0, w}); }
-    std::sort(dirty.begin(), dirty.end(), [](const WordRange &a, const WordRange &b) { return a.b < b.b; });
-    auto send = [&](size_t b, size_t e) -> int {
-        if (e <= b) return 0;
-        HIPCHK(hipMemcpyAsync((char *) sc->blob.p + 16 * b, (const char *) H + 16 * b, 16 * (e - b), hipMemcpyHostToDevice, nullptr));
-        info.bytes_uploaded += (int64_t) (16 * (e - b));
-        return 0;
-    };
-    for (size_t i = 0; i < dirty.size();) {
-        size_t b = dirty[i].b, e = dirty[i].e, j = i + 1;
-        while (j < dirty.size() && dirty[j].b <= e) { e = std::max(e, dirty[j].e); ++j; }
-        if (blob_moved && !build && uses_bvh) {
-            // (after a move of the allocation the nodes a refit wrote were carried over on the device: the host copy of a refitted tree is stale)
-            const size_t nb = (size_t) T.nodes_off, ne = nb + (size_t) (kNodeFloats / 4) * (size_t) T.n_nodes;
-            if (send(b, std::min(e, nb)) || send(std::max(b, ne), e)) return 1;
-        } else if (send(b, e)) return 1;
-        i = j;
-    }
-    info.ms_upload = ms_since(t_up);
-
-    // ---- the tree follows the triangles
-    info.sah_cost_built = sc->cost_built;
-    info.sah_cost = sc->cost_built;
-    if (!build && geo && uses_bvh) {
-        const auto t_refit = std::chrono::steady_clock::now();
-        double cost = 0.0;
-        if (tree_refit(sc, &cost)) return 1;
-        info.tree = 1;
-        info.sah_cost = cost;
-        info.ms_tree += ms_since(t_refit);
-        // the topology no longer fits the geometry: build again (everything that depends on the triangle order is rewritten)
-        if (!(cost <= kRebuildFactor * sc->cost_built)) {
-            if (!rows_valid) return PSDR_HIP_NEED_ROWS;         // (the rows on the device are this state's, the tables are complete: the caller comes back with its rows and the tree is built then)
-            return scene_sync(sc, s, 0, false, true, info_out, ereq);
+    // send the sections that were written (adjacent ones as one copy)
+    int send() {
+        if (blob_moved) { dirty.clear(); dirty.push_back({0, L.words}); }
+        std::sort(dirty.begin(), dirty.end(), [](const WordRange &a, const WordRange &b) { return a.b < b.b; });
+        auto send = [&](size_t b, size_t e) -> int {
+            if (e <= b) return 0;
+            HIPCHK(hipMemcpyAsync((char *) sc->blob.p + 16 * b, (const char *) H + 16 * b, 16 * (e - b), hipMemcpyHostToDevice, nullptr));
+            info.bytes_uploaded += (int64_t) (16 * (e - b));
+            return 0;
+        };
+        for (size_t i = 0; i < dirty.size();) {
+            size_t b = dirty[i].b, e = dirty[i].e, j = i + 1;
+            while (j < dirty.size() && dirty[j].b <= e) { e = std::max(e, dirty[j].e); ++j; }
+            if (blob_moved && !build && uses_bvh) {
+                // (after a move of the allocation the nodes a refit wrote were carried over on the device: the host copy of a refitted tree is stale)
+                const size_t nb = (size_t) T.nodes_off, ne = nb + (size_t) (kNodeFloats / 4) * (size_t) T.n_nodes;
+                if (send(b, std::min(e, nb)) || send(std::max(b, ne), e)) return 1;
+            } else if (send(b, e)) return 1;
+            i = j;
         }
+        return 0;
     }
 
-    // ---- scene class, launch geometry
-    const size_t stack_bytes = (size_t) T.stack_depth * kBlock * sizeof(int);
-    const size_t blob_bytes = (size_t) T.blob_words * 16;
-    // keeps >= 4 workgroups per CU (160 KiB LDS); the environment-map and texture code lives in the LDS=false kernels only (shade.h)
-    bool no_lds = false;
-#ifdef PSDR_DEV_KNOBS
-    no_lds = std::getenv("PSDR_NO_LDS") != nullptr;      // measurement knob: run small scenes through the global-memory classes
-#endif
-    sc->lds = !no_lds && !uses_bvh && blob_bytes + stack_bytes <= 40 * 1024 && T.env_emitter < 0 && T.tex == nullptr && T.mat == nullptr && T.pv == nullptr;      // (LDS class = brute-force scenes)
-    sc->lean = !sc->lds && T.tex == nullptr && T.mat == nullptr && T.pv == nullptr;
-    // class 3: the same staging for small scenes WITH materials / bitmap parameters (the material and texture tables stay in global
-    // memory; the triangle, BSDF, emitter and edge tables are what every path vertex reads)
-    sc->lds_mat = !no_lds && !sc->lds && !uses_bvh && blob_bytes + stack_bytes <= 40 * 1024 && T.env_emitter < 0 && T.pv == nullptr;
-    sc->smem_bytes = ((sc->lds || sc->lds_mat) ? blob_bytes : 0) + stack_bytes;
-    if (sc->smem_bytes > 64 * 1024) return fail("BVH too deep for the LDS traversal stack");
-    if (fresh) {
-        if (sc->counters.upload(nullptr, sizeof(Counters))) return 1;
-        if (sc->queues.upload(nullptr, sizeof(unsigned long long) * kQueueRing)) return 1;
-    }
-    if (build) {
+    // scene class, launch geometry
+    int launch_geometry() {
+        const size_t stack_bytes = (size_t) T.stack_depth * kBlock * sizeof(int);
+        const size_t blob_bytes = (size_t) T.blob_words * 16;
+        // keeps >= 4 workgroups per CU (160 KiB LDS); the environment-map and texture code lives in the LDS=false kernels only (shade.h)
+        bool no_lds = false;
+    #ifdef PSDR_DEV_KNOBS
+        no_lds = std::getenv("PSDR_NO_LDS") != nullptr;      // measurement knob: run small scenes through the global-memory classes
+    #endif
+        sc->lds = !no_lds && !uses_bvh && blob_bytes + stack_bytes <= 40 * 1024 && T.env_emitter < 0 && T.tex == nullptr && T.mat == nullptr && T.pv == nullptr;      // (LDS class = brute-force scenes)
+        sc->lean = !sc->lds && T.tex == nullptr && T.mat == nullptr && T.pv == nullptr;
+        // class 3: the same staging for small scenes WITH materials / bitmap parameters (the material and texture tables stay in global
+        // memory; the triangle, BSDF, emitter and edge tables are what every path vertex reads)
+        sc->lds_mat = !no_lds && !sc->lds && !uses_bvh && blob_bytes + stack_bytes <= 40 * 1024 && T.env_emitter < 0 && T.pv == nullptr;
+        sc->smem_bytes = ((sc->lds || sc->lds_mat) ? blob_bytes : 0) + stack_bytes;
+        if (sc->smem_bytes > 64 * 1024) return fail("BVH too deep for the LDS traversal stack");
+        if (fresh) {
+            if (sc->counters.upload(nullptr, sizeof(Counters))) return 1;
+            if (sc->queues.upload(nullptr, sizeof(unsigned long long) * kQueueRing)) return 1;
+        }
+        if (!build) return 0;
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount; }
         // workgroups per launch: a multiple of what fits on the device (persistent workgroups pull work until the launch's queue is empty; the ones that start late find it empty)
         // (measured, round 4: brute-force scenes 4 per CU - what is resident at most - C3 forward -0.5 %, its backward pass 8.28 -> 8.06 ms; BVH scenes 8: config 5 218.7 ms, with 4 220.1)
         int per_cu = uses_bvh ? 8 : 4;
-#ifdef PSDR_DEV_KNOBS
+    #ifdef PSDR_DEV_KNOBS
         if (const char *e = std::getenv("PSDR_GRID_PER_CU")) per_cu = std::max(1, std::atoi(e));
-#endif
+    #endif
         sc->grid = cus * per_cu;
         T.gstack = nullptr; T.gstack_stride = 0;
         if (uses_bvh && sc->tree_max_stack > T.stack_lds) {
@@ -1436,14 +1393,79 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
             if (sc->gstack.ensure(sizeof(int) * sc->gstack_slice * (size_t) kTermSlices)) return 1;
             T.gstack = (int *) sc->gstack.p; T.gstack_stride = (int) stride;
         }
+        return 0;
     }
+};
+
+// Everything between a snapshot and a renderable device scene.  fresh: the handle is new.  same: PSDR_SAME_* bits the caller vouches for
+// (relative to the snapshot of the previous create / update of this handle); force_build: build the tree even if the triangle count fits.
+static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned same, bool fresh, bool force_build, psdr_update_info *info_out, const EdgeRequest *ereq = nullptr) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (int rc = sync_validate(s)) return rc;
+    SceneSync c{sc, s, ereq, fresh};
+    if (int rc = c.plan_request(same, force_build)) return rc;
+    if (!fresh) {
+        // the previous calls on this scene read what is about to be overwritten: wait for the last of them (configure() is a synchronisation point in the reference as well)
+        std::lock_guard<std::mutex> lk(sc->mu);
+        if (sc->ev && sc->have_last) HIPCHK(hipEventSynchronize(sc->ev));
+    }
+    const auto t_tree = std::chrono::steady_clock::now();
+    if (c.build) {
+        if (tree_build(sc, s->tris, c.new_nodes)) return 1;
+        c.info.tree = 2;
+    }
+    c.info.ms_tree = ms_since(t_tree);
+    const auto t_fill = std::chrono::steady_clock::now();
+    if (int rc = c.plan_layout()) return rc;
+    c.commit_tables();
+    if (int rc = c.blob()) return rc;
+    if (int rc = c.geometry()) return rc;
+    c.tri_rows();
+    c.filter();
+    c.small_tables();
+    if (c.sec_edges() || c.sensors() || c.environment() || c.bitmaps() || c.materials() || c.per_vertex()) return 1;
+    if (c.build && c.hot_triangles()) return 1;
+    c.info.ms_fill = ms_since(t_fill);
+    const auto t_up = std::chrono::steady_clock::now();
+    if (c.send()) return 1;
+    c.info.ms_upload = ms_since(t_up);
+
+    // ---- the tree follows the triangles
+    c.info.sah_cost_built = sc->cost_built;
+    c.info.sah_cost = sc->cost_built;
+    if (!c.build && c.geo && c.uses_bvh) {
+        const auto t_refit = std::chrono::steady_clock::now();
+        double cost = 0.0;
+        if (tree_refit(sc, &cost)) return 1;
+        c.info.tree = 1;
+        c.info.sah_cost = cost;
+        c.info.ms_tree += ms_since(t_refit);
+        // the topology no longer fits the geometry: build again (everything that depends on the triangle order is rewritten)
+        if (!(cost <= kRebuildFactor * sc->cost_built)) {
+            if (!c.rows_valid) return PSDR_HIP_NEED_ROWS;         // (the rows on the device are this state's, the tables are complete: the caller comes back with its rows and the tree is built then)
+            return scene_sync(sc, s, 0, false, true, info_out, ereq);
+        }
+    }
+    if (c.launch_geometry()) return 1;
     HIPCHK(hipStreamSynchronize(nullptr));
-    info.ms_total = ms_since(t_start);
-    sc->edge_path = edge_path; sc->edge_bytes = edge_bytes;
-    sc->pe_cap = cap_layout ? pe_cap : 0;
-    sc->last_info = info;
-    if (info_out) *info_out = info;
+    c.info.ms_total = ms_since(t_start);
+    sc->edge_path = c.edge_path; sc->edge_bytes = c.edge_bytes;
+    sc->pe_cap = c.cap_layout ? c.pe_cap : 0;
+    sc->last_info = c.info;
+    if (info_out) *info_out = c.info;
     return 0;
+}
+
+// psdr_hip_scene_update / _update_edges.  scene_sync rewrites the handle in place (tables, offsets, named buffers, sensors) while it uploads: a failure midway - a validation
+// message, out of memory, an LDS budget - leaves old and new sections mixed.  Such a handle is POISONED: the render entry points refuse it, and the next update ignores what
+// the caller vouches for (its `same` bits are relative to a snapshot the device never fully received) and builds everything again.
+static int update_entry(psdr_hip_scene *scene, const psdr_scene_snapshot *s, uint32_t same, psdr_update_info *info, const EdgeRequest *ereq) {
+    const bool was_poisoned = scene->poisoned;
+    const int rc = scene_sync(scene, s, was_poisoned ? 0u : same, false, was_poisoned, info, ereq);
+    if (rc == PSDR_HIP_NEED_ROWS) return rc;                  // (nothing was changed, or only rows that are this state's: see psdr_scene_snapshot.rows_valid)
+    scene->poisoned = rc != 0;
+    if (rc) scene->tree_tris = -1;
+    return rc;
 }
 
 extern "C" {
@@ -1460,15 +1482,7 @@ int psdr_hip_scene_create(const psdr_scene_snapshot *s, psdr_hip_scene **out) {
 int psdr_hip_scene_update(psdr_hip_scene *scene, const psdr_scene_snapshot *s, uint32_t same, psdr_update_info *info) {
     if (!scene || !s) return fail("psdr_hip_scene_update: null argument");
     if (s->abi_version != PSDR_HIP_ABI_VERSION) return fail("psdr_hip_scene_update: ABI version mismatch");
-    // scene_sync rewrites the handle in place (tables, offsets, named buffers, sensors) while it validates and uploads: a failure midway - a validation message, out of
-    // memory, an LDS budget - leaves old and new sections mixed.  Such a handle is POISONED: the render entry points refuse it, and the next update ignores what the
-    // caller vouches for (its `same` bits are relative to a snapshot the device never fully received) and builds everything again.
-    const bool was_poisoned = scene->poisoned;
-    const int rc = scene_sync(scene, s, was_poisoned ? 0u : same, false, was_poisoned, info);
-    if (rc == PSDR_HIP_NEED_ROWS) return rc;                  // (nothing was changed, or only rows that are this state's: see psdr_scene_snapshot.rows_valid)
-    scene->poisoned = rc != 0;
-    if (rc) scene->tree_tris = -1;
-    return rc;
+    return update_entry(scene, s, same, info, nullptr);
 }
 
 int psdr_hip_scene_update_edges(psdr_hip_scene *scene, const psdr_scene_snapshot *s, uint32_t same, const psdr_edge_topology *topo, const int32_t *sensor_mode, psdr_update_info *info) {
@@ -1477,12 +1491,7 @@ int psdr_hip_scene_update_edges(psdr_hip_scene *scene, const psdr_scene_snapshot
     for (int i = 0; i < s->n_sensors; ++i)
         if (sensor_mode[i] < PSDR_EDGES_HOST || sensor_mode[i] > PSDR_EDGES_KEEP) return fail("psdr_hip_scene_update_edges: unknown sensor mode");
     const EdgeRequest er{topo, sensor_mode};
-    const bool was_poisoned = scene->poisoned;               // (as psdr_hip_scene_update)
-    const int rc = scene_sync(scene, s, was_poisoned ? 0u : same, false, was_poisoned, info, &er);
-    if (rc == PSDR_HIP_NEED_ROWS) return rc;
-    scene->poisoned = rc != 0;
-    if (rc) scene->tree_tris = -1;
-    return rc;
+    return update_entry(scene, s, same, info, &er);
 }
 
 int psdr_hip_scene_primary_edges(const psdr_hip_scene *sc, int32_t sensor_id, int32_t *count, int32_t *ids, int32_t cap, float *edge_sum) {
@@ -1542,13 +1551,10 @@ int psdr_hip_scene_check_edges(const psdr_hip_scene *sc, const psdr_scene_snapsh
         if (n == 0) continue;
         bad += std::memcmp(&d.edge_sum, &r.edge_sum, 4) != 0 ? 1 : 0;
         if (fetch(4 * (size_t) d.pe_off, 12 * (size_t) n, rows) || fetch(4 * (size_t) d.pecdf_off, 2 * (size_t) n, cdf)) return 1;
-        const float z2[2] = {0.f, 0.f};
         for (size_t i = 0; i < (size_t) n; ++i) {
-            const float *q = &rows[12 * i];
-            const float *dp0 = r.d_edge_p0 ? r.d_edge_p0 + 2 * i : z2, *dp1 = r.d_edge_p1 ? r.d_edge_p1 + 2 * i : z2;
-            const float h[12] = {r.edge_p0[2 * i], r.edge_p0[2 * i + 1], r.edge_p1[2 * i], r.edge_p1[2 * i + 1], dp0[0], dp0[1], dp1[0], dp1[1],
-                                 r.edge_normal[2 * i], r.edge_normal[2 * i + 1], r.edge_length[i], 0.f};
-            diff(q, h, 12);
+            float h[4 * kPeWords];
+            pack_pe_row(r, i, h);
+            diff(&rows[12 * i], h, 12);
         }
         diff(cdf.data(), r.edge_pmf, (size_t) n); diff(cdf.data() + n, r.edge_cmf, (size_t) n);
         if (guide_diff(r.edge_cmf, n, r.edge_sum, d.pe_guide, d.pe_guide_n)) return 1;
@@ -1602,33 +1608,25 @@ int psdr_hip_scene_check_rows(const psdr_hip_scene *sc, const psdr_scene_snapsho
     if (fetch(T.trav_off, 3 * (size_t) n, trav) || fetch(T.shade_off, 6 * (size_t) n, shade)) return 1;
     if (T.has_tangent && fetch(T.tan_off, 6 * (size_t) n, tan)) return 1;
     long long bad = 0;
-    auto cmp = [&](const float *dev, float x, float y, float z, float w) { const float h[4] = {x, y, z, w}; for (int k = 0; k < 4; ++k) bad += std::memcmp(dev + k, h + k, 4) != 0 ? 1 : 0; };
+    auto diff = [&](const float *dev, const float *host, size_t n) { for (size_t i = 0; i < n; ++i) bad += std::memcmp(dev + i, host + i, 4) != 0 ? 1 : 0; };
     for (int slot = 0; slot < n; ++slot) {
         const size_t o = (size_t) sc->order[(size_t) slot];
-        const float *p0 = tr.p0 + 3 * o, *e1 = tr.e1 + 3 * o, *e2 = tr.e2 + 3 * o;
-        const float *t = &trav[12 * (size_t) slot];
-        cmp(t, p0[0], p0[1], p0[2], e1[0]); cmp(t + 4, e1[1], e1[2], e2[0], e2[1]); cmp(t + 8, e2[2], ibits((int32_t) o), 0.f, 0.f);
-        const float *n0 = tr.n0 + 3 * o, *n1 = tr.n1 + 3 * o, *n2 = tr.n2 + 3 * o, *fn = tr.face_normal + 3 * o;
-        const float *w = &shade[24 * (size_t) slot];
-        cmp(w, n0[0], n0[1], n0[2], tr.face_area[o]); cmp(w + 4, n1[0], n1[1], n1[2], ibits(tr.mesh_id[o]));
-        cmp(w + 8, n2[0], n2[1], n2[2], ibits(tr.use_face_normal && tr.use_face_normal[o] ? 1 : 0)); cmp(w + 12, fn[0], fn[1], fn[2], ibits((int32_t) o));
+        float h_trav[4 * kTravWords], h_shade[4 * kShadeWords], h_tan[4 * kTanWords];
+        pack_tri_rows(tr, o, h_trav, h_shade);
+        diff(&trav[12 * (size_t) slot], h_trav, 12);
+        diff(&shade[24 * (size_t) slot], h_shade, 16);          // (words 4 and 5 - the uv of the three corners - do not depend on the vertices: the device never writes them)
         if (T.has_tangent && tr.d_p0) {
-            const float *a = tr.d_p0 + 3 * o, *b = tr.d_e1 + 3 * o, *c = tr.d_e2 + 3 * o, *d0 = tr.d_n0 + 3 * o, *d1 = tr.d_n1 + 3 * o, *d2 = tr.d_n2 + 3 * o, *df = tr.d_face_normal + 3 * o;
-            const float *q = &tan[24 * (size_t) slot];
-            cmp(q, a[0], a[1], a[2], b[0]); cmp(q + 4, b[1], b[2], c[0], c[1]); cmp(q + 8, c[2], d0[0], d0[1], d0[2]); cmp(q + 12, d1[0], d1[1], d1[2], d2[0]);
-            cmp(q + 16, d2[1], d2[2], df[0], df[1]); cmp(q + 20, df[2], tr.d_face_area[o], 0.f, 0.f);
+            pack_tan_row(tr, o, h_tan);
+            diff(&tan[24 * (size_t) slot], h_tan, 24);
         }
     }
     const psdr_sec_edges &se = s->sec_edges;
     if (se.n_edges > 0 && se.n_edges == sc->E.n) {
         if (fetch(sc->E.off, 6 * (size_t) se.n_edges, sec)) return 1;
-        const float z3[3] = {0.f, 0.f, 0.f};
         for (size_t i = 0; i < (size_t) se.n_edges; ++i) {
-            const float *p0 = se.p0 + 3 * i, *e1 = se.e1 + 3 * i, *n0 = se.n0 + 3 * i, *n1 = se.n1 + 3 * i, *p2 = se.p2 + 3 * i;
-            const float *dp0 = se.d_p0 ? se.d_p0 + 3 * i : z3, *de1 = se.d_e1 ? se.d_e1 + 3 * i : z3;
-            const float *q = &sec[24 * i];
-            cmp(q, p0[0], p0[1], p0[2], e1[0]); cmp(q + 4, e1[1], e1[2], n0[0], n0[1]); cmp(q + 8, n0[2], n1[0], n1[1], n1[2]);
-            cmp(q + 12, p2[0], p2[1], p2[2], ibits(se.is_boundary[i] ? 1 : 0)); cmp(q + 16, dp0[0], dp0[1], dp0[2], de1[0]); cmp(q + 20, de1[1], de1[2], 0.f, 0.f);
+            float h[4 * kSecWords];
+            pack_sec_row(se, i, h);
+            diff(&sec[24 * i], h, 24);
         }
     }
     *mismatches = bad;

@@ -1,5 +1,6 @@
 // scene_obj.h — the device-resident scene behind a psdr_hip_scene handle, shared by the two host translation units of
-// libpsdr_hip.so: scene_build.hip (psdr_hip_scene_create / _update: tree build and refit, blob layout, uploads - what the
+// libpsdr_hip.so: scene_build.hip (psdr_hip_scene_create / _update: tree build and refit, uploads, with the blob's layout in
+// blob_layout.h and the host's row formats in blob_rows.h, both host-only - what the
 // reference does in Scene_OptiX::configure + the jit uploads of Scene::configure, src/scene/scene_optix.cpp:265-332,
 // src/scene/scene.cpp:311-599) and api.hip (the render entry points; their kernels: render_kernels.h).
 #pragma once
