@@ -279,6 +279,29 @@ def ortho_cbox_scene(width=48, height=48, spp=4, sppe=0, sppse=0, param="box_x")
     return spec
 
 
+def with_extra_sensors(spec, kind="perspective"):
+    """Appends two cameras to a one-camera spec (in place; -> spec), for the tests that render through sensors other than Sensor[0].
+    kind 'perspective': the Cornell-box-sized scenes - camera 1 from the upper left, tilted down, with a narrower lens; camera 2 from the
+    lower right with a wider one.  kind 'ortho': ortho_cbox_scene's unit scale - camera 1 is camera 2 above carried into that scene's
+    frame (a PerspectiveCamera beside the orthographic Sensor[0]), camera 2 a second OrthographicCamera that looks at the box from the
+    upper left (turned 20 degrees about y, tilted 10 degrees down), five units away like Sensor[0]."""
+    if kind == "perspective":
+        spec.cameras.append(CameraSpec(45.0, 0.000001, 10000000.0, to_world_raw=translate(120.0, 420.0, -650.0) @ _rot_x(np.radians(20.0))))
+        spec.cameras.append(CameraSpec(75.0, 0.000001, 10000000.0, to_world_raw=translate(420.0, 150.0, -500.0)))
+    elif kind == "ortho":
+        p = np.float32([420.0 - 278.0, 150.0 - 273.0, -500.0 - 280.0]) / np.float32(300.0)
+        spec.cameras.append(CameraSpec(75.0, 0.000001, 10000000.0, to_world_raw=translate(p[0], p[1], p[2])))
+        turn = np.eye(4, dtype=np.float32)
+        c, s = np.cos(np.radians(20.0)), np.sin(np.radians(20.0))
+        turn[0, 0], turn[0, 2], turn[2, 0], turn[2, 2] = c, s, -s, c
+        rot = (turn @ _rot_x(np.radians(10.0))).astype(np.float32)
+        q = np.float32([0.1, 0.05, 0.0]) - np.float32(5.0) * rot[:3, 2]           # the box's middle seen along the camera axis
+        spec.cameras.append(CameraSpec(0.0, 0.1, 100.0, to_world_raw=(translate(q[0], q[1], q[2]) @ rot).astype(np.float32), orthographic=True))
+    else:
+        raise ValueError(kind)
+    return spec
+
+
 def microfacet_cbox_scene(width=48, height=48, spp=8, sppe=0, sppse=0, param="roughness", two_sided=False):
     """The README Cornell box with Microfacet boxes and floor (reference src/bsdf/microfacet.cpp).
     param: 'roughness' | 'specular' | 'diffuse' (d/dP = 1 on the boxes' BSDF) | 'box_x' | None"""

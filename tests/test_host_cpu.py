@@ -41,25 +41,33 @@ def test_cabi_exports_every_declared_symbol(psdr):
             assert int(L.psdr_hip_tea64(int(a), int(b))) == int(want)
 
 
-@pytest.mark.parametrize("name", ["cbox", "sphere"])
+@pytest.mark.parametrize("name", ["cbox", "sphere", "cbox3"])
 @pytest.mark.parametrize("param", ["light_x", "camera_x"])
 def test_host_snapshot_matches_oracle(psdr, orc, name, param):
+    active = [0]
     if name == "cbox":
         spec = scenes.cbox_scene(96, 64, 4, 4, 4, param=param)
+    elif name == "cbox3":          # three cameras, two of them active: every sensor's own edge list, none for the inactive one
+        spec = scenes.with_extra_sensors(scenes.cbox_scene(96, 64, 4, 4, 4, param=param))
+        active = [0, 2]
     else:
         spec = scenes.sphere_scene(96, 64, 1, 1, 1)
         if param == "camera_x":
             pytest.skip("one tangent configuration is enough for the sphere scene")
-    ref = orc.OracleScene(spec, [0])
-    sc = product.build_scene(spec, host_only=True)
+    ref = orc.OracleScene(spec, active)
+    sc = product.build_scene(spec, host_only=True, active=active)
     snap = sc._snapshot()
     assert np.array_equal(snap["triangles"], ref.triangle_info(False)[:, :22])
     assert np.array_equal(snap["d_triangles"], ref.triangle_info(True)[:, :22])
     assert np.array_equal(snap["sec_edges"], ref.sec_edges(False))
     assert np.array_equal(snap["d_sec_edges"][:, :6], ref.sec_edges(True)[:, :6])
+    assert sc.num_sensors == len(spec.cameras)
+    for sid in range(sc.num_sensors):
+        cam = sc.param_map["Sensor[%d]" % sid]
+        assert np.array_equal(cam._primary_edges(False), ref.primary_edges(sid, False)), sid
+        assert np.array_equal(cam._primary_edges(True), ref.primary_edges(sid, True)), sid
+        assert (cam._primary_edges(False).shape[0] > 0) == (sid in active), sid
     cam = sc.param_map["Sensor[0]"]
-    assert np.array_equal(cam._primary_edges(False), ref.primary_edges(0, False))
-    assert np.array_equal(cam._primary_edges(True), ref.primary_edges(0, True))
     for mi in range(sc.num_meshes):
         assert np.array_equal(sc.param_map["Mesh[%d]" % mi].edge_indices(), ref.mesh_edges(mi))
     assert abs(sc.param_map["Emitter[0]"].sampling_weight - ref.emitter_sampling_weight(0)) == 0.0
