@@ -22,7 +22,7 @@ HIP_LIB = os.path.join(LIBDIR, "libpsdr_hip.so")
 CORE_LIB = os.path.join(HERE, "_psdr_core" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
 
 API_SRC = os.path.join(CSRC, "hip", "api.hip")                  # the host unit: the render entry points (C ABI) and the small kernels
-UNITS_SRC = os.path.join(CSRC, "hip", "render_units.hip")       # the eight kernel units: the heavy kernel templates of render_kernels.h, one list of instantiations each (see hip_units)
+UNITS_SRC = os.path.join(CSRC, "hip", "render_units.hip")       # the ten kernel units: the heavy kernel templates of render_kernels.h, one list of instantiations each (see hip_units)
 SCENE_SRC = os.path.join(CSRC, "hip", "scene_build.hip")        # psdr_hip_scene_create / _update: tree build and refit, uploads (blob_layout.h, blob_rows.h: the blob's layout and row formats)
 PRECOND_SRC = os.path.join(CSRC, "hip", "precond.hip")         # psdr_hip_precond_*: the Laplacian vertex preconditioner, its matrix-vector product and CG solver
 HIP_SRCS = [API_SRC, UNITS_SRC, SCENE_SRC, PRECOND_SRC]
@@ -80,12 +80,12 @@ def _run(cmd):
     return r.stdout
 
 
-N_KERNEL_UNITS = 8      # render_kernels.h's PSDR_TU1..8: the heavy kernel templates of each scene class
-UNIT_CLASS_BIT = {1: 1, 2: 1, 6: 1, 8: 1, 3: 2, 4: 4, 7: 4, 5: 8}      # the PSDR_CLS_MASK bit of the scene class a unit instantiates
+N_KERNEL_UNITS = 10     # render_kernels.h's PSDR_TU1..10: the heavy kernel templates of each scene class (9, 10: the lean path kernels of classes 1 and 2)
+UNIT_CLASS_BIT = {1: 1, 2: 1, 6: 1, 8: 1, 3: 2, 9: 2, 4: 4, 7: 4, 10: 4, 5: 8}      # the PSDR_CLS_MASK bit of the scene class a unit instantiates
 
 
 def build_hip(force=False, extra_flags=(), target=None):
-    """Eleven translation units compiled in parallel - api.hip (the host code with the small kernels), render_units.hip eight times (-DPSDR_TU=k:
+    """Thirteen translation units compiled in parallel - api.hip (the host code with the small kernels), render_units.hip ten times (-DPSDR_TU=k:
     unit k only instantiates list k of the heavy kernel templates, one scene class each), scene_build.hip and precond.hip - and linked into one
     library: ~4 minutes of wall time instead of ~10 for a single unit (PSDR_BUILD_JOBS=1 compiles them one after the other)."""
     os.makedirs(LIBDIR, exist_ok=True)
@@ -157,7 +157,7 @@ def hip_units(flags=()):
     for f in flags:
         if f.startswith("-DPSDR_CLS_MASK="):
             mask = int(f.split("=")[1])
-    return [("main", API_SRC, [], API_DEPS)] + [("tu%d" % k, UNITS_SRC, ["-DPSDR_TU=%d" % k], KERNEL_DEPS) for k in (1, 6, 8, 2, 4, 7, 5, 3) if UNIT_CLASS_BIT[k] & mask] + \
+    return [("main", API_SRC, [], API_DEPS)] + [("tu%d" % k, UNITS_SRC, ["-DPSDR_TU=%d" % k], KERNEL_DEPS) for k in (1, 6, 8, 2, 4, 10, 7, 5, 3, 9) if UNIT_CLASS_BIT[k] & mask] + \
            [("scene", SCENE_SRC, [], SCENE_DEPS), ("precond", PRECOND_SRC, [], PRECOND_DEPS)]
 
 
@@ -170,7 +170,7 @@ def _compile_hip(flags, target, objdir):
     jobs = max(1, int(os.environ.get("PSDR_BUILD_JOBS", str(min(len(units), os.cpu_count() or 1)))))
     objs, pending, running = [], [], []
     # an object is compiled again only when ITS sources, headers or flags changed (signature beside it): editing the scene-build unit or
-    # bvh.h leaves the eight kernel units - minutes of compile time - alone, and so does editing api.hip
+    # bvh.h leaves the ten kernel units - minutes of compile time - alone, and so does editing api.hip
     usigs = {}
     for name, src, defs, deps in units:
         obj = os.path.join(objdir, "api_%s.o" % name)

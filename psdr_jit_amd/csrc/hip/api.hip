@@ -22,7 +22,7 @@
 [[maybe_unused]] static int fail(const std::string &msg) { return psdr::api_fail(msg); }
 
 // the heavy kernels: every instantiation the launch layer below can name is defined in one of the kernel units
-PSDR_TU1(extern) PSDR_TU2(extern) PSDR_TU3(extern) PSDR_TU4(extern) PSDR_TU5(extern) PSDR_TU6(extern) PSDR_TU7(extern) PSDR_TU8(extern)
+PSDR_TU1(extern) PSDR_TU2(extern) PSDR_TU3(extern) PSDR_TU4(extern) PSDR_TU5(extern) PSDR_TU6(extern) PSDR_TU7(extern) PSDR_TU8(extern) PSDR_TU9(extern) PSDR_TU10(extern)
 
 // ------------------------------------------------------------------------------------------------
 // the plain kernels of this unit (its small kernel TEMPLATES - k_trace, k_intersect*, k_guiding_round - are in render_kernels.h and are
@@ -173,6 +173,12 @@ static inline int grid_for(const psdr_hip_scene *sc, long long n) {
 #define LAUNCH_CLS_(cls, K, RUNG3) do { if ((cls) == 1) ON_CLS(1, K(1)); else if ((cls) == 2) ON_CLS(2, K(2)); RUNG3 else ON_CLS(0, K(0)); } while (0)
 #define LAUNCH_CLS_FWD(cls, K) LAUNCH_CLS_(cls, K, else if ((cls) == 3) ON_CLS(3, K(3));)
 #define LAUNCH_CLS_REV(cls, K) LAUNCH_CLS_(cls, K, )
+// THE VARIANT DISPATCH of the forward path kernels (paths.h::Switches): the lean instantiations exist for classes 1 and 2, uncounted (PSDR_TU9 / PSDR_TU10); every
+// other rung names the general kernel twice.  `lean_`: this call is one the lean kernels are compiled for (render_impl)
+#define PATHS_VAR(C, COUNT) ((((C) == 1 || (C) == 2) && !(COUNT)) ? kLean : kGeneral)
+#define LAUNCH_PATHS(C, AD_, COUNT, MODE_, lean_, sc, n_lanes, stream, ...) \
+    do { if (lean_) LAUNCH(C, (k_paths<AD_, C, CLS_COUNTED(C, COUNT), MODE_, PATHS_VAR(C, COUNT)>), sc, n_lanes, stream, __VA_ARGS__); \
+         else LAUNCH(C, (k_paths<AD_, C, CLS_COUNTED(C, COUNT), MODE_, kGeneral>), sc, n_lanes, stream, __VA_ARGS__); } while (0)
 
 // dynamic LDS of a kernel of scene class `cls` (0 global tables, 1 LDS blob, 2 lean BVH, 3 LDS blob with materials): the traversal stack / cold rows,
 // plus the blob only for the classes that stage it - a class-0 kernel launched on a scene that ALSO has an LDS class (reverse mode,
@@ -289,6 +295,9 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
     //  duration (tools/profile.sh) and a test can compare the forked call with the serial one)
     const bool no_fork = std::getenv("PSDR_NO_FORK") != nullptr;
     const bool fork = !no_fork && ad && !a->pix_ids && !lanes_out && !COUNT && T.n_tris > kBruteForceMax && ((terms & (PSDR_TERM_PRIMARY | PSDR_TERM_SECONDARY)) != 0) && (terms & (terms - 1)) != 0;
+    // the lean path kernels: forward mode (this function), PathTracer, perspective sensor, no per-lane output - what they fix at compile time (paths.h::Switches)
+    // (PSDR_NO_LEAN: measurement / test knob, read per call - the general kernels, which compute the same samples)
+    const bool lean = std::getenv("PSDR_NO_LEAN") == nullptr && a->direct_mode == 0 && a->field_mode == 0 && !lanes_out && !cam.ortho;
     unsigned long long *q_int = nullptr, *q_prim = nullptr, *q_sec = nullptr;
     // concurrent launches must not share the global tail of the traversal stack (trav4.h indexes it by workgroup and thread only): the edge terms get slices of their own
     SceneTables T_prim = T, T_sec = T;
@@ -308,8 +317,8 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
         if (lanes_out) { P.begin = lane_b; P.end = lane_e; P.shard_rank = 0; P.shard_count = 1; P.n_local = local_lanes(P.end - P.begin, 0, 1); }
         if (P.n_local > 0) {
             if (fork) P.counter = q_int; else if (next_queue(sc, st, P.counter)) return 1;
-#define K_INTERIOR_AD(C) LAUNCH(C, (k_paths<true, C, CLS_COUNTED(C, COUNT), 0>), sc, P.n_local, st, sc->blob.as<float4>(), T, cam, P, ctr)
-#define K_INTERIOR_C(C) LAUNCH(C, (k_paths<false, C, CLS_COUNTED(C, COUNT), 0>), sc, P.n_local, st, sc->blob.as<float4>(), T, cam, P, ctr)
+#define K_INTERIOR_AD(C) LAUNCH_PATHS(C, true, COUNT, 0, lean, sc, P.n_local, st, sc->blob.as<float4>(), T, cam, P, ctr)
+#define K_INTERIOR_C(C) LAUNCH_PATHS(C, false, COUNT, 0, lean, sc, P.n_local, st, sc->blob.as<float4>(), T, cam, P, ctr)
             if (ad) LAUNCH_CLS_FWD(cls, K_INTERIOR_AD); else LAUNCH_CLS_FWD(cls, K_INTERIOR_C);
 #undef K_INTERIOR_AD
 #undef K_INTERIOR_C
@@ -331,7 +340,7 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
             P.skip_static = a->skip_static_edges;
             if (P.n_local > 0) {
                 if (fork) P.counter = q_prim; else if (next_queue(sc, st, P.counter)) return 1;
-#define K_PRIMARY(C) LAUNCH(C, (k_paths<false, C, CLS_COUNTED(C, COUNT), 1>), sc, P.n_local, s_prim, sc->blob.as<float4>(), T_prim, cam, P, ctr)
+#define K_PRIMARY(C) LAUNCH_PATHS(C, false, COUNT, 1, lean, sc, P.n_local, s_prim, sc->blob.as<float4>(), T_prim, cam, P, ctr)
                 LAUNCH_CLS_FWD(cls, K_PRIMARY);
 #undef K_PRIMARY
             }
@@ -560,7 +569,7 @@ static int render_bwd_impl(const psdr_hip_scene *sc, const psdr_render_args *a, 
         if (P.n_local > 0) {
             if (next_queue(sc, st, P.counter)) return 1;
             const size_t sm = smem_for(sc, cls) + (P.lds_acc ? sizeof(float) * 4 * (size_t) cam.n_edges : 0);
-#define K_PRIMARY_ADJ(C) LAUNCH_SM((k_paths<false, C, false, 1>), sc, P.n_local, sm, st, sc->blob.as<float4>(), Tp, cam, P, (Counters *) nullptr)
+#define K_PRIMARY_ADJ(C) LAUNCH_SM((k_paths<false, C, false, 1, kGeneral>), sc, P.n_local, sm, st, sc->blob.as<float4>(), Tp, cam, P, (Counters *) nullptr)
             LAUNCH_CLS_REV(cls, K_PRIMARY_ADJ);
 #undef K_PRIMARY_ADJ
         }

@@ -9,9 +9,22 @@
 
 namespace psdr {
 
+// the origin of a perspective sensor's primary rays, xform_pos(cam.to_world, 0) term for term - the same for every sample of a launch.  Its homogeneous
+// coordinate is the matrix's own m[15]: where that is 1 (a wave-uniform test) the three divisions are skipped, x / 1.f being x in IEEE arithmetic (signed
+// zeros, infinities and NaN included)
+PSDR_DEV Vec3f primary_ray_origin(const SensorDev &cam) {
+    const Mat4<float> &M = cam.to_world;
+    float r[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = fma_(M.m[4 * i + 2], 0.f, fma_(M.m[4 * i + 1], 0.f, M.m[4 * i] * 0.f)) + M.m[4 * i + 3];
+    if (r[3] == 1.f) return Vec3f(r[0], r[1], r[2]);
+    return Vec3f(r[0], r[1], r[2]) / r[3];
+}
+
 // PerspectiveCamera::sample_primary_ray, reference perspective.cpp:160-178 (direction detached in D mode)
-template <bool AD> PSDR_DEV RayT<AD> sample_primary_ray(const SensorDev &cam, float sx, float sy) {
-    if (cam.ortho) {      // OrthographicCamera::sample_primary_ray, orthographic.cpp:161-181
+// ORTHO_POSSIBLE = false: the caller knows the sensor to be a perspective one (the lean path kernels, paths.h)
+template <bool AD, bool ORTHO_POSSIBLE = true> PSDR_DEV RayT<AD> sample_primary_ray(const SensorDev &cam, float sx, float sy) {
+    if (ORTHO_POSSIBLE && cam.ortho) {      // OrthographicCamera::sample_primary_ray, orthographic.cpp:161-181
         const Vec3f near_p = xform_pos(cam.sample_to_camera, Vec3f(sx, sy, 0.f));
         RayT<AD> r;
         if constexpr (AD) {
@@ -35,7 +48,7 @@ template <bool AD> PSDR_DEV RayT<AD> sample_primary_ray(const SensorDev &cam, fl
         r.o = xform_pos(M, Vec3d(Dual(0.f)));
         r.d = xform_dir(M, promote(d));
     } else {
-        r.o = xform_pos(cam.to_world, Vec3f(0.f));
+        r.o = primary_ray_origin(cam);
         r.d = xform_dir(cam.to_world, d);
     }
     return r;

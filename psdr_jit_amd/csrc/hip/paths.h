@@ -50,9 +50,27 @@ struct PathParams {
     const unsigned char *prim_filter;
 };
 
+// KERNEL VARIANTS (the last template parameter of k_paths / run_paths / run_paths_async).  A launch is one kind of call - forward or reverse mode, PathTracer or a
+// DirectIntegrator or a first-hit integrator, perspective or orthographic sensor, with or without the per-lane output - and the general kernel carries all of
+// them as launch-uniform run-time branches, whose operands are kernel arguments that stay live across the path loop.  The lean variant fixes the commonest call at
+// compile time: forward mode (adj_w == NULL; lds_acc and prim_filter unused), PathTracer (mis == -1, field < 0), lanes_out == NULL, perspective sensor.  The path
+// code reads these switches through Switches<VAR> only, so one body serves both; skip_static, hide_emitters, max_depth, the shard and pix_ids stay run-time.
+// api.hip launches the lean kernel when the call qualifies (PSDR_NO_LEAN in the environment: never).
+constexpr int kGeneral = 0, kLean = 1;
+template <int VAR> struct Switches {
+    static constexpr bool lean = VAR == kLean;
+    static PSDR_DEV const float *adj_w(const PathParams &P) { if constexpr (lean) return nullptr; else return P.adj_w; }
+    static PSDR_DEV const unsigned char *prim_filter(const PathParams &P) { if constexpr (lean) return nullptr; else return P.prim_filter; }
+    static PSDR_DEV float *lanes_out(const PathParams &P) { if constexpr (lean) return nullptr; else return P.lanes_out; }
+    static PSDR_DEV int mis(const PathParams &P) { if constexpr (lean) return -1; else return P.mis; }
+    template <typename View> static PSDR_DEV int field(const View &S) { if constexpr (lean) return -1; else return S.field; }
+    static PSDR_DEV bool ortho(const SensorDev &cam) { if constexpr (lean) return false; else return cam.ortho != 0; }
+};
+
 // (x_dot_n.d == 0: the sample's d_out is 0 x (Ln - Lp) / pdf - zero, or a NaN that the accumulation drops)
-PSDR_DEV bool edge_sample_idle(const PathParams &P, int ei, float xdn_d) {
-    return P.adj_w == nullptr ? (P.skip_static != 0 && xdn_d == 0.f) : (P.prim_filter != nullptr && P.prim_filter[ei] == 0);
+template <int VAR> PSDR_DEV bool edge_sample_idle(const PathParams &P, int ei, float xdn_d) {
+    using sw = Switches<VAR>;
+    return sw::adj_w(P) == nullptr ? (P.skip_static != 0 && xdn_d == 0.f) : (sw::prim_filter(P) != nullptr && sw::prim_filter(P)[ei] == 0);
 }
 
 #ifndef PSDR_FETCH_BATCH
@@ -114,9 +132,9 @@ PSDR_DEV long long take_live_items(const SceneTables &T, const SensorDev &cam, c
     return item;
 }
 
-template <bool AD, int LDS, bool COUNT, int MODE>
+template <bool AD, int LDS, bool COUNT, int MODE, int VAR = kGeneral>
 PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParams &P) {
-    using R = Num<AD>; using V = VecN<AD>;
+    using R = Num<AD>; using V = VecN<AD>; using sw = Switches<VAR>;
     const SceneTables &T = *S.T;
     const int lane_id = threadIdx.x & 63;
     const unsigned long long lt_mask = (1ull << lane_id) - 1ull;
@@ -176,7 +194,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
             const int n_need = __popcll(need);
             long long item = q_end;                       // the work item this lane starts (q_end: none)
             int n_taken;                                  // queue positions consumed
-            if (MODE == 0 && !COUNT && cam.live != nullptr && P.lanes_out == nullptr && P.end < (1ll << 31)) {      // (the counted builds and the per-lane output see every sample)
+            if (MODE == 0 && !COUNT && cam.live != nullptr && sw::lanes_out(P) == nullptr && P.end < (1ll << 31)) {      // (the counted builds and the per-lane output see every sample)
                 // LIVE PIXELS ONLY (round 4): take_live_items above
                 item = take_live_items(T, cam, P, !busy, q_next, q_end, lane_id, lt_mask, n_taken);
             } else {
@@ -192,11 +210,11 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                         const long long k = T.spp > 1 ? lane / T.spp : lane;
                         const int pix = P.pix_ids ? P.pix_ids[k] : (int) k;
                         park_i(kPix, (int) k);
-                        if (P.lanes_out) { park_i(kLaneLo, (int) (unsigned) ((lane - P.begin) & 0xffffffffll)); park_i(kLaneHi, (int) ((lane - P.begin) >> 32)); }
+                        if (sw::lanes_out(P)) { park_i(kLaneLo, (int) (unsigned) ((lane - P.begin) & 0xffffffffll)); park_i(kLaneHi, (int) ((lane - P.begin) >> 32)); }
                         rng.seed(P.seed + (P.pix_ids ? (unsigned long long) (long long) pix : (unsigned long long) lane), (unsigned long long) lane, P.skip);
                         const float bx = (float) (pix % T.width), by = (float) (pix / T.width);
                         const float jx = rng.next_1d(), jy = rng.next_1d();
-                        ext = sample_primary_ray<AD>(cam, (bx + jx) / (float) T.width, (by + jy) / (float) T.height);
+                        ext = sample_primary_ray<AD, !sw::lean>(cam, (bx + jx) / (float) T.width, (by + jy) / (float) T.height);
                     } else {
                         // PerspectiveCamera::sample_primary_edge, reference perspective.cpp:200-226
                         rng.seed(P.seed + (unsigned long long) lane, (unsigned long long) lane, P.skip);
@@ -212,13 +230,15 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                         const Dual x_dot_n = fma_(py, ny, px * nx);
                         const int ix = (int) floorf(px.v * (float) T.width), iy = (int) floorf(py.v * (float) T.height);
                         const int edge_slot = (ix >= 0 && ix < T.width && iy >= 0 && iy < T.height) ? edge_pixel_slot(T, iy * T.width + ix) : -1;      // (-1 also: not in the batch list)
-                        const bool edge_valid = edge_slot >= 0 && !edge_sample_idle(P, ei, x_dot_n.d);
+                        const bool edge_valid = edge_slot >= 0 && !edge_sample_idle<VAR>(P, ei, x_dot_n.d);
                         park_i(kPix, edge_valid ? edge_slot : -1);
-                        const RayT<false> ray_p = sample_primary_ray<false>(cam, px.v + kEdgeEpsilon * nx, py.v + kEdgeEpsilon * ny);
-                        const RayT<false> ray_n = sample_primary_ray<false>(cam, px.v - kEdgeEpsilon * nx, py.v - kEdgeEpsilon * ny);
-                        if constexpr (!AD) { ext = ray_n; cam_p = ray_p; trace_p = edge_valid; }      // (ray_p is rebuilt from (edge_i, edge_s) when the first path has ended: make_its wants it)
+                        const RayT<false> ray_p = sample_primary_ray<false, !sw::lean>(cam, px.v + kEdgeEpsilon * nx, py.v + kEdgeEpsilon * ny);
+                        const RayT<false> ray_n = sample_primary_ray<false, !sw::lean>(cam, px.v - kEdgeEpsilon * nx, py.v - kEdgeEpsilon * ny);
+                        if constexpr (!AD) { ext = ray_n; cam_p = ray_p; trace_p = edge_valid; }
                         side = 0;
-                        park_f(kXdnV, x_dot_n.v); park_f(kXdnD, x_dot_n.d); park_f(kPdf, pdf); park_f(kEdgeS, s); park_f(kNx, nx); park_f(kNy, ny); park_i(kEdgeI, ei);
+                        park_f(kXdnV, x_dot_n.v); park_f(kXdnD, x_dot_n.d); park_f(kPdf, pdf);
+                        // (the edge sample itself: read again by the reverse mode's scatter and by an orthographic sensor's second path, see the side switch below)
+                        if (sw::adj_w(P) != nullptr || sw::ortho(cam)) { park_f(kEdgeS, s); park_f(kNx, nx); park_f(kNy, ny); park_i(kEdgeI, ei); }
                         if (!edge_valid) busy = false;       // Li(..., valid=false) contributes nothing
                     }
                 }
@@ -234,7 +254,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
         PositionSample<AD> ps;
         V wod(R(0.f)); R dist_sqr(0.f), dist(0.f);
         RayT<AD> ray1; ray1.o = V(R(0.f)); ray1.d = V(R(0.f));
-        if (at_vertex && P.mis != 1) {           // (DirectIntegrator(1) neither draws nor uses the emitter sample)
+        if (at_vertex && sw::mis(P) != 1) {           // (DirectIntegrator(1) neither draws nor uses the emitter sample)
             const float sx = rng.next_1d(), sy = rng.next_1d();
             do_nee = mesh_emitter(S, its.mesh) < 0;
             if (do_nee) {
@@ -249,7 +269,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
         // ------------------------------------------------------------------ [B] extension ray (drawn before the traces
         // so that both rays of this vertex share one pass over the triangles; the draw order is unchanged)
         BSDFSample bs; bs.wo = Vec3f(0.f, 0.f, 1.f); bs.pdf = 1.f; bs.valid = true;
-        const bool do_bsdf = at_vertex && P.mis != 0;      // (DirectIntegrator(0) stops after the emitter sample)
+        const bool do_bsdf = at_vertex && sw::mis(P) != 0;      // (DirectIntegrator(0) stops after the emitter sample)
         if (at_vertex && !do_bsdf) bs.valid = false;
         if (do_bsdf) {
             const float s0 = rng.next_1d(), s1 = rng.next_1d(), s2 = rng.next_1d();
@@ -280,7 +300,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                     V bsdf_val2 = bsdf_eval<AD, LDS>(S, its, wo_local, true);
                     bsdf_val2 = bsdf_val2 * div_(G_val * ps.J, R(ps.pdf));
                     const float pdf1 = bsdf_pdf<AD, LDS>(S, its, wo_local, true) * detach(G_val);
-                    if (pdf1 != 0.f) res = res + thr * emitter_val * bsdf_val2 * R(P.mis == 0 ? 1.f : mis_weight(ps.pdf, pdf1));
+                    if (pdf1 != 0.f) res = res + thr * emitter_val * bsdf_val2 * R(sw::mis(P) == 0 ? 1.f : mis_weight(ps.pdf, pdf1));
                 }
             }
         }
@@ -292,7 +312,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
             if (depth < 0) {
                 // first hit: result = Le (path.cpp:38-43)
                 its = itx;
-                if (S.field >= 0) { if constexpr (has_mat(LDS)) res = first_hit_value<AD, LDS>(S, itx); }
+                if (sw::field(S) >= 0) { if constexpr (has_mat(LDS)) res = first_hit_value<AD, LDS>(S, itx); }
                 else if (!P.hide_emitters) res = eval_Le<AD, LDS>(S, itx, itx.valid);
                 depth = 0;
                 finished = !itx.valid || P.max_depth == 0;
@@ -315,7 +335,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                         if (itx.t < kEpsilon) bsdf_val = V(0.f);
                         else bsdf_val = vdiv_(bsdf_eval<AD, LDS>(S, its, bs.wo, true), bs.pdf);
                     }
-                    const float weight2 = P.mis == 1 ? 1.f : mis_weight(pdf0, emitter_position_pdf<AD, LDS>(S, detach(its.p), itx));
+                    const float weight2 = sw::mis(P) == 1 ? 1.f : mis_weight(pdf0, emitter_position_pdf<AD, LDS>(S, detach(its.p), itx));
                     thr = thr * bsdf_val;
                     res = res + eval_Le<AD, LDS>(S, itx, true) * thr * R(weight2);
                     its = itx;
@@ -334,9 +354,9 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                 const float pv[3] = {detach(res.x), detach(res.y), detach(res.z)};
                 const float tv[3] = {tangent(res.x), tangent(res.y), tangent(res.z)};
                 const int pix_slot = cold_i(kPix);
-                if (P.lanes_out) {
+                if (sw::lanes_out(P)) {
                     const long long o = 3 * (((long long) cold_i(kLaneHi) << 32) | (long long) (unsigned) cold_i(kLaneLo));
-                    P.lanes_out[o] = pv[0]; P.lanes_out[o + 1] = pv[1]; P.lanes_out[o + 2] = pv[2];
+                    float *lo = sw::lanes_out(P); lo[o] = pv[0]; lo[o + 1] = pv[1]; lo[o + 2] = pv[2];
                 }
                 if (P.out) {
 #pragma unroll
@@ -356,21 +376,28 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                 if (side == 0) {
                     { const Vec3f Ln = detach(res); park_f(kLnX, Ln.x); park_f(kLnY, Ln.y); park_f(kLnZ, Ln.z); }
                     // the reference's Li always draws 5 numbers per depth level; skip what this path left
-                    if (depth < P.max_depth) rng.advance((unsigned long long) ((P.mis == 0 ? 2 : (P.mis == 1 ? 3 : 5)) * (P.max_depth - depth)));
+                    if (depth < P.max_depth) rng.skip_levels(sw::mis(P) == 0 ? 2 : (sw::mis(P) == 1 ? 3 : 5), P.max_depth - depth);
                     side = 1; depth = -1; thr = V(R(1.f)); res = V(R(0.f));
                     if constexpr (!AD) {
-                        // ray_p = sample_primary_ray(p + EdgeEpsilon * n): the same arithmetic as at the start of the work item
-                        const int edge_i = cold_i(kEdgeI);
-                        const float edge_s = cold_f(kEdgeS), edge_nx = cold_f(kNx), edge_ny = cold_f(kNy);
-                        const float4 r0 = S.ld(cam.pe_off + 3 * edge_i);
-                        const float oms = 1.0f - edge_s;
-                        const float pxv = fmaf(r0.x, oms, r0.z * edge_s), pyv = fmaf(r0.y, oms, r0.w * edge_s);
-                        ext = sample_primary_ray<false>(cam, pxv + kEdgeEpsilon * edge_nx, pyv + kEdgeEpsilon * edge_ny);
+                        // The second path's camera ray ray_p = sample_primary_ray(p + EdgeEpsilon * n) was traced in the first path's first trace.  Of the ray itself only
+                        // the ORIGIN is still wanted - make_its below takes its direction from hit point - origin, and ext.d is set by the BSDF sample before the next
+                        // trace reads it -: the sensor's position for a perspective camera, the same for every sample; for an orthographic one the near-plane point,
+                        // by the same arithmetic as at the start of the work item
+                        if (sw::ortho(cam)) {
+                            const int edge_i = cold_i(kEdgeI);
+                            const float edge_s = cold_f(kEdgeS), edge_nx = cold_f(kNx), edge_ny = cold_f(kNy);
+                            const float4 r0 = S.ld(cam.pe_off + 3 * edge_i);
+                            const float oms = 1.0f - edge_s;
+                            const float pxv = fmaf(r0.x, oms, r0.z * edge_s), pyv = fmaf(r0.y, oms, r0.w * edge_s);
+                            ext.o = sample_primary_ray<false, !sw::lean>(cam, pxv + kEdgeEpsilon * edge_nx, pyv + kEdgeEpsilon * edge_ny).o;
+                        } else {
+                            ext.o = primary_ray_origin(cam);
+                        }
                         // ... and its hit was found in the first path's first trace: the second path starts AT its first vertex (path.cpp:38-43)
                         Hit hp; hp.slot = cold_i(kHpSlot); hp.u = cold_f(kHpU); hp.v = cold_f(kHpV); hp.t = cold_f(kHpT);
                         const Its<AD> itp = make_its<AD, LDS, true>(S, hp, ext, false);
                         its = itp;
-                        if (S.field >= 0) { if constexpr (has_mat(LDS)) res = first_hit_value<AD, LDS>(S, itp); }
+                        if (sw::field(S) >= 0) { if constexpr (has_mat(LDS)) res = first_hit_value<AD, LDS>(S, itp); }
                         else if (!P.hide_emitters) res = eval_Le<AD, LDS>(S, itp, itp.valid);
                         depth = 0;
                         sample_done = !itp.valid || P.max_depth == 0;
@@ -383,7 +410,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                     const int pix_slot = cold_i(kPix);
                     const Vec3f dL = vdiv_(Ln - Lp, edge_pdf);
                     const float o3[3] = {dL.x, dL.y, dL.z};
-                    if (P.adj_w == nullptr) {
+                    if (sw::adj_w(P) == nullptr) {
 #pragma unroll
                         for (int c = 0; c < 3; ++c) {
                             const float pv = edge_xdn_v * o3[c];
@@ -400,7 +427,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                             float k = o3[c];
                             if (!finite_(edge_xdn_v * k) || !finite_(k)) k = 0.f;
                             if (T.sppe > 1) k /= (float) T.sppe;
-                            kw += P.adj_w[3 * (long long) pix_slot + c] * k;
+                            kw += sw::adj_w(P)[3 * (long long) pix_slot + c] * k;
                         }
                         if (kw != 0.f) {
                             const int edge_i = cold_i(kEdgeI);
@@ -441,9 +468,9 @@ constexpr int kShadeMin = PSDR_SHADE_MIN;
 
 // (round 5, measured and not kept here: posting the second edge path's camera ray beside the first's - what run_paths does - leaves config 5's primary-edge kernel at
 //  163.6 ms (163.3 before): the four registers of the parked hit and the second make_its cost what the saved queue rounds give)
-template <bool AD, int LDS, bool COUNT, int MODE>
+template <bool AD, int LDS, bool COUNT, int MODE, int VAR = kGeneral>
 PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const PathParams &P) {
-    using R = Num<AD>; using V = VecN<AD>;
+    using R = Num<AD>; using V = VecN<AD>; using sw = Switches<VAR>;
     const SceneTables &T = *S.T;
     const int lane_id = threadIdx.x & 63;
     const unsigned long long lt_mask = (1ull << lane_id) - 1ull;
@@ -518,7 +545,7 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                         V bsdf_val2 = bsdf_eval<AD, LDS>(S, its, wo_local, true);
                         bsdf_val2 = bsdf_val2 * div_(G_val * ps.J, R(ps.pdf));
                         const float pdf1 = bsdf_pdf<AD, LDS>(S, its, wo_local, true) * detach(G_val);
-                        if (pdf1 != 0.f) res = res + thr * emitter_val * bsdf_val2 * R(P.mis == 0 ? 1.f : mis_weight(ps.pdf, pdf1));
+                        if (pdf1 != 0.f) res = res + thr * emitter_val * bsdf_val2 * R(sw::mis(P) == 0 ? 1.f : mis_weight(ps.pdf, pdf1));
                     }
                 }
 #if !PSDR_DIAG
@@ -527,7 +554,7 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                 const Its<AD> itx = make_its<AD, LDS, true>(S, hx, ext, depth >= 0);
                 if (depth < 0) {
                     its = itx;
-                    if (S.field >= 0) { if constexpr (has_mat(LDS)) res = first_hit_value<AD, LDS>(S, itx); }
+                    if (sw::field(S) >= 0) { if constexpr (has_mat(LDS)) res = first_hit_value<AD, LDS>(S, itx); }
                     else if (!P.hide_emitters) res = eval_Le<AD, LDS>(S, itx, itx.valid);
                     depth = 0;
                     finished = !itx.valid || P.max_depth == 0;
@@ -549,7 +576,7 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                             if (itx.t < kEpsilon) bsdf_val = V(0.f);
                             else bsdf_val = vdiv_(bsdf_eval<AD, LDS>(S, its, bs.wo, true), bs.pdf);
                         }
-                        const float weight2 = P.mis == 1 ? 1.f : mis_weight(pdf0, emitter_position_pdf<AD, LDS>(S, detach(its.p), itx));
+                        const float weight2 = sw::mis(P) == 1 ? 1.f : mis_weight(pdf0, emitter_position_pdf<AD, LDS>(S, detach(its.p), itx));
                         thr = thr * bsdf_val;
                         res = res + eval_Le<AD, LDS>(S, itx, true) * thr * R(weight2);
                         its = itx;
@@ -566,9 +593,9 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                 if (MODE == 0) {
                     const float pv[3] = {detach(res.x), detach(res.y), detach(res.z)};
                     const float tv[3] = {tangent(res.x), tangent(res.y), tangent(res.z)};
-                    if (P.lanes_out) {
+                    if (sw::lanes_out(P)) {
                         const long long o = 3 * (lane - P.begin);
-                        P.lanes_out[o] = pv[0]; P.lanes_out[o + 1] = pv[1]; P.lanes_out[o + 2] = pv[2];
+                        float *lo = sw::lanes_out(P); lo[o] = pv[0]; lo[o + 1] = pv[1]; lo[o + 2] = pv[2];
                     }
                     if (P.out) {
 #pragma unroll
@@ -586,19 +613,19 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                 } else {
                     if (side == 0) {
                         Ln = detach(res);
-                        if (depth < P.max_depth) rng.advance((unsigned long long) ((P.mis == 0 ? 2 : (P.mis == 1 ? 3 : 5)) * (P.max_depth - depth)));
+                        if (depth < P.max_depth) rng.skip_levels(sw::mis(P) == 0 ? 2 : (sw::mis(P) == 1 ? 3 : 5), P.max_depth - depth);
                         side = 1; depth = -1; thr = V(R(1.f)); res = V(R(0.f));
                         if constexpr (!AD) {
                             const float4 r0 = S.ld(cam.pe_off + 3 * edge_i);
                             const float oms = 1.0f - edge_s;
                             const float pxv = fmaf(r0.x, oms, r0.z * edge_s), pyv = fmaf(r0.y, oms, r0.w * edge_s);
-                            ext = sample_primary_ray<false>(cam, pxv + kEdgeEpsilon * edge_nx, pyv + kEdgeEpsilon * edge_ny);
+                            ext = sample_primary_ray<false, !sw::lean>(cam, pxv + kEdgeEpsilon * edge_nx, pyv + kEdgeEpsilon * edge_ny);
                         }
                     } else {
                         const Vec3f Lp = detach(res);
                         const Vec3f dL = vdiv_(Ln - Lp, edge_pdf);
                         const float o3[3] = {dL.x, dL.y, dL.z};
-                        if (P.adj_w == nullptr) {
+                        if (sw::adj_w(P) == nullptr) {
 #pragma unroll
                             for (int c = 0; c < 3; ++c) {
                                 const float pv = edge_xdn_v * o3[c];
@@ -614,7 +641,7 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                                 float k = o3[c];
                                 if (!finite_(edge_xdn_v * k) || !finite_(k)) k = 0.f;
                                 if (T.sppe > 1) k /= (float) T.sppe;
-                                kw += P.adj_w[3 * (long long) pix_slot + c] * k;
+                                kw += sw::adj_w(P)[3 * (long long) pix_slot + c] * k;
                             }
                             if (kw != 0.f) {
                                 const float a = (1.0f - edge_s) * kw, b = edge_s * kw;
@@ -639,7 +666,7 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                 const int n_need = __popcll(need);
                 long long item;
                 int n_taken;
-                if (MODE == 0 && !COUNT && cam.live != nullptr && P.lanes_out == nullptr && P.end < (1ll << 31)) item = take_live_items(T, cam, P, ready && !busy, q_next, q_end, lane_id, lt_mask, n_taken);
+                if (MODE == 0 && !COUNT && cam.live != nullptr && sw::lanes_out(P) == nullptr && P.end < (1ll << 31)) item = take_live_items(T, cam, P, ready && !busy, q_next, q_end, lane_id, lt_mask, n_taken);
                 else { item = q_next + __popcll(need & lt_mask); n_taken = n_need < (int) (q_end - q_next) ? n_need : (int) (q_end - q_next); }
                 if (ready && !busy && item < q_end) {
                     const long long chunk = (item >> 8) * P.shard_count + P.shard_rank;
@@ -653,7 +680,7 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                             rng.seed(P.seed + (P.pix_ids ? (unsigned long long) (long long) pix : (unsigned long long) lane), (unsigned long long) lane, P.skip);
                             const float bx = (float) (pix % T.width), by = (float) (pix / T.width);
                             const float jx = rng.next_1d(), jy = rng.next_1d();
-                            ext = sample_primary_ray<AD>(cam, (bx + jx) / (float) T.width, (by + jy) / (float) T.height);
+                            ext = sample_primary_ray<AD, !sw::lean>(cam, (bx + jx) / (float) T.width, (by + jy) / (float) T.height);
                         } else {
                             rng.seed(P.seed + (unsigned long long) lane, (unsigned long long) lane, P.skip);
                             float s = rng.next_1d(), pdf;
@@ -668,9 +695,9 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                             const Dual x_dot_n = fma_(py, ny, px * nx);
                             const int ix = (int) floorf(px.v * (float) T.width), iy = (int) floorf(py.v * (float) T.height);
                             const int edge_slot = (ix >= 0 && ix < T.width && iy >= 0 && iy < T.height) ? edge_pixel_slot(T, iy * T.width + ix) : -1;      // (-1 also: not in the batch list)
-                            edge_valid = edge_slot >= 0 && !edge_sample_idle(P, ei, x_dot_n.d);
+                            edge_valid = edge_slot >= 0 && !edge_sample_idle<VAR>(P, ei, x_dot_n.d);
                             pix_slot = edge_valid ? edge_slot : -1;
-                            const RayT<false> ray_n = sample_primary_ray<false>(cam, px.v - kEdgeEpsilon * nx, py.v - kEdgeEpsilon * ny);
+                            const RayT<false> ray_n = sample_primary_ray<false, !sw::lean>(cam, px.v - kEdgeEpsilon * nx, py.v - kEdgeEpsilon * ny);
                             if constexpr (!AD) ext = ray_n;
                             side = 0;
                             edge_xdn_v = x_dot_n.v; edge_xdn_d = x_dot_n.d; edge_pdf = pdf; edge_s = s; edge_nx = nx; edge_ny = ny; edge_i = ei;
@@ -685,7 +712,7 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                 const bool at_vertex = depth >= 0;
                 do_nee = false;
                 wod = V(R(0.f)); dist_sqr = R(0.f); dist = R(0.f);
-                if (at_vertex && P.mis != 1) {
+                if (at_vertex && sw::mis(P) != 1) {
                     const float sx = rng.next_1d(), sy = rng.next_1d();
                     do_nee = mesh_emitter(S, its.mesh) < 0;
                     if (do_nee) {
@@ -697,7 +724,7 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                     }
                 }
                 bs.wo = Vec3f(0.f, 0.f, 1.f); bs.pdf = 1.f; bs.valid = true;
-                const bool do_bsdf = at_vertex && P.mis != 0;
+                const bool do_bsdf = at_vertex && sw::mis(P) != 0;
                 if (at_vertex && !do_bsdf) bs.valid = false;
                 if (do_bsdf) {
                     const float s0 = rng.next_1d(), s1 = rng.next_1d(), s2 = rng.next_1d();

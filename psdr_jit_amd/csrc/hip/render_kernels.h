@@ -65,19 +65,20 @@ template <int LDS> PSDR_DEV float *scratch_base(float4 *smem, const SceneTables 
 
 // BVH scenes of the global-memory classes take the decoupled form (traversal refilled per ray, paths.h); brute-force scenes and the
 // LDS class keep the lock-step form
-template <bool AD, int LDS, bool COUNT, int MODE>
+template <bool AD, int LDS, bool COUNT, int MODE, int VAR>
 PSDR_DEV void run_paths_any(SceneView<LDS> &S, const SensorDev &cam, const PathParams &P) {
     if constexpr (!in_lds(LDS)) {
 #ifndef PSDR_NO_ASYNC        // measurement knob: the lock-step form on BVH scenes too
-        if (S.T->n_tris > kBruteForceMax) { run_paths_async<AD, LDS, COUNT, MODE>(S, cam, P); return; }
+        if (S.T->n_tris > kBruteForceMax) { run_paths_async<AD, LDS, COUNT, MODE, VAR>(S, cam, P); return; }
 #endif
     }
-    run_paths<AD, LDS, COUNT, MODE>(S, cam, P);
+    run_paths<AD, LDS, COUNT, MODE, VAR>(S, cam, P);
 }
 
 // ------------------------------------------------------------------------------------------------
 // interior term (MODE 0) and primary-edge term (MODE 1): persistent lanes with path regeneration, paths.h
-template <bool AD, int LDS, bool COUNT, int MODE>
+// VAR: kGeneral - every kind of call; kLean - forward mode, PathTracer, perspective sensor, no per-lane output, fixed at compile time (paths.h::Switches)
+template <bool AD, int LDS, bool COUNT, int MODE, int VAR>
 #ifndef PSDR_GLOBAL_C_WAVES
 #define PSDR_GLOBAL_C_WAVES 4
 #endif
@@ -97,19 +98,22 @@ __global__ __launch_bounds__(kBlock, (AD ? (in_lds(LDS) ? PSDR_LDS_AD_WAVES : (L
                                                   const PathParams P, Counters *ctr) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneView<LDS> S = make_view<LDS>(blob, T, smem);
-    S.mis = P.mis; S.field = P.field; S.field_object = P.field_object; S.intensity = P.intensity; S.d_intensity = P.d_intensity;
-    if (MODE == 1 && P.adj_w != nullptr && P.lds_acc) {
+    using sw = Switches<VAR>;
+    static_assert(!(COUNT && sw::lean), "the counted instantiations are general ones");
+    if constexpr (!sw::lean) { S.mis = P.mis; S.field = P.field; S.field_object = P.field_object; }      // (lean: make_view's -1 / -1, the PathTracer)
+    S.intensity = P.intensity; S.d_intensity = P.d_intensity;
+    if (MODE == 1 && sw::adj_w(P) != nullptr && P.lds_acc) {
         // reverse mode of the primary-edge term: 8.4 M samples add into a 42 x 4 table - accumulate per workgroup in LDS
         float *acc = scratch_base<LDS>(smem, T);
         for (int i = threadIdx.x; i < 4 * P.n_prim; i += kBlock) acc[i] = 0.f;
         __syncthreads();
         PathParams Q = P;
         Q.g_prim = acc;
-        run_paths_any<AD, LDS, COUNT, MODE>(S, cam, Q);
+        run_paths_any<AD, LDS, COUNT, MODE, VAR>(S, cam, Q);
         __syncthreads();
         for (int i = threadIdx.x; i < 4 * P.n_prim; i += kBlock) if (acc[i] != 0.f) atomicAdd(&P.g_prim[i], acc[i]);
     } else {
-        run_paths_any<AD, LDS, COUNT, MODE>(S, cam, P);
+        run_paths_any<AD, LDS, COUNT, MODE, VAR>(S, cam, P);
     }
     if (COUNT) flush_counters(S, ctr);
 }
@@ -761,9 +765,11 @@ __global__ __launch_bounds__(kBlock) void k_intersect_adj(const float4 *__restri
 
 // ------------------------------------------------------------------------------------------------
 // Split build (psdr_jit_amd/build.py): the heavy kernel templates of each scene class are instantiated in translation units of
-// their own - render_units.hip compiled with -DPSDR_TU=1..8, kernels only - and compiled in parallel; the host unit (api.hip: host
+// their own - render_units.hip compiled with -DPSDR_TU=1..10, kernels only - and compiled in parallel; the host unit (api.hip: host
 // code + the small kernels) declares those instantiations extern.  PSDR_TU<k>() defines list k, PSDR_TU<k>(extern) declares it.
-#define PSDR_INST_PATHS(PFX, AD_, C_, CNT_, M_) PFX template __global__ void k_paths<AD_, C_, CNT_, M_>(const float4 *, const SceneTables, const SensorDev, const PathParams, Counters *);
+#define PSDR_INST_PATHS_V(PFX, AD_, C_, CNT_, M_, V_) PFX template __global__ void k_paths<AD_, C_, CNT_, M_, V_>(const float4 *, const SceneTables, const SensorDev, const PathParams, Counters *);
+#define PSDR_INST_PATHS(PFX, AD_, C_, CNT_, M_) PSDR_INST_PATHS_V(PFX, AD_, C_, CNT_, M_, kGeneral)
+#define PSDR_INST_LEAN3(PFX, C_) PSDR_INST_PATHS_V(PFX, true, C_, false, 0, kLean) PSDR_INST_PATHS_V(PFX, false, C_, false, 0, kLean) PSDR_INST_PATHS_V(PFX, false, C_, false, 1, kLean)
 #define PSDR_INST_ADJ(PFX, C_) PFX template __global__ void k_interior_adjoint<C_>(const float4 *, const SceneTables, const SensorDev, const AdjointParams);
 #define PSDR_INST_ADJM(PFX, C_) PFX template __global__ void k_interior_adjoint_mat<C_>(const float4 *, const SceneTables, const SensorDev, const AdjointParams);
 #define PSDR_INST_SEC(PFX, C_, CNT_, ADJ_) PFX template __global__ void k_secondary_edges<C_, CNT_, ADJ_>(const float4 *, const SceneTables, const SecEdgeTables, const SensorDev, const PathParams, const GuidingDev, const int, Counters *);
@@ -776,4 +782,7 @@ __global__ __launch_bounds__(kBlock) void k_intersect_adj(const float4 *__restri
 #define PSDR_TU3(PFX) PSDR_INST_PATHS6(PFX, 1) PSDR_INST_ADJ(PFX, 1) PSDR_INST_SEC(PFX, 1, false, false) PSDR_INST_SEC(PFX, 1, true, false) PSDR_INST_SEC(PFX, 1, false, true)
 #define PSDR_TU4(PFX) PSDR_INST_PATHS6(PFX, 2) PSDR_INST_SEC(PFX, 2, false, false) PSDR_INST_SEC(PFX, 2, true, false) PSDR_INST_SEC(PFX, 2, false, true)
 #define PSDR_TU7(PFX) PSDR_INST_ADJ(PFX, 2)          // a unit of its own: when the ISA lint sends it to the second allocator (build.py), the class-2 path kernels do not pay for it
+// the lean path kernels (paths.h::Switches) of the classes that have them: 1 (the Cornell boxes) and 2 (BVH scenes), the uncounted instantiations
+#define PSDR_TU9(PFX) PSDR_INST_LEAN3(PFX, 1)
+#define PSDR_TU10(PFX) PSDR_INST_LEAN3(PFX, 2)
 #define PSDR_TU5(PFX) PSDR_INST_PATHS(PFX, true, 3, false, 0) PSDR_INST_PATHS(PFX, false, 3, false, 0) PSDR_INST_PATHS(PFX, false, 3, false, 1) PSDR_INST_SEC(PFX, 3, false, false)

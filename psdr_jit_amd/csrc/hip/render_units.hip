@@ -1,9 +1,9 @@
-// render_units.hip — the kernel units of libpsdr_hip.so: compiled once per k = 1..8 with -DPSDR_TU=k (psdr_jit_amd/build.py), each time
+// render_units.hip — the kernel units of libpsdr_hip.so: compiled once per k = 1..10 with -DPSDR_TU=k (psdr_jit_amd/build.py), each time
 // instantiating list PSDR_TU<k> of render_kernels.h and nothing else.  No host code: an edit of api.hip leaves these objects alone.
 #include "render_kernels.h"
 
 #if !defined(PSDR_TU)
-#error "render_units.hip is compiled with -DPSDR_TU=1..8"
+#error "render_units.hip is compiled with -DPSDR_TU=1..10"
 #elif PSDR_TU == 1
 PSDR_TU1()
 #elif PSDR_TU == 2
@@ -20,6 +20,10 @@ PSDR_TU6()
 PSDR_TU7()
 #elif PSDR_TU == 8
 PSDR_TU8()
+#elif PSDR_TU == 9
+PSDR_TU9()
+#elif PSDR_TU == 10
+PSDR_TU10()
 #else
-#error "PSDR_TU: 1..8"
+#error "PSDR_TU: 1..10"
 #endif

@@ -43,7 +43,7 @@ PSDR_RNG_HD uint64_t tea64(uint64_t v0, uint64_t v1) {
 struct SkipAhead {
     uint64_t mult, g;
 };
-PSDR_RNG_HD SkipAhead skip_ahead(uint64_t delta) {
+PSDR_RNG_HD constexpr SkipAhead skip_ahead(uint64_t delta) {
     uint64_t cur_mult = kPcgMult, cur_plus = 1u, acc_mult = 1u, acc_plus = 0u;
     while (delta > 0) {
         if (delta & 1) { acc_mult *= cur_mult; acc_plus = acc_plus * cur_mult + cur_plus; }
@@ -52,6 +52,19 @@ PSDR_RNG_HD SkipAhead skip_ahead(uint64_t delta) {
         delta >>= 1;
     }
     return SkipAhead{acc_mult, acc_plus};
+}
+
+// A path that ends early skips the draws of the depth levels it leaves: nd * k with nd the draws per level - 2, 3 or 5 (DirectIntegrator(0), (1), everything else) -
+// and k the levels left.  Up to kSkipLevelsMax levels the maps are constants of the code object (read-only device memory, one 16-byte load per lane: nothing of the
+// table lives in a register across the path loop) and a lane applies its entry with two multiplications instead of running the doubling loop.
+constexpr int kSkipLevelsMax = 8;
+struct SkipLevels { SkipAhead e[3][kSkipLevelsMax]; };
+PSDR_RNG_HD constexpr SkipLevels make_skip_levels() {
+    SkipLevels t{};
+    const int nds[3] = {2, 3, 5};
+    for (int a = 0; a < 3; ++a)
+        for (int k = 1; k <= kSkipLevelsMax; ++k) t.e[a][k - 1] = skip_ahead((uint64_t) (nds[a] * k));
+    return t;
 }
 
 struct LaneRng {
@@ -78,6 +91,16 @@ struct LaneRng {
             delta >>= 1;
         }
         state = acc_mult * state + acc_plus;
+    }
+    // advance(nd * k) for nd in {2, 3, 5}, k >= 1: the same numbers mod 2^64, from the table up to kSkipLevelsMax levels
+    PSDR_RNG_HD void skip_levels(int nd, int k) {
+        static constexpr SkipLevels tab = make_skip_levels();
+        if (k <= kSkipLevelsMax) {
+            const SkipAhead sk = tab.e[nd == 2 ? 0 : (nd == 3 ? 1 : 2)][k - 1];
+            state = sk.mult * state + sk.g * inc;
+        } else {
+            advance((uint64_t) nd * (uint64_t) k);
+        }
     }
     // Sampler::seed for one lane, then skip the draws earlier render calls consumed
     PSDR_RNG_HD void seed(uint64_t seed_value, uint64_t lane, uint64_t skip) {

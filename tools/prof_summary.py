@@ -97,7 +97,7 @@ def pmc(tag):
 def bench_name(k):
     """kernel template instantiation -> the name bench.py prints (un-instrumented forward kernels only)"""
     import re
-    m = re.match(r"k_paths<(\w+), (\d+), (\w+), (\d+)>", k)
+    m = re.match(r"k_paths<(\w+), (\d+), (\w+), (\d+)(?:, \d+)?>", k)       # (the fifth argument: the variant, paths.h::Switches - 0 general, 1 lean)
     if m and m.group(3) == "false":
         return "k_primary_edges" if m.group(4) == "1" else ("k_interior<AD>" if m.group(1) == "true" else "k_interior")
     m = re.match(r"k_secondary_edges<(\d+), (\w+), (\w+)>", k)
