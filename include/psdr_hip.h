@@ -29,8 +29,8 @@
 extern "C" {
 #endif
 
-/* (psdr_hip_render_d_fwd_batch / psdr_hip_render_d_bwd_batch were ADDED under version 16: no struct changed its layout and no existing entry point its behaviour,
- * so every ABI-16 caller stays valid; a caller that wants the two functions looks the symbols up) */
+/* (psdr_hip_render_d_fwd_batch / psdr_hip_render_d_bwd_batch, and later psdr_hip_render_c_sq / psdr_hip_render_d_fwd_sq, were ADDED under version 16: no struct changed
+ * its layout and no existing entry point its behaviour, so every ABI-16 caller stays valid; a caller that wants the added functions looks the symbols up) */
 #define PSDR_HIP_ABI_VERSION 16
 
 /* TriangleInfo SoA, reference include/psdr/types.h:162-175 (+ Scene::m_triangle_uv,
@@ -406,6 +406,22 @@ int psdr_hip_render_d_fwd(const psdr_hip_scene *scene, const psdr_render_args *a
  * psdr_hip_render_d_fwd (0 = all three).  The shards of such a call add up to the unsharded call, as those of the full frame do. */
 int psdr_hip_render_d_fwd_batch(const psdr_hip_scene *scene, const psdr_render_args *args,
                                 float *out_rgb, float *out_drgb, void *stream);
+/* psdr_hip_render_c / psdr_hip_render_d_fwd WITH the per-pixel sums of squared sample contributions (a diagnostic the reference does not have; DESIGN.md, "Sample
+ * squares").  out_sq / out_dsq have the layout of out_rgb / out_drgb, and
+ *     out_sq[p, c]  = the sum, over the samples of the launched terms, of (what that sample adds to out_rgb[p, c])^2,        out_dsq: the same for out_drgb:
+ * interior image (value / spp)^2, interior derivative (tangent / spp)^2, an edge sample (its whole, already / sppe or / sppse and / pdf divided, contribution)^2 - each
+ * after the NaN / Inf scrub of the plain call, so a scrubbed or zero contribution adds nothing to either buffer.  For ONE term with n independent samples behind a pixel
+ * estimate m - n = spp for the interior term, W*H*sppe and W*H*sppse for the edge terms, whose samples may land on any pixel - the unbiased variance of m is
+ * (sq - m*m/n) * n/(n-1).  Independent terms add: with several terms in args->terms, out_dsq is the SUM of their raw second moments, and the exact variance of such a
+ * derivative is the sum over single-term calls.  out_rgb / out_drgb and the sampler streams are those of the plain call with the same arguments (other order of the
+ * float atomics); args->pix_ids, terms, the shards in both modes, guiding, direct_mode, field_mode, hide_emitters, skip_static_edges and zero_output (which also clears
+ * the two new buffers) mean what they mean there - a pixel list has the interior term only; the squares of psdr_hip_render_d_fwd_batch do not exist.  The shards of
+ * such a call add up to the unsharded call in all four buffers.  NULL scene, args or output pointers are refused before any device call.
+ * Range: the squares are float32 like the sums, so a contribution below ~1e-19 in magnitude adds 0 and one above ~1.8e19 (finite, so it passes the scrub) adds +inf
+ * to the square while the image stays finite; such an entry says "one sample dominates", not a variance. */
+int psdr_hip_render_c_sq(const psdr_hip_scene *scene, const psdr_render_args *args, float *out_rgb, float *out_sq, void *stream);
+int psdr_hip_render_d_fwd_sq(const psdr_hip_scene *scene, const psdr_render_args *args,
+                             float *out_rgb, float *out_drgb, float *out_sq, float *out_dsq, void *stream);
 /* Reverse mode of renderD (the reference's drjit.backward through Integrator::renderD, README.md:102-106):
  * given d_rgb = d loss / d image ([n_pixels*3], device), accumulate the adjoints of the snapshot quantities
  * the image depends on.  All buffers are DEVICE pointers owned by the caller; rows follow the snapshot order.

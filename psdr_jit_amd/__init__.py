@@ -1569,5 +1569,73 @@ def render_d_fwd(integrator, scene, sensor_id=0, seed=-1, batch_pix=-1, terms=TE
     return _render_d_raw(integrator, scene, sensor_id, seed, batch_pix, terms, **_batch_kw(batch_edges))
 
 
+# ------------------------------------------------------------------ per-pixel sums of squared sample contributions
+def render_c_sq(integrator, scene, sensor_id=0, seed=-1, batch_pix=-1):
+    """renderC with its noise estimate from the same samples: returns (img, sq), both float32 [n_pixels, 3] and detached.
+
+    sq[p, c] = the sum over the pixel's spp samples of (what the sample adds to img[p, c])^2 = sum (x / spp)^2, after renderC's NaN / Inf scrub;
+    variance_from_sq(img, sq, samples_behind(scene, TERM_INTERIOR)) is the unbiased variance of img.  Works for every integrator that has renderC; img is
+    renderC's image (the float atomics add in another order) and the sampler state afterwards is the one renderC leaves.  On several ranks both
+    buffers travel in one all_reduce (written like the rest of the multi-GPU code without a node to measure it on)."""
+    dev = _device()
+    pix = _pix(batch_pix, dev)
+    n = int(pix.numel()) if pix is not None else scene.opts.width * scene.opts.height
+    rank, world = _shard()
+    buf = _torch.empty((2, n, 3), dtype=_torch.float32, device=dev)
+    integrator._shard_mode = _shard_mode() if world > 1 else 0
+    integrator._renderC(scene, sensor_id, seed, pix.data_ptr() if pix is not None else 0, n, buf[0].data_ptr(), _stream_ptr(), rank, world, buf[1].data_ptr())
+    _all_reduce(buf, world > 1)
+    return buf[0], buf[1]
+
+
+def render_d_fwd_sq(integrator, scene, sensor_id=0, seed=-1, batch_pix=-1, terms=TERM_ALL, tangents=None, batch_edges=False):
+    """render_d_fwd with the noise estimates of the image and of its forward derivative: returns (img, d_img, sq, d_sq), float32 [n_pixels, 3], detached.
+
+    sq / d_sq[p, c] = the sum, over the samples of the launched terms, of the square of what each sample adds to img / d_img[p, c] (interior: value / spp and
+    tangent / spp; an edge sample: its whole contribution).  For ONE term, variance_from_sq(d_img, d_sq, samples_behind(scene, term)) is the unbiased variance of
+    that term's d_img.  The three terms are independent, so the variance of a full derivative is the sum over three single-term calls (terms=TERM_INTERIOR,
+    TERM_PRIMARY, TERM_SECONDARY); with several terms in one call d_sq is the SUM of their raw second moments - an upper bound of the variance once
+    multiplied by n / (n - 1), not the variance.  The edge terms add nothing to img, hence nothing to sq.  A pixel list has the interior term only;
+    batch_edges=True is not accepted (the squares of that form do not exist).  img, d_img and the three sampler states are those of render_d_fwd with the same
+    arguments.  The buffers are diagnostics: nothing of them enters reverse mode.  On several ranks the four buffers travel in one all_reduce, the unsplit
+    form of _render_terms (no node exists to measure this on, as for the rest of the multi-GPU code)."""
+    if batch_edges:
+        raise ValueError("render_d_fwd_sq: batch_edges=True is not accepted (a pixel list has the squares of the interior term only)")
+    if tangents is not None:
+        _sync_params(scene, {id(k): v for k, v in tangents.items()})
+        scene._configure(scene.__dict__.get("_psdr_active", []))
+    dev = _device()
+    pix = _pix(batch_pix, dev)
+    n = int(pix.numel()) if pix is not None else scene.opts.width * scene.opts.height
+    rank, world = _shard()
+    integrator._shard_mode = _shard_mode() if world > 1 else 0
+    buf = _torch.zeros((4, n, 3), dtype=_torch.float32, device=dev)       # (zeros: the host may find nothing to launch - a pixel list with edge terms only, a first-hit integrator's secondary term)
+    integrator._renderD(scene, sensor_id, seed, pix.data_ptr() if pix is not None else 0, n, buf[0].data_ptr(), buf[1].data_ptr(), _stream_ptr(), rank, world, terms, False,
+                        buf[2].data_ptr(), buf[3].data_ptr())
+    _all_reduce(buf, world > 1)
+    return buf[0], buf[1], buf[2], buf[3]
+
+
+def variance_from_sq(mean, sq, n):
+    """The unbiased variance of a pixel estimate `mean` that is the sum of n independent, identically distributed sample contributions whose squares sum to `sq`:
+    (sq - mean^2 / n) * n / (n - 1).  Tensors or arrays, in their own precision; n = samples_behind(scene, term).  n <= 1 raises ValueError."""
+    if not n > 1:
+        raise ValueError("variance_from_sq: a variance needs n > 1 samples, got %r" % (n,))
+    return (sq - mean * mean / n) * (n / (n - 1))
+
+
+def samples_behind(scene, term):
+    """n of variance_from_sq for one term: spp samples behind a pixel of the interior term; W*H*sppe / W*H*sppse behind a pixel of an edge term, whose
+    samples are drawn over the whole frame and may land on any pixel."""
+    o = scene.opts
+    if term == TERM_INTERIOR:
+        return int(o.spp)
+    if term == TERM_PRIMARY:
+        return int(o.width) * int(o.height) * int(o.sppe)
+    if term == TERM_SECONDARY:
+        return int(o.width) * int(o.height) * int(o.sppse)
+    raise ValueError("samples_behind: one of TERM_INTERIOR, TERM_PRIMARY, TERM_SECONDARY")
+
+
 # the Laplacian vertex preconditioner and its optimiser (precond.py; kernels: csrc/hip/precond.hip)
 from .precond import laplacian_csr, LaplacianPreconditioner, AdamUniform  # noqa: E402,F401

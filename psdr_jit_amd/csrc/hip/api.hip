@@ -268,9 +268,10 @@ static int batch_edge_scratch(const psdr_hip_scene *sc, const psdr_render_args *
     return 0;
 }
 
+// sq / dsq (psdr_hip_render_c_sq / _d_fwd_sq; NULL = a plain call): the per-pixel sums of squared sample contributions, rows as out / dout
 template <bool COUNT>
 static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool ad, float *out, float *dout, float *lanes_out,
-                       long long lane_b, long long lane_e, psdr_counters *counters, void *stream, bool batch_edges = false) {
+                       long long lane_b, long long lane_e, psdr_counters *counters, void *stream, bool batch_edges = false, float *sq = nullptr, float *dsq = nullptr) {
     CallShape s;
     if (call_shape(sc, a, ad, !COUNT, batch_edges, "psdr_hip_render_d_fwd", s)) return 1;
     SCRATCH_GUARD(sc, stream);
@@ -280,6 +281,8 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
     if (a->zero_output) {
         if (out) HIPCHK(hipMemsetAsync(out, 0, sizeof(float) * 3 * npx, st));
         if (dout) HIPCHK(hipMemsetAsync(dout, 0, sizeof(float) * 3 * npx, st));
+        if (sq) HIPCHK(hipMemsetAsync(sq, 0, sizeof(float) * 3 * npx, st));
+        if (dsq) HIPCHK(hipMemsetAsync(dsq, 0, sizeof(float) * 3 * npx, st));
     }
     Counters *ctr = (Counters *) sc->counters.p;
     if (COUNT) HIPCHK(hipMemsetAsync(ctr, 0, sizeof(Counters), st));
@@ -297,7 +300,8 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
     const bool fork = !no_fork && ad && !a->pix_ids && !lanes_out && !COUNT && T.n_tris > kBruteForceMax && ((terms & (PSDR_TERM_PRIMARY | PSDR_TERM_SECONDARY)) != 0) && (terms & (terms - 1)) != 0;
     // the lean path kernels: forward mode (this function), PathTracer, perspective sensor, no per-lane output - what they fix at compile time (paths.h::Switches)
     // (PSDR_NO_LEAN: measurement / test knob, read per call - the general kernels, which compute the same samples)
-    const bool lean = std::getenv("PSDR_NO_LEAN") == nullptr && a->direct_mode == 0 && a->field_mode == 0 && !lanes_out && !cam.ortho;
+    // (a call with the squares takes the general kernels: the lean ones have no second accumulation)
+    const bool lean = std::getenv("PSDR_NO_LEAN") == nullptr && a->direct_mode == 0 && a->field_mode == 0 && !lanes_out && !sq && !dsq && !cam.ortho;
     unsigned long long *q_int = nullptr, *q_prim = nullptr, *q_sec = nullptr;
     // concurrent launches must not share the global tail of the traversal stack (trav4.h indexes it by workgroup and thread only): the edge terms get slices of their own
     SceneTables T_prim = T, T_sec = T;
@@ -313,7 +317,7 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
     if ((terms & PSDR_TERM_INTERIOR) && T.spp > 0) {
         PathParams P = sampler_params<PathParams>(a, s, 0, npx * T.spp, a->pix_ids ? (long long) T.spp : (long long) T.width * T.spp);
         P.pix_ids = a->pix_ids;
-        P.out = out; P.dout = dout; P.lanes_out = lanes_out;
+        P.out = out; P.dout = dout; P.lanes_out = lanes_out; P.sq = sq; P.dsq = dsq;
         if (lanes_out) { P.begin = lane_b; P.end = lane_e; P.shard_rank = 0; P.shard_count = 1; P.n_local = local_lanes(P.end - P.begin, 0, 1); }
         if (P.n_local > 0) {
             if (fork) P.counter = q_int; else if (next_queue(sc, st, P.counter)) return 1;
@@ -336,7 +340,7 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
         }
         if (want_prim) {
             PathParams P = sampler_params<PathParams>(a, s, 1, npx_e * T.sppe, kBlock);
-            P.dout = edge_out;
+            P.dout = edge_out; P.dsq = dsq;
             P.skip_static = a->skip_static_edges;
             if (P.n_local > 0) {
                 if (fork) P.counter = q_prim; else if (next_queue(sc, st, P.counter)) return 1;
@@ -348,13 +352,15 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
         if (want_sec) {
             // (the term exists with field_mode == 0 only, where `cls` is the scene's own class: LDS blob, lean BVH, LDS blob with materials, global)
             PathParams P = sampler_params<PathParams>(a, s, 2, npx_e * T.sppse, kBlock);
-            P.dout = edge_out;
+            P.dout = edge_out; P.dsq = dsq;
             const GuidingDev G = a->guiding ? a->guiding->G : GuidingDev{};
             const int use_g = a->guiding ? 1 : 0;
             if (P.n_local > 0) {
                 if (fork) P.counter = q_sec; else if (next_queue(sc, st, P.counter)) return 1;
 #define K_SECONDARY(C) LAUNCH(C, (k_secondary_edges<C, CLS_COUNTED(C, COUNT), false>), sc, P.n_local, s_sec, sc->blob.as<float4>(), T_sec, sc->E, cam, P, G, use_g, ctr)
-                LAUNCH_CLS_FWD(cls, K_SECONDARY);
+#define K_SECONDARY_SQ(C) LAUNCH(C, (k_secondary_edges<C, false, false, true>), sc, P.n_local, s_sec, sc->blob.as<float4>(), T_sec, sc->E, cam, P, G, use_g, ctr)
+                if (dsq) LAUNCH_CLS_FWD(cls, K_SECONDARY_SQ); else LAUNCH_CLS_FWD(cls, K_SECONDARY);
+#undef K_SECONDARY_SQ
 #undef K_SECONDARY
             }
         }
@@ -390,6 +396,16 @@ int psdr_hip_render_d_fwd(const psdr_hip_scene *sc, const psdr_render_args *a, f
 int psdr_hip_render_d_fwd_batch(const psdr_hip_scene *sc, const psdr_render_args *a, float *out, float *dout, void *stream) {
     if (!out || !dout) return fail("null output");
     return render_impl<false>(sc, a, true, out, dout, nullptr, 0, 0, nullptr, stream, true);
+}
+int psdr_hip_render_c_sq(const psdr_hip_scene *sc, const psdr_render_args *a, float *out, float *out_sq, void *stream) {
+    if (!sc || !a) return fail("null argument");
+    if (!out || !out_sq) return fail("null output");
+    return render_impl<false>(sc, a, false, out, nullptr, nullptr, 0, 0, nullptr, stream, false, out_sq, nullptr);
+}
+int psdr_hip_render_d_fwd_sq(const psdr_hip_scene *sc, const psdr_render_args *a, float *out, float *dout, float *out_sq, float *out_dsq, void *stream) {
+    if (!sc || !a) return fail("null argument");
+    if (!out || !dout || !out_sq || !out_dsq) return fail("null output");
+    return render_impl<false>(sc, a, true, out, dout, nullptr, 0, 0, nullptr, stream, false, out_sq, out_dsq);
 }
 int psdr_hip_render_c_counted(const psdr_hip_scene *sc, const psdr_render_args *a, float *out, psdr_counters *c, void *stream) {
     if (!out) return fail("null output");

@@ -48,12 +48,15 @@ struct PathParams {
     // reverse mode - the row of g_prim the sample would add to is not wanted (psdr_grads.prim_edge_filter)
     int skip_static;
     const unsigned char *prim_filter;
+    // per-pixel sums of squared sample contributions (psdr_hip_render_c_sq / _d_fwd_sq; NULL = none): whatever a sample adds to out / dout, its square is added here at the
+    // same slot.  Last in the struct: the fields above keep their kernel-argument offsets
+    float *sq, *dsq;
 };
 
 // KERNEL VARIANTS (the last template parameter of k_paths / run_paths / run_paths_async).  A launch is one kind of call - forward or reverse mode, PathTracer or a
 // DirectIntegrator or a first-hit integrator, perspective or orthographic sensor, with or without the per-lane output - and the general kernel carries all of
 // them as launch-uniform run-time branches, whose operands are kernel arguments that stay live across the path loop.  The lean variant fixes the commonest call at
-// compile time: forward mode (adj_w == NULL; lds_acc and prim_filter unused), PathTracer (mis == -1, field < 0), lanes_out == NULL, perspective sensor.  The path
+// compile time: forward mode (adj_w == NULL; lds_acc and prim_filter unused), PathTracer (mis == -1, field < 0), lanes_out == NULL, sq == dsq == NULL, perspective sensor.  The path
 // code reads these switches through Switches<VAR> only, so one body serves both; skip_static, hide_emitters, max_depth, the shard and pix_ids stay run-time.
 // api.hip launches the lean kernel when the call qualifies (PSDR_NO_LEAN in the environment: never).
 constexpr int kGeneral = 0, kLean = 1;
@@ -62,6 +65,8 @@ template <int VAR> struct Switches {
     static PSDR_DEV const float *adj_w(const PathParams &P) { if constexpr (lean) return nullptr; else return P.adj_w; }
     static PSDR_DEV const unsigned char *prim_filter(const PathParams &P) { if constexpr (lean) return nullptr; else return P.prim_filter; }
     static PSDR_DEV float *lanes_out(const PathParams &P) { if constexpr (lean) return nullptr; else return P.lanes_out; }
+    static PSDR_DEV float *sq(const PathParams &P) { if constexpr (lean) return nullptr; else return P.sq; }
+    static PSDR_DEV float *dsq(const PathParams &P) { if constexpr (lean) return nullptr; else return P.dsq; }
     static PSDR_DEV int mis(const PathParams &P) { if constexpr (lean) return -1; else return P.mis; }
     template <typename View> static PSDR_DEV int field(const View &S) { if constexpr (lean) return -1; else return S.field; }
     static PSDR_DEV bool ortho(const SensorDev &cam) { if constexpr (lean) return false; else return cam.ortho != 0; }
@@ -363,10 +368,18 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                     for (int c = 0; c < 3; ++c) {             // NaN/Inf scrub, integrator.cpp:126
                         const bool okp = finite_(pv[c]);
                         const float v = okp ? pv[c] : 0.f;
-                        if (v != 0.f) atomicAdd(&P.out[3 * (long long) pix_slot + c], v * inv_spp);
+                        if (v != 0.f) {
+                            const float a = v * inv_spp;
+                            atomicAdd(&P.out[3 * (long long) pix_slot + c], a);
+                            if (sw::sq(P)) atomicAdd(&sw::sq(P)[3 * (long long) pix_slot + c], a * a);
+                        }
                         if (AD) {
                             const float d = (okp && finite_(tv[c])) ? tv[c] : 0.f;
-                            if (d != 0.f) atomicAdd(&P.dout[3 * (long long) pix_slot + c], d * inv_spp);
+                            if (d != 0.f) {
+                                const float b = d * inv_spp;
+                                atomicAdd(&P.dout[3 * (long long) pix_slot + c], b);
+                                if (sw::dsq(P)) atomicAdd(&sw::dsq(P)[3 * (long long) pix_slot + c], b * b);
+                            }
                         }
                     }
                 }
@@ -417,7 +430,10 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                             float dv = edge_xdn_d * o3[c];
                             if (!finite_(pv) || !finite_(dv)) dv = 0.f;
                             if (T.sppe > 1) dv /= (float) T.sppe;
-                            if (dv != 0.f) atomicAdd(&P.dout[3 * (long long) pix_slot + c], dv);
+                            if (dv != 0.f) {
+                                atomicAdd(&P.dout[3 * (long long) pix_slot + c], dv);
+                                if (sw::dsq(P)) atomicAdd(&sw::dsq(P)[3 * (long long) pix_slot + c], dv * dv);
+                            }
                         }
                     } else {
                         // adjoint: the tangent is d(x_dot_n) * o3 / sppe with d(x_dot_n) = n . ((1-s) d p0 + s d p1)
@@ -602,10 +618,18 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                         for (int c = 0; c < 3; ++c) {             // NaN/Inf scrub, integrator.cpp:126
                             const bool okp = finite_(pv[c]);
                             const float v = okp ? pv[c] : 0.f;
-                            if (v != 0.f) atomicAdd(&P.out[3 * (long long) pix_slot + c], v * inv_spp);
+                            if (v != 0.f) {
+                                const float a = v * inv_spp;
+                                atomicAdd(&P.out[3 * (long long) pix_slot + c], a);
+                                if (sw::sq(P)) atomicAdd(&sw::sq(P)[3 * (long long) pix_slot + c], a * a);
+                            }
                             if (AD) {
                                 const float d = (okp && finite_(tv[c])) ? tv[c] : 0.f;
-                                if (d != 0.f) atomicAdd(&P.dout[3 * (long long) pix_slot + c], d * inv_spp);
+                                if (d != 0.f) {
+                                    const float b = d * inv_spp;
+                                    atomicAdd(&P.dout[3 * (long long) pix_slot + c], b);
+                                    if (sw::dsq(P)) atomicAdd(&sw::dsq(P)[3 * (long long) pix_slot + c], b * b);
+                                }
                             }
                         }
                     }
@@ -632,7 +656,10 @@ PSDR_DEV void run_paths_async(SceneView<LDS> &S, const SensorDev &cam, const Pat
                                 float dv = edge_xdn_d * o3[c];
                                 if (!finite_(pv) || !finite_(dv)) dv = 0.f;
                                 if (T.sppe > 1) dv /= (float) T.sppe;
-                                if (dv != 0.f) atomicAdd(&P.dout[3 * (long long) pix_slot + c], dv);
+                                if (dv != 0.f) {
+                                    atomicAdd(&P.dout[3 * (long long) pix_slot + c], dv);
+                                    if (sw::dsq(P)) atomicAdd(&sw::dsq(P)[3 * (long long) pix_slot + c], dv * dv);
+                                }
                             }
                         } else {
                             float kw = 0.f;

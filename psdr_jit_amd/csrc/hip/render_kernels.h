@@ -186,11 +186,14 @@ PSDR_DEV float guiding_sample_reuse(const GuidingDev &G, Vec3f &s) {
 #ifndef PSDR_SEC_WAVES
 #define PSDR_SEC_WAVES 4
 #endif
-template <int LDS, bool COUNT, bool ADJ>
+// SQ (forward mode, uncounted): a sample's square goes to P.dsq where the sample goes to P.dout (psdr_hip_render_d_fwd_sq).  A compile-time switch, so the plain
+// instantiations are the code they were (their names gain the fourth argument)
+template <int LDS, bool COUNT, bool ADJ, bool SQ = false>
 __global__ __launch_bounds__(kBlock, (ADJ ? PSDR_SEC_ADJ_WAVES : PSDR_SEC_WAVES)) void k_secondary_edges(
                                                             const float4 *__restrict__ blob, const SceneTables T, const SecEdgeTables E,
                                                             const SensorDev cam, const PathParams P, const GuidingDev G, const int use_guiding,
                                                             Counters *ctr) {
+    static_assert(!(SQ && (ADJ || COUNT)), "the squares exist in forward mode, uncounted");
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneView<LDS> S = make_view<LDS>(blob, T, smem);
     const int lane_id = threadIdx.x & 63;
@@ -391,7 +394,10 @@ __global__ __launch_bounds__(kBlock, (ADJ ? PSDR_SEC_ADJ_WAVES : PSDR_SEC_WAVES)
                         for (int c = 0; c < 3; ++c) {
                             if (pdf0 > kEpsilon) o[c] /= pdf0;
                             if (T.sppse > 1) o[c] /= (float) T.sppse;
-                            if (finite_(o[c]) && o[c] != 0.f) atomicAdd(&P.dout[3 * (long long) idx + c], o[c]);
+                            if (finite_(o[c]) && o[c] != 0.f) {
+                                atomicAdd(&P.dout[3 * (long long) idx + c], o[c]);
+                                if constexpr (SQ) atomicAdd(&P.dsq[3 * (long long) idx + c], o[c] * o[c]);
+                            }
                         }
                     }
                 }
@@ -521,7 +527,10 @@ __global__ __launch_bounds__(kBlock, (ADJ ? PSDR_SEC_ADJ_WAVES : PSDR_SEC_WAVES)
                 for (int c = 0; c < 3; ++c) {
                     if (pdf0 > kEpsilon) o[c] /= pdf0;
                     if (T.sppse > 1) o[c] /= (float) T.sppse;
-                    if (finite_(o[c]) && o[c] != 0.f) atomicAdd(&P.dout[3 * (long long) idx + c], o[c]);
+                    if (finite_(o[c]) && o[c] != 0.f) {
+                        atomicAdd(&P.dout[3 * (long long) idx + c], o[c]);
+                        if constexpr (SQ) atomicAdd(&P.dsq[3 * (long long) idx + c], o[c] * o[c]);
+                    }
                 }
             }
             have = false;
@@ -772,17 +781,19 @@ __global__ __launch_bounds__(kBlock) void k_intersect_adj(const float4 *__restri
 #define PSDR_INST_LEAN3(PFX, C_) PSDR_INST_PATHS_V(PFX, true, C_, false, 0, kLean) PSDR_INST_PATHS_V(PFX, false, C_, false, 0, kLean) PSDR_INST_PATHS_V(PFX, false, C_, false, 1, kLean)
 #define PSDR_INST_ADJ(PFX, C_) PFX template __global__ void k_interior_adjoint<C_>(const float4 *, const SceneTables, const SensorDev, const AdjointParams);
 #define PSDR_INST_ADJM(PFX, C_) PFX template __global__ void k_interior_adjoint_mat<C_>(const float4 *, const SceneTables, const SensorDev, const AdjointParams);
-#define PSDR_INST_SEC(PFX, C_, CNT_, ADJ_) PFX template __global__ void k_secondary_edges<C_, CNT_, ADJ_>(const float4 *, const SceneTables, const SecEdgeTables, const SensorDev, const PathParams, const GuidingDev, const int, Counters *);
+#define PSDR_INST_SEC(PFX, C_, CNT_, ADJ_) PFX template __global__ void k_secondary_edges<C_, CNT_, ADJ_, false>(const float4 *, const SceneTables, const SecEdgeTables, const SensorDev, const PathParams, const GuidingDev, const int, Counters *);
+#define PSDR_INST_SEC_SQ(PFX, C_) PFX template __global__ void k_secondary_edges<C_, false, false, true>(const float4 *, const SceneTables, const SecEdgeTables, const SensorDev, const PathParams, const GuidingDev, const int, Counters *);
 #define PSDR_INST_PATHS6(PFX, C_) PSDR_INST_PATHS(PFX, true, C_, false, 0) PSDR_INST_PATHS(PFX, false, C_, false, 0) PSDR_INST_PATHS(PFX, false, C_, false, 1) \
                                   PSDR_INST_PATHS(PFX, true, C_, true, 0) PSDR_INST_PATHS(PFX, false, C_, true, 0) PSDR_INST_PATHS(PFX, false, C_, true, 1)
 #define PSDR_TU1(PFX) PSDR_INST_PATHS(PFX, true, 0, false, 0) PSDR_INST_PATHS(PFX, false, 0, false, 0) PSDR_INST_PATHS(PFX, false, 0, false, 1)
-#define PSDR_TU6(PFX) PSDR_INST_PATHS(PFX, true, 0, true, 0) PSDR_INST_PATHS(PFX, false, 0, true, 0) PSDR_INST_PATHS(PFX, false, 0, true, 1)
+#define PSDR_TU6(PFX) PSDR_INST_PATHS(PFX, true, 0, true, 0) PSDR_INST_PATHS(PFX, false, 0, true, 0) PSDR_INST_PATHS(PFX, false, 0, true, 1) PSDR_INST_SEC_SQ(PFX, 0)
 #define PSDR_TU2(PFX) PSDR_INST_ADJ(PFX, 0) PSDR_INST_SEC(PFX, 0, false, false) PSDR_INST_SEC(PFX, 0, true, false) PSDR_INST_SEC(PFX, 0, false, true)
 #define PSDR_TU8(PFX) PSDR_INST_ADJM(PFX, 0)         // the material sweep, a unit of its own for the same reason as PSDR_TU7: its not-inlined bsdf_back lambda shows the allocator defect
 #define PSDR_TU3(PFX) PSDR_INST_PATHS6(PFX, 1) PSDR_INST_ADJ(PFX, 1) PSDR_INST_SEC(PFX, 1, false, false) PSDR_INST_SEC(PFX, 1, true, false) PSDR_INST_SEC(PFX, 1, false, true)
 #define PSDR_TU4(PFX) PSDR_INST_PATHS6(PFX, 2) PSDR_INST_SEC(PFX, 2, false, false) PSDR_INST_SEC(PFX, 2, true, false) PSDR_INST_SEC(PFX, 2, false, true)
 #define PSDR_TU7(PFX) PSDR_INST_ADJ(PFX, 2)          // a unit of its own: when the ISA lint sends it to the second allocator (build.py), the class-2 path kernels do not pay for it
 // the lean path kernels (paths.h::Switches) of the classes that have them: 1 (the Cornell boxes) and 2 (BVH scenes), the uncounted instantiations
-#define PSDR_TU9(PFX) PSDR_INST_LEAN3(PFX, 1)
-#define PSDR_TU10(PFX) PSDR_INST_LEAN3(PFX, 2)
-#define PSDR_TU5(PFX) PSDR_INST_PATHS(PFX, true, 3, false, 0) PSDR_INST_PATHS(PFX, false, 3, false, 0) PSDR_INST_PATHS(PFX, false, 3, false, 1) PSDR_INST_SEC(PFX, 3, false, false)
+// (the secondary-edge kernel with the squares, k_secondary_edges<C, false, false, true>, rides in the shortest unit of each class: 6, 9, 10 and 5)
+#define PSDR_TU9(PFX) PSDR_INST_LEAN3(PFX, 1) PSDR_INST_SEC_SQ(PFX, 1)
+#define PSDR_TU10(PFX) PSDR_INST_LEAN3(PFX, 2) PSDR_INST_SEC_SQ(PFX, 2)
+#define PSDR_TU5(PFX) PSDR_INST_PATHS(PFX, true, 3, false, 0) PSDR_INST_PATHS(PFX, false, 3, false, 0) PSDR_INST_PATHS(PFX, false, 3, false, 1) PSDR_INST_SEC(PFX, 3, false, false) PSDR_INST_SEC_SQ(PFX, 3)

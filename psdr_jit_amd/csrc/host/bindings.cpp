@@ -527,9 +527,9 @@ PYBIND11_MODULE(_psdr_core, m) {
 
     py::class_<Integrator, Object>(m, "Integrator", py::dynamic_attr())
         .def("_renderC", &Integrator::renderC, "scene"_a, "sensor_id"_a, "seed"_a, "pix_ids"_a, "n_pix"_a, "out"_a, "stream"_a, "shard_rank"_a, "shard_count"_a,
-             py::call_guard<py::gil_scoped_release>())
+             "sq"_a = 0, py::call_guard<py::gil_scoped_release>())
         .def("_renderD", &Integrator::renderD, "scene"_a, "sensor_id"_a, "seed"_a, "pix_ids"_a, "n_pix"_a, "out"_a, "dout"_a, "stream"_a, "shard_rank"_a,
-             "shard_count"_a, "terms"_a, "batch_edges"_a = false, py::call_guard<py::gil_scoped_release>())
+             "shard_count"_a, "terms"_a, "batch_edges"_a = false, "sq"_a = 0, "dsq"_a = 0, py::call_guard<py::gil_scoped_release>())
         .def_readwrite("trace_static_edges", &Integrator::m_trace_static_edges)
         .def_readwrite("_shard_mode", &Integrator::m_shard_mode);
 

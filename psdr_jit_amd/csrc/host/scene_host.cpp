@@ -1564,7 +1564,7 @@ static void fill_args(psdr_render_args &a, const Scene &scene, const Integrator 
     a.shard_mode = it.m_shard_mode;
 }
 
-void Integrator::renderC(const Scene &scene, int sensor_id, int seed, uintptr_t pix_ids, int n_pix, uintptr_t out, uintptr_t stream, int rank, int count) const {
+void Integrator::renderC(const Scene &scene, int sensor_id, int seed, uintptr_t pix_ids, int n_pix, uintptr_t out, uintptr_t stream, int rank, int count, uintptr_t sq) const {
     using namespace std::chrono;
     const auto start_time = high_resolution_clock::now();
     const RenderOption &opts = scene.m_opts;
@@ -1576,7 +1576,8 @@ void Integrator::renderC(const Scene &scene, int sensor_id, int seed, uintptr_t 
     if (seed != -1) scene.m_samplers[0] = SamplerState{true, npx * opts.spp, (uint64_t) (int64_t) seed, 0};
     psdr_render_args a;
     fill_args(a, scene, *this, sensor_id, pix_ids, n_pix, rank, count);
-    hip_check(psdr_hip_render_c(scene.m_hip, &a, reinterpret_cast<float *>(out), reinterpret_cast<void *>(stream)));
+    if (sq) hip_check(psdr_hip_render_c_sq(scene.m_hip, &a, reinterpret_cast<float *>(out), reinterpret_cast<float *>(sq), reinterpret_cast<void *>(stream)));
+    else hip_check(psdr_hip_render_c(scene.m_hip, &a, reinterpret_cast<float *>(out), reinterpret_cast<void *>(stream)));
     if (opts.spp > 0) scene.m_samplers[0].skip += 2 + (uint64_t) draws_per_level() * (uint64_t) max_depth();
     if (opts.log_level) {
         std::ostringstream oss;
@@ -1586,7 +1587,7 @@ void Integrator::renderC(const Scene &scene, int sensor_id, int seed, uintptr_t 
 }
 
 void Integrator::renderD(const Scene &scene, int sensor_id, int seed, uintptr_t pix_ids, int n_pix, uintptr_t out, uintptr_t dout, uintptr_t stream,
-                         int rank, int count, int terms, bool batch_edges) const {
+                         int rank, int count, int terms, bool batch_edges, uintptr_t sq, uintptr_t dsq) const {
     using namespace std::chrono;
     const auto start_time = high_resolution_clock::now();
     const RenderOption &opts = scene.m_opts;
@@ -1594,6 +1595,7 @@ void Integrator::renderD(const Scene &scene, int sensor_id, int seed, uintptr_t 
     PSDR_ASSERT_MSG(scene.is_ready(), "Input scene must be configured!");
     PSDR_ASSERT_MSG(sensor_id >= 0 && sensor_id < scene.m_num_sensors, "Invalid sensor id!");
     PSDR_ASSERT_MSG(!(batch_edges && pix_ids == 0), "batch_edges needs batch_pix: the full frame always has its edge terms");
+    PSDR_ASSERT_MSG((sq != 0) == (dsq != 0) && !(sq != 0 && batch_edges), "the sample squares come as a pair and do not exist with batch_edges");
     const int64_t num_pixels = (int64_t) opts.height * opts.width;
     const int64_t npx = pix_ids ? n_pix : num_pixels;
     if (seed != -1) {
@@ -1611,7 +1613,9 @@ void Integrator::renderD(const Scene &scene, int sensor_id, int seed, uintptr_t 
     if (field() >= 0) terms &= ~PSDR_TERM_SECONDARY;         // Integrator::render_secondary_edges is a no-op for the first-hit integrators
     a.terms = launch & terms;
     // batch_edges: the full-frame edge samples that land on a listed pixel are kept (psdr_hip_render_d_fwd_batch); without it a pixel list has the interior term only
-    if (a.terms)
+    if (a.terms && sq)
+        hip_check(psdr_hip_render_d_fwd_sq(scene.m_hip, &a, reinterpret_cast<float *>(out), reinterpret_cast<float *>(dout), reinterpret_cast<float *>(sq), reinterpret_cast<float *>(dsq), reinterpret_cast<void *>(stream)));
+    else if (a.terms)
         hip_check((batch_edges ? psdr_hip_render_d_fwd_batch : psdr_hip_render_d_fwd)(scene.m_hip, &a, reinterpret_cast<float *>(out), reinterpret_cast<float *>(dout), reinterpret_cast<void *>(stream)));
     const PerspectiveCamera *cam = static_cast<const PerspectiveCamera *>(scene.m_sensors[sensor_id]);
     if (opts.spp > 0 && (terms & PSDR_TERM_INTERIOR)) scene.m_samplers[0].skip += 2 + (uint64_t) draws_per_level() * (uint64_t) max_depth();

@@ -382,10 +382,11 @@ private:
 
 struct Integrator : Object {
     // out / dout / pix_ids are DEVICE pointers (uintptr_t from the caller's tensors), stream a hipStream_t
+    // sq / dsq (0 = none): the per-pixel sums of squared sample contributions, rows as out / dout (psdr_hip_render_c_sq / psdr_hip_render_d_fwd_sq)
     void renderC(const Scene &scene, int sensor_id, int seed, uintptr_t pix_ids, int n_pix, uintptr_t out, uintptr_t stream,
-                 int shard_rank, int shard_count) const;
+                 int shard_rank, int shard_count, uintptr_t sq = 0) const;
     void renderD(const Scene &scene, int sensor_id, int seed, uintptr_t pix_ids, int n_pix, uintptr_t out, uintptr_t dout, uintptr_t stream,
-                 int shard_rank, int shard_count, int terms, bool batch_edges = false) const;
+                 int shard_rank, int shard_count, int terms, bool batch_edges = false, uintptr_t sq = 0, uintptr_t dsq = 0) const;
     virtual int max_depth() const = 0;
     virtual bool hide_emitters() const = 0;
     virtual const psdr_hip_guiding *guiding(int sensor_id) const { (void) sensor_id; return nullptr; }

@@ -100,7 +100,7 @@ def bench_name(k):
     m = re.match(r"k_paths<(\w+), (\d+), (\w+), (\d+)(?:, \d+)?>", k)       # (the fifth argument: the variant, paths.h::Switches - 0 general, 1 lean)
     if m and m.group(3) == "false":
         return "k_primary_edges" if m.group(4) == "1" else ("k_interior<AD>" if m.group(1) == "true" else "k_interior")
-    m = re.match(r"k_secondary_edges<(\d+), (\w+), (\w+)>", k)
+    m = re.match(r"k_secondary_edges<(\d+), (\w+), (\w+)(?:, false)?>", k)    # (the fourth argument: with the sample squares - not a kernel bench.py names)
     if m and m.group(2) == "false" and m.group(3) == "false":
         return "k_secondary_edges"
     return None
