@@ -515,6 +515,35 @@ int psdr_hip_precond_apply(const psdr_hip_precond *precond, const float *x, floa
  * (alpha = beta = 0) for the rest of the solve; a zero column of b gives exactly zero.  The handle holds the work arrays: one solve at a time per handle. */
 int psdr_hip_precond_solve(psdr_hip_precond *precond, const float *b, float *x, float rtol, int32_t max_iter, psdr_precond_info *info, void *stream);
 
+/* ADAPTIVE SAMPLING (csrc/hip/adaptive.hip; psdr_jit_amd/adaptive.py): a per-pixel weight map becomes a pixel list that spends an exact sample budget -
+ * the list the batch entry points take, duplicates and all - and the rows of that list are folded back into a frame.  Device pointers throughout, plain launches on `stream`,
+ * no synchronisation, no float atomics (the same input gives the same bits).  Every call checks its arguments BEFORE any device call and returns non-zero with
+ * psdr_hip_last_error text for a NULL pointer or a value out of range.  Added under ABI 16 like the batch entry points: nothing existing changed.
+ *
+ * counts: w_i = weights[i] if finite and > 0, else 0; wmax = max w_i; q_i = (uint32) floor((double) w_i / (double) wmax * 2^bits), every q_i = 1 if wmax == 0;
+ * C = the exclusive prefix sum of q in uint64 (n + 1 positions), S = C_n; B' = budget - n * min_count;
+ *     counts[i] = min_count + floor(B' C_{i+1} / S) - floor(B' C_i / S),      offsets[i] = i * min_count + floor(B' C_i / S),  offsets[n] = budget
+ * so the counts add up to budget exactly and each is within one of its share min_count + B' q_i / S.  bits = min(20, 62 - ceil_log2(n) - ceil_log2(max(budget, 1)))
+ * (the value the bits call returns, -1 for n <= 0 or budget < 0) keeps B' S below 2^62; the call refuses n outside [1, 2^24], budget outside [n * min_count, 2^31 - 1],
+ * min_count < 0 and bits < 8.  scratch: a device buffer of at least the scratch_bytes call's size, the call's own between its launches. */
+int64_t psdr_hip_adaptive_scratch_bytes(void);
+int psdr_hip_adaptive_bits(int32_t n, int64_t budget);
+int psdr_hip_adaptive_counts(const float *weights, int32_t n, int64_t budget, int32_t min_count, int32_t *counts, int32_t *offsets, void *scratch, void *stream);
+/* pix_ids[k] = the pixel p with offsets[p] <= k < offsets[p + 1], for k in [0, total): the list sorted by pixel.  total = offsets[n] (the budget: the host knows it);
+ * total == 0 writes nothing and accepts pix_ids == NULL */
+int psdr_hip_adaptive_expand(const int32_t *offsets, int32_t n, int64_t total, int32_t *pix_ids, void *stream);
+/* The segment fold.  rows is [total, channels], row k belongs to pixel p(k) and averages rows_n samples; base is an earlier frame [n, channels] that averaged base_n samples
+ * per pixel, or NULL with base_n = 0.  With c_p = offsets[p + 1] - offsets[p] and n_tot = base_n + rows_n c_p:
+ *     square = 0:  out[p] = (base_n base[p] + rows_n sum_k rows[k]) / n_tot                      the combined mean
+ *     square = 1:  out[p] = (base_n / n_tot)^2 base[p] + (rows_n / n_tot)^2 sum_k rows[k]        the same estimator's sum of squared sample contributions
+ * and 0 where n_tot = 0.  One wave per pixel adds its segment in a fixed order in float32; the rest of the formula is evaluated in double and rounded once.
+ * channels in [1, 4]; rows_n > 0; base_n >= 0. */
+int psdr_hip_adaptive_merge(const int32_t *offsets, int32_t n, int64_t total, int32_t channels, const float *rows, float rows_n, const float *base, float base_n,
+                            int32_t square, float *out, void *stream);
+/* the transpose of the square = 0 fold: d_rows[k] = d_out[p(k)] rows_n / n_tot (a gather, one thread per row), d_base[p] = d_out[p] base_n / n_tot (d_base may be NULL) */
+int psdr_hip_adaptive_merge_adj(const int32_t *offsets, int32_t n, int64_t total, int32_t channels, const float *d_out, float rows_n, float base_n, float *d_rows,
+                                float *d_base, void *stream);
+
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);
 int psdr_hip_sampler_floats(uint64_t seed_value, uint64_t lane, uint64_t skip, int32_t n, float *out_dev, void *stream);

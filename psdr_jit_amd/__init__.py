@@ -1639,3 +1639,5 @@ def samples_behind(scene, term):
 
 # the Laplacian vertex preconditioner and its optimiser (precond.py; kernels: csrc/hip/precond.hip)
 from .precond import laplacian_csr, LaplacianPreconditioner, AdamUniform  # noqa: E402,F401
+# adaptive sampling: a sample budget placed by the noise estimate of render_c_sq (adaptive.py; kernels: csrc/hip/adaptive.hip)
+from .adaptive import adaptive_weights, PixelPlan, render_c_adaptive  # noqa: E402,F401
