@@ -13,23 +13,12 @@
 // separate adjoint derivation exists that could disagree with the forward-mode code the parity tests pin.
 // Cost: ~(22 x touched triangles + 3 x touched BSDFs + 3) shading replays per path.
 #pragma once
+#include "adj_layout.h"
 #include "paths.h"
 
 namespace psdr {
 
-// per-lane LDS records of one path, sized from the path depth D by the launch: 1 + 2 D hits of 4 words, 2 D light-sample slots,
-// 4 D + 4 lookups of 3 words (per vertex: the BSDF's bitmaps and, under a normal map, the nested BSDF's; per bounce: two environment lookups)
-inline __host__ __device__ int adj_hit_words(int depth) { return 4 * (1 + 2 * depth); }
-inline __host__ __device__ int adj_ext_words(int depth) { return 2 * depth > 2 ? 2 * depth : 2; }
-inline __host__ __device__ int adj_lk_entries(int depth) { return 4 * depth + 4; }
-// LDS words per lane of the interior adjoint kernel: scenes without bitmap / per-vertex parameters and without an environment map
-// make no lookups, carry no lookup record and keep more workgroups per CU (AdjointParams::lk_words)
-// the reverse sweep keeps, per lane: 3 words per vertex (slot, u, v) and 11 per bounce (light sample, shadow hit, constants, throughput)
-inline __host__ __device__ int adj_sweep_words(int depth) { return 3 * (depth + 1) + 11 * (depth > 0 ? depth : 1); }
-inline __host__ __device__ int adj_lane_words(int depth, bool with_lookups) { return adj_hit_words(depth) + adj_ext_words(depth) + (with_lookups ? 3 * adj_lk_entries(depth) : 0); }
-// the secondary-edge adjoint records three hits per lane, followed by 16 floats of camera-pose accumulators
-constexpr int kSecAdjLaneWords = 12;
-constexpr int kSecAdjScratch = kSecAdjLaneWords * kBlock + 16;
+static_assert(kAdjBlock == kBlock, "adj_layout.h sizes the LDS for workgroups of kBlock lanes");
 
 struct AdjointParams {
     int max_depth, hide_emitters;
@@ -67,10 +56,6 @@ struct AdjointParams {
                                     //   (paths too deep for 160 KB of LDS: any depth works, at global-memory latency)
 };
 
-constexpr int kMatOut = 16;         // a BSDF's row of psdr_grads.g_mat
-constexpr int kMatRow = 28;         // ... and of its LDS accumulator when uv transforms are differentiated: the g_mat row, then [rot, scale, tx, ty] of its three bitmaps (g_uv_xf);
-                                    // without g_uv_xf the accumulator's row is the g_mat row alone (`mrow` in the kernels, api.hip::render_bwd_impl, the LDS sizes)
-constexpr int kAdjMisc = 32;        // LDS accumulators every path adds to: camera pose, environment scale and transform
 // number of constant material parameters a BSDF record's flags announce (Microfacet 4 - fewer with maps -, RoughConductor 11, RoughDielectric 3)
 PSDR_DEV int mat_param_count(int fl) { return (fl & 4) ? 4 : ((fl & 8) ? 11 : ((fl & 16) ? 3 : 0)); }
 
@@ -80,28 +65,60 @@ PSDR_DEV void adj_add(float *lds_g, float *glob, int idx, float v, bool use_lds)
     if (use_lds) atomicAdd(&lds_g[idx], v); else atomicAdd(&glob[idx], v);
 }
 
+// The LDS of an interior-adjoint workgroup behind the traversal rows (adj_layout.h): the per-lane records - or their rows in the global array -, then the accumulators.
+struct AdjAcc { float *recs, *cam, *mat, *tri, *bsdf, *emit, *env; };
+PSDR_DEV AdjLdsLayout adj_layout_of(const SceneTables &T, const AdjointParams &P) {
+    return adj_lds_layout(P.rec_global ? 0 : P.hit_words + P.ext_words + P.lk_words, T.n_bsdfs, adj_mat_row(P.g_uv_xf != nullptr), P.n_hot, T.n_emitters, P.env_lds);
+}
+// the pointers into `scratch` by the layout; rec_global != NULL: the records of this workgroup are `lane_words` rows of that array
+PSDR_DEV AdjAcc adj_pointers(float *scratch, const AdjLdsLayout L, float *rec_global, int lane_words) {
+    AdjAcc A;
+    A.recs = rec_global ? rec_global + (size_t) blockIdx.x * (size_t) lane_words * kBlock : scratch + L.rec;
+    A.cam = scratch + L.misc; A.mat = scratch + L.mat; A.tri = scratch + L.hot; A.bsdf = scratch + L.bsdf; A.emit = scratch + L.emit; A.env = scratch + L.env;
+    return A;
+}
+// ... at the start of a kernel, with every accumulator zeroed
+PSDR_DEV AdjAcc adj_carve(float *scratch, const AdjLdsLayout L, float *rec_global, int lane_words) {
+    for (int i = L.misc + threadIdx.x; i < L.total; i += kBlock) scratch[i] = 0.f;
+    __syncthreads();
+    return adj_pointers(scratch, L, rec_global, lane_words);
+}
+// ... and at its end: the workgroup's accumulators go to the caller's buffers, each guarded by its own pointer (the layout is taken from the launch parameters again:
+// nothing of it has to live through the main loop)
+PSDR_DEV void adj_flush(float *scratch, const SceneTables &T, const AdjointParams &P) {
+    __syncthreads();
+    const AdjLdsLayout L = adj_layout_of(T, P);
+    const AdjAcc A = adj_pointers(scratch, L, P.rec_global, 0);
+    const int t = threadIdx.x;
+    if (P.g_cam != nullptr && t < 12 && A.cam[kAdjCam + t] != 0.f) atomicAdd(&P.g_cam[t], A.cam[kAdjCam + t]);
+    if (P.g_env_scale != nullptr && t == 0 && A.cam[kAdjEnvScale] != 0.f) atomicAdd(P.g_env_scale, A.cam[kAdjEnvScale]);
+    if (P.g_env_xf != nullptr && t < 11 && A.cam[kAdjEnvXf + t] != 0.f) atomicAdd(&P.g_env_xf[t], A.cam[kAdjEnvXf + t]);
+    if (P.g_mat != nullptr)
+        for (int i = t; i < T.n_bsdfs * kMatOut; i += kBlock) { const float v = A.mat[(i / kMatOut) * L.mat_row + i % kMatOut]; if (v != 0.f) atomicAdd(&P.g_mat[i], v); }
+    if (P.g_uv_xf != nullptr) {          // uv transforms: three bitmaps per BSDF, then the environment map's
+        for (int i = t; i < T.n_bsdfs * 12; i += kBlock) { const float v = A.mat[(i / 12) * L.mat_row + kMatOut + i % 12]; if (v != 0.f) atomicAdd(&P.g_uv_xf[i], v); }
+        if (t < 4 && A.cam[kAdjEnvUv + t] != 0.f) atomicAdd(&P.g_uv_xf[12 * T.n_bsdfs + t], A.cam[kAdjEnvUv + t]);
+    }
+    for (int i = t; i < P.n_hot * kAdjTriRow; i += kBlock) if (A.tri[i] != 0.f) atomicAdd(&P.g_tri[P.hot_inv[i / kAdjTriRow] * kAdjTriRow + i % kAdjTriRow], A.tri[i]);
+    for (int i = t; i < T.n_bsdfs * 3; i += kBlock) if (A.bsdf[i] != 0.f) atomicAdd(&P.g_bsdf[i], A.bsdf[i]);
+    for (int i = t; i < T.n_emitters * 3; i += kBlock) if (A.emit[i] != 0.f) atomicAdd(&P.g_emitter[i], A.emit[i]);
+    for (int i = t; i < P.env_lds; i += kBlock) if (A.env[i] != 0.f) atomicAdd(&P.g_env[i], A.env[i]);
+}
+
 // scratch: per-block LDS region behind the blob/stack: [hits: hit_words x 256][ext: ext_words x 256][lookups: lk_words x 256][accumulators]
 template <int LDS>
 PSDR_DEV void run_interior_adjoint(SceneView<LDS> &S, const SensorDev &cam, const AdjointParams &P, float *scratch) {
     const SceneTables &T = *S.T;
-    const int mrow = S.uv_adj ? kMatRow : kMatOut;                     // LDS row of a BSDF's material adjoints (kMatRow)
     const int lane_id = threadIdx.x & 63;
     const unsigned long long lt_mask = (1ull << lane_id) - 1ull;
     const float inv_spp = T.spp > 1 ? 1.f / (float) T.spp : 1.f;
-    float *recs = P.rec_global ? P.rec_global + (size_t) blockIdx.x * (size_t) (P.hit_words + P.ext_words + P.lk_words) * kBlock : scratch;
-    float *rec = recs + threadIdx.x;
-    int *ext = reinterpret_cast<int *>(recs + P.hit_words * kBlock) + threadIdx.x;
-    float *lk = recs + (P.hit_words + P.ext_words) * kBlock + threadIdx.x;
-    float *acc_cam = P.rec_global ? scratch : scratch + (P.hit_words + P.ext_words + P.lk_words) * kBlock;        // 16 floats, always in LDS: every path adds to the same 12 entries
-    float *acc_mat = acc_cam + kAdjMisc;                               // [n_bsdfs * mrow], always in LDS like the camera block
-    float *acc = acc_mat + T.n_bsdfs * mrow;
-    const int n_acc = P.n_hot * 22 + T.n_bsdfs * 3 + T.n_emitters * 3;
-    const bool use_lds = true;                                         // colours and emitters always accumulate in LDS
-    for (int i = threadIdx.x; i < n_acc; i += kBlock) acc[i] = 0.f;
-    float *acc_bsdf = acc + P.n_hot * 22, *acc_emit = acc_bsdf + T.n_bsdfs * 3;
-    if (threadIdx.x < kAdjMisc) acc_cam[threadIdx.x] = 0.f;    // [0..11] camera pose, [12] environment-map scale, [16..26] environment from_world, [28..31] the map's uv transform
-    for (int i = threadIdx.x; i < T.n_bsdfs * mrow; i += kBlock) acc_mat[i] = 0.f;
-    __syncthreads();
+    const AdjLdsLayout L = adj_layout_of(T, P);
+    const AdjAcc A = adj_carve(scratch, L, P.rec_global, P.hit_words + P.ext_words + P.lk_words);
+    const int mrow = L.mat_row;
+    float *rec = A.recs + threadIdx.x;
+    int *ext = reinterpret_cast<int *>(A.recs + P.hit_words * kBlock) + threadIdx.x;
+    float *lk = A.recs + (P.hit_words + P.ext_words) * kBlock + threadIdx.x;
+    float *acc_cam = A.cam, *acc_mat = A.mat, *acc = A.tri, *acc_bsdf = A.bsdf, *acc_emit = A.emit;
     S.rec = rec; S.ext = ext; S.lk = lk; S.ext_max = P.ext_words; S.lk_max = P.lk_words / 3;
 
     long long q_next = 0, q_end = 0;
@@ -291,10 +308,10 @@ PSDR_DEV void run_interior_adjoint(SceneView<LDS> &S, const SensorDev &cam, cons
                             else adj_add<LDS>(acc, P.g_tri, st_orig * 22 + st_comp, gval, false);
                         }
                         else if (st_stage == 1 && bc >= 3) adj_add<LDS>(acc_mat, acc_mat, st_id * mrow + bc - 3, gval, true);
-                        else if (st_stage == 1) adj_add<LDS>(acc_bsdf, P.g_bsdf, st_id * 3 + bc, gval, use_lds);
-                        else if (st_stage == 2) adj_add<LDS>(acc_emit, P.g_emitter, st_id * 3 + st_comp, gval, use_lds);
-                        else if (st_stage == 4) { adj_add<LDS>(acc_cam, acc_cam, st_comp, gval, true); ray_p = ray; }
-                        else if (st_stage == 5) adj_add<LDS>(acc_cam, acc_cam, 16 + st_comp, gval, true);
+                        else if (st_stage == 1) adj_add<LDS>(acc_bsdf, P.g_bsdf, st_id * 3 + bc, gval, true);
+                        else if (st_stage == 2) adj_add<LDS>(acc_emit, P.g_emitter, st_id * 3 + st_comp, gval, true);
+                        else if (st_stage == 4) { adj_add<LDS>(acc_cam, acc_cam, kAdjCam + st_comp, gval, true); ray_p = ray; }
+                        else if (st_stage == 5) adj_add<LDS>(acc_cam, acc_cam, kAdjEnvXf + st_comp, gval, true);
                         else if (st_stage == 6) {
                             // transpose of the blend n0 (1 - u - v) + n1 u + n2 v at this hit's barycentrics
                             const float bu = rec[(4 * st_i + 1) * kBlock], bv = rec[(4 * st_i + 2) * kBlock];
@@ -320,8 +337,8 @@ PSDR_DEV void run_interior_adjoint(SceneView<LDS> &S, const SensorDev &cam, cons
                                         atomicAdd(&P.g_env[3ll * idx[k] + st_comp], gval * wt[k]);
                                         rgb_c += wt[k] * E.radiance[3ll * idx[k] + st_comp];
                                     }
-                                    if (P.g_env_scale != nullptr && E.scale != 0.f) atomicAdd(&acc_cam[12], gval * rgb_c / E.scale);
-                                    if (P.g_uv_xf != nullptr) { float ob[3] = {0.f, 0.f, 0.f}; ob[st_comp] = gval; env_xf_adjoint(E, S.probe_u, S.probe_v, ob, &acc_cam[28]); }
+                                    if (P.g_env_scale != nullptr && E.scale != 0.f) atomicAdd(&acc_cam[kAdjEnvScale], gval * rgb_c / E.scale);
+                                    if (P.g_uv_xf != nullptr) { float ob[3] = {0.f, 0.f, 0.f}; ob[st_comp] = gval; env_xf_adjoint(E, S.probe_u, S.probe_v, ob, &acc_cam[kAdjEnvUv]); }
                                 }
                             } else if (!has_mat(LDS)) {
                             } else if (st_id <= kPvLookup) {
@@ -359,22 +376,7 @@ PSDR_DEV void run_interior_adjoint(SceneView<LDS> &S, const SensorDev &cam, cons
             have = false;
         }
     }
-    __syncthreads();
-    if (P.g_cam != nullptr && threadIdx.x < 12 && acc_cam[threadIdx.x] != 0.f) atomicAdd(&P.g_cam[threadIdx.x], acc_cam[threadIdx.x]);
-    if (P.g_env_scale != nullptr && threadIdx.x == 12 && acc_cam[12] != 0.f) atomicAdd(P.g_env_scale, acc_cam[12]);
-    if (P.g_env_xf != nullptr && threadIdx.x >= 16 && threadIdx.x < 27 && acc_cam[threadIdx.x] != 0.f) atomicAdd(&P.g_env_xf[threadIdx.x - 16], acc_cam[threadIdx.x]);
-    if (P.g_mat != nullptr)
-        for (int i = threadIdx.x; i < T.n_bsdfs * kMatOut; i += kBlock) { const float v = acc_mat[(i / kMatOut) * mrow + i % kMatOut]; if (v != 0.f) atomicAdd(&P.g_mat[i], v); }
-    if (P.g_uv_xf != nullptr) {          // uv transforms: three bitmaps per BSDF, then the environment map's
-        for (int i = threadIdx.x; i < T.n_bsdfs * 12; i += kBlock) { const float v = acc_mat[(i / 12) * mrow + kMatOut + i % 12]; if (v != 0.f) atomicAdd(&P.g_uv_xf[i], v); }
-        if (threadIdx.x >= 28 && threadIdx.x < 32 && acc_cam[threadIdx.x] != 0.f) atomicAdd(&P.g_uv_xf[12 * T.n_bsdfs + threadIdx.x - 28], acc_cam[threadIdx.x]);
-    }
-    if (use_lds) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < P.n_hot * 22; i += kBlock) if (acc[i] != 0.f) atomicAdd(&P.g_tri[P.hot_inv[i / 22] * 22 + i % 22], acc[i]);
-        for (int i = threadIdx.x; i < T.n_bsdfs * 3; i += kBlock) if (acc_bsdf[i] != 0.f) atomicAdd(&P.g_bsdf[i], acc_bsdf[i]);
-        for (int i = threadIdx.x; i < T.n_emitters * 3; i += kBlock) if (acc_emit[i] != 0.f) atomicAdd(&P.g_emitter[i], acc_emit[i]);
-    }
+    adj_flush(scratch, T, P);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -459,28 +461,22 @@ template <int LDS> PSDR_DEV VtxGeom load_vertex(const SceneView<LDS> &S, int slo
 template <int LDS>
 PSDR_DEV void run_interior_adjoint_sweep(SceneView<LDS> &S, const SensorDev &cam, const AdjointParams &P, float *scratch) {
     const SceneTables &T = *S.T;
-    const int mrow = S.uv_adj ? kMatRow : kMatOut;                     // LDS row of a BSDF's material adjoints (kMatRow)
     const int lane_id = threadIdx.x & 63;
     const unsigned long long lt_mask = (1ull << lane_id) - 1ull;
     const float inv_spp = T.spp > 1 ? 1.f / (float) T.spp : 1.f;
     const int D = P.max_depth;
     const int lane_words = P.hit_words + P.ext_words + P.lk_words;        // sized by the launch: >= adj_sweep_words(D)
-    float *vrec = (P.rec_global ? P.rec_global + (size_t) blockIdx.x * (size_t) lane_words * kBlock : scratch) + threadIdx.x;    // [3 * (D + 1)] slot, u, v per vertex, stride kBlock
-    float *brec = vrec + 3 * (D + 1) * kBlock;                            // [11 * D] per bounce: 0 light slot, 1-2 its barycentrics, 3 shadow-hit slot,
-                                                                          //   4 cN, 5 cf, 6 w2, 7 flags, 8-10 thr_k
-    float *acc_cam = P.rec_global ? scratch : scratch + lane_words * kBlock;      // same accumulator layout as run_interior_adjoint
-    float *acc_mat = acc_cam + kAdjMisc;
-    float *acc = acc_mat + T.n_bsdfs * mrow;
-    const int n_acc = P.n_hot * 22 + T.n_bsdfs * 3 + T.n_emitters * 3 + P.env_lds;
 #ifdef PSDR_LDS_POISON
     // (diagnostic) the per-lane records start as garbage: a record word that is read before this path wrote it shows up in the result
     if (!P.rec_global) { for (int i = threadIdx.x; i < lane_words * kBlock; i += kBlock) scratch[i] = PSDR_LDS_POISON; __syncthreads(); }
 #endif
-    for (int i = threadIdx.x; i < n_acc; i += kBlock) acc[i] = 0.f;
-    float *acc_bsdf = acc + P.n_hot * 22, *acc_emit = acc_bsdf + T.n_bsdfs * 3;
-    float *acc_env = acc_emit + T.n_emitters * 3;        // [env_lds] texel adjoints of a small environment map (every sample of a wave hits the same few texels)
-    if (threadIdx.x < kAdjMisc) acc_cam[threadIdx.x] = 0.f;
-    __syncthreads();
+    const AdjLdsLayout L = adj_layout_of(T, P);
+    const AdjAcc A = adj_carve(scratch, L, P.rec_global, lane_words);
+    float *vrec = A.recs + threadIdx.x;                                   // [3 * (D + 1)] slot, u, v per vertex, stride kBlock
+    float *brec = vrec + 3 * (D + 1) * kBlock;                            // [11 * D] per bounce: 0 light slot, 1-2 its barycentrics, 3 shadow-hit slot,
+                                                                          //   4 cN, 5 cf, 6 w2, 7 flags, 8-10 thr_k
+    float *acc_cam = A.cam, *acc = A.tri, *acc_bsdf = A.bsdf, *acc_emit = A.emit;
+    float *acc_env = A.env;              // [env_lds] texel adjoints of a small environment map (every sample of a wave hits the same few texels)
     S.mode = 0; S.probe_kind = 0;
 
     auto add_row = [&](const VtxGeom &g, int comp, float val) {
@@ -545,13 +541,13 @@ PSDR_DEV void run_interior_adjoint_sweep(SceneView<LDS> &S, const SensorDev &cam
                         else atomicAdd(&P.g_env[3ll * idx[k] + c], lb[c] * E.scale * wt[k]);
                     }
             }
-            if (P.g_env_scale != nullptr) { const float sb = lb[0] * rgb0[0] + lb[1] * rgb0[1] + lb[2] * rgb0[2]; if (sb != 0.f && finite_(sb)) atomicAdd(&acc_cam[12], sb); }
-            if (P.g_uv_xf != nullptr) { const float ob[3] = {lb[0] * E.scale, lb[1] * E.scale, lb[2] * E.scale}; env_xf_adjoint(E, uu, ww, ob, &acc_cam[28]); }
+            if (P.g_env_scale != nullptr) { const float sb = lb[0] * rgb0[0] + lb[1] * rgb0[1] + lb[2] * rgb0[2]; if (sb != 0.f && finite_(sb)) atomicAdd(&acc_cam[kAdjEnvScale], sb); }
+            if (P.g_uv_xf != nullptr) { const float ob[3] = {lb[0] * E.scale, lb[1] * E.scale, lb[2] * E.scale}; env_xf_adjoint(E, uu, ww, ob, &acc_cam[kAdjEnvUv]); }
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
                 if (!finite_(vb[r])) vb[r] = 0.f;
                 if (P.g_env_xf != nullptr)
-                    for (int c = 0; c < 3; ++c) { const float val = vb[r] * dv[c]; if (val != 0.f) atomicAdd(&acc_cam[16 + 4 * r + c], val); }
+                    for (int c = 0; c < 3; ++c) { const float val = vb[r] * dv[c]; if (val != 0.f) atomicAdd(&acc_cam[kAdjEnvXf + 4 * r + c], val); }
             }
             dirb = Vec3f(E.from_world.m[0] * vb[0] + E.from_world.m[4] * vb[1] + E.from_world.m[8] * vb[2],
                          E.from_world.m[1] * vb[0] + E.from_world.m[5] * vb[1] + E.from_world.m[9] * vb[2],
@@ -886,7 +882,7 @@ PSDR_DEV void run_interior_adjoint_sweep(SceneView<LDS> &S, const SensorDev &cam
 #pragma unroll
                             for (int c = 0; c < 4; ++c) {
                                 const float val = obv[r] * oc[c] + dbv[r] * dc[c];
-                                if (val != 0.f && finite_(val)) atomicAdd(&acc_cam[4 * r + c], val);
+                                if (val != 0.f && finite_(val)) atomicAdd(&acc_cam[kAdjCam + 4 * r + c], val);
                             }
                     }
                 }
@@ -924,15 +920,7 @@ PSDR_DEV void run_interior_adjoint_sweep(SceneView<LDS> &S, const SensorDev &cam
             for (int q = 0; q < 12; ++q) pe_val[q] = 0.f;
         }
     }
-    __syncthreads();
-    if (P.g_cam != nullptr && threadIdx.x < 12 && acc_cam[threadIdx.x] != 0.f) atomicAdd(&P.g_cam[threadIdx.x], acc_cam[threadIdx.x]);
-    if (P.g_env_scale != nullptr && threadIdx.x == 12 && acc_cam[12] != 0.f) atomicAdd(P.g_env_scale, acc_cam[12]);
-    if (P.g_env_xf != nullptr && threadIdx.x >= 16 && threadIdx.x < 27 && acc_cam[threadIdx.x] != 0.f) atomicAdd(&P.g_env_xf[threadIdx.x - 16], acc_cam[threadIdx.x]);
-    if (P.g_uv_xf != nullptr && threadIdx.x >= 28 && threadIdx.x < 32 && acc_cam[threadIdx.x] != 0.f) atomicAdd(&P.g_uv_xf[12 * T.n_bsdfs + threadIdx.x - 28], acc_cam[threadIdx.x]);
-    for (int i = threadIdx.x; i < P.n_hot * 22; i += kBlock) if (acc[i] != 0.f) atomicAdd(&P.g_tri[P.hot_inv[i / 22] * 22 + i % 22], acc[i]);
-    for (int i = threadIdx.x; i < T.n_bsdfs * 3; i += kBlock) if (acc_bsdf[i] != 0.f) atomicAdd(&P.g_bsdf[i], acc_bsdf[i]);
-    for (int i = threadIdx.x; i < T.n_emitters * 3; i += kBlock) if (acc_emit[i] != 0.f) atomicAdd(&P.g_emitter[i], acc_emit[i]);
-    for (int i = threadIdx.x; i < P.env_lds; i += kBlock) if (acc_env[i] != 0.f) atomicAdd(&P.g_env[i], acc_env[i]);
+    adj_flush(scratch, T, P);
 }
 
 } // namespace psdr

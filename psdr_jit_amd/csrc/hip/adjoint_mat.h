@@ -52,10 +52,9 @@ PSDR_DEV void vertex_frame(const Vec3<R> &ns, const Vec3<R> &e1, const Vec3<R> &
 // barycentrics are differentiable).
 template <int LDS>
 PSDR_DEV Vec3f bsdf_plain_value_and_adjoint(const SceneView<LDS> &S, int bid, const Vec3f &wi, const Vec3f &wo, float tu, float tv, const Vec3f *Fb,
-                                            float *wib, float *wob, float *acc_bsdf, float *acc_mat, float *g_tex, float *uvb,
+                                            float *wib, float *wob, float *acc_bsdf, float *acc_mat, int mrow, float *g_tex, float *uvb,
                                             int slot = -1, float bu = 0.f, float bv = 0.f, float *bcb = nullptr) {
     if (wib) { wib[0] = wib[1] = wib[2] = 0.f; wob[0] = wob[1] = wob[2] = 0.f; }
-    const int mrow = S.uv_adj ? kMatRow : kMatOut;                     // LDS row of a BSDF's material adjoints (kMatRow)
     if (bid < 0) return Vec3f(0.f);
     const float4 a = S.ld(S.T->bsdf_off + 2 * bid);
     const int fl = __float_as_int(a.w);
@@ -276,9 +275,8 @@ PSDR_DEV void nm_geometry(const Vec3<R> &wi, const Vec3<R> &wo, const Vec3<R> &c
 // coordinates) and dp_du (`dpb`: the caller takes it to the triangle's edges).  dpdu / dpb: the vertex's dp_du (make_its), needed by NormalMaps only.
 template <int LDS>
 PSDR_DEV Vec3f bsdf_value_and_adjoint(const SceneView<LDS> &S, int bid, const Vec3f &wi_, const Vec3f &wo_, float tu, float tv, const Vec3f *Fb,
-                                      float *wib, float *wob, float *acc_bsdf, float *acc_mat, float *g_tex, float *uvb,
+                                      float *wib, float *wob, float *acc_bsdf, float *acc_mat, int mrow, float *g_tex, float *uvb,
                                       int slot = -1, float bu = 0.f, float bv = 0.f, float *bcb = nullptr, const Vec3f *dpdu = nullptr, float *dpb = nullptr) {
-    const int mrow = S.uv_adj ? kMatRow : kMatOut;                     // LDS row of a BSDF's material adjoints (kMatRow)
     if constexpr (has_mat(LDS)) {
         if (bid >= 0 && (__float_as_int(S.ld(S.T->bsdf_off + 2 * bid).w) & 256)) {
             if (wib) { wib[0] = wib[1] = wib[2] = 0.f; wob[0] = wob[1] = wob[2] = 0.f; }
@@ -302,19 +300,19 @@ PSDR_DEV Vec3f bsdf_value_and_adjoint(const SceneView<LDS> &S, int bid, const Ve
             float lp, g1;
             bool refl;
             nm_geometry<float>(wi, wo, c, dp, pwi, pwo, rwi, lp, g1, refl);
-            const Vec3f N1 = bsdf_plain_value_and_adjoint<LDS>(S, nested, pwi, pwo, tu, tv, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, slot, bu, bv, nullptr);
+            const Vec3f N1 = bsdf_plain_value_and_adjoint<LDS>(S, nested, pwi, pwo, tu, tv, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, slot, bu, bv, nullptr);
             Vec3f N2(0.f);
-            if (refl) N2 = bsdf_plain_value_and_adjoint<LDS>(S, nested, rwi, pwo, tu, tv, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, slot, bu, bv, nullptr);
+            if (refl) N2 = bsdf_plain_value_and_adjoint<LDS>(S, nested, rwi, pwo, tu, tv, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, slot, bu, bv, nullptr);
             const Vec3f F = N1 * (lp * g1) + N2 * ((1.f - lp) * g1);
             if (Fb == nullptr) return F;
             if (!(finite_(Fb->x) && finite_(Fb->y) && finite_(Fb->z)) || (Fb->x == 0.f && Fb->y == 0.f && Fb->z == 0.f)) return F;
             // the nested BSDF's adjoints (its parameters accumulate inside) for the two evaluations
             float pwib[3], pwob[3], rwib[3] = {0.f, 0.f, 0.f}, pwob2[3] = {0.f, 0.f, 0.f};
             const Vec3f Nb1 = *Fb * (lp * g1);
-            bsdf_plain_value_and_adjoint<LDS>(S, nested, pwi, pwo, tu, tv, &Nb1, pwib, pwob, acc_bsdf, acc_mat, g_tex, uvb, slot, bu, bv, bcb);
+            bsdf_plain_value_and_adjoint<LDS>(S, nested, pwi, pwo, tu, tv, &Nb1, pwib, pwob, acc_bsdf, acc_mat, mrow, g_tex, uvb, slot, bu, bv, bcb);
             if (refl) {
                 const Vec3f Nb2 = *Fb * ((1.f - lp) * g1);
-                bsdf_plain_value_and_adjoint<LDS>(S, nested, rwi, pwo, tu, tv, &Nb2, rwib, pwob2, acc_bsdf, acc_mat, g_tex, uvb, slot, bu, bv, bcb);
+                bsdf_plain_value_and_adjoint<LDS>(S, nested, rwi, pwo, tu, tv, &Nb2, rwib, pwob2, acc_bsdf, acc_mat, mrow, g_tex, uvb, slot, bu, bv, bcb);
             }
             const Vec3f dN = N1 - N2, mix = N1 * lp + N2 * (1.f - lp);
             const float lpb = g1 * (Fb->x * dN.x + Fb->y * dN.y + Fb->z * dN.z), g1b = Fb->x * mix.x + Fb->y * mix.y + Fb->z * mix.z;
@@ -361,31 +359,25 @@ PSDR_DEV Vec3f bsdf_value_and_adjoint(const SceneView<LDS> &S, int bid, const Ve
             return F;
         }
     }
-    return bsdf_plain_value_and_adjoint<LDS>(S, bid, wi_, wo_, tu, tv, Fb, wib, wob, acc_bsdf, acc_mat, g_tex, uvb, slot, bu, bv, bcb);
+    return bsdf_plain_value_and_adjoint<LDS>(S, bid, wi_, wo_, tu, tv, Fb, wib, wob, acc_bsdf, acc_mat, mrow, g_tex, uvb, slot, bu, bv, bcb);
 }
 
 template <int LDS>
 PSDR_DEV void run_interior_adjoint_sweep_mat(SceneView<LDS> &S, const SensorDev &cam, const AdjointParams &P, float *scratch) {
     const SceneTables &T = *S.T;
-    const int mrow = S.uv_adj ? kMatRow : kMatOut;                     // LDS row of a BSDF's material adjoints (kMatRow)
     const int lane_id = threadIdx.x & 63;
     const unsigned long long lt_mask = (1ull << lane_id) - 1ull;
     const float inv_spp = T.spp > 1 ? 1.f / (float) T.spp : 1.f;
     const int D = P.max_depth;
     const int lane_words = P.hit_words + P.ext_words + P.lk_words;        // sized by the launch: >= adj_sweep_words(D)
-    float *vrec = (P.rec_global ? P.rec_global + (size_t) blockIdx.x * (size_t) lane_words * kBlock : scratch) + threadIdx.x;    // [3 * (D + 1)] slot, u, v per vertex, stride kBlock
+    const AdjLdsLayout L = adj_layout_of(T, P);
+    const AdjAcc A = adj_carve(scratch, L, P.rec_global, lane_words);
+    float *vrec = A.recs + threadIdx.x;                                   // [3 * (D + 1)] slot, u, v per vertex, stride kBlock
     float *brec = vrec + 3 * (D + 1) * kBlock;                            // [11 * D] per bounce: 0 light slot, 1-2 its barycentrics, 3 shadow-hit slot,
                                                                           //   4 cN, 5 cf, 6 w2, 7 flags, 8-10 thr_k
-    float *acc_cam = P.rec_global ? scratch : scratch + lane_words * kBlock;      // same accumulator layout as run_interior_adjoint
-    float *acc_mat = acc_cam + kAdjMisc;
-    float *acc = acc_mat + T.n_bsdfs * mrow;
-    const int n_acc = P.n_hot * 22 + T.n_bsdfs * 3 + T.n_emitters * 3 + P.env_lds;
-    for (int i = threadIdx.x; i < n_acc; i += kBlock) acc[i] = 0.f;
-    float *acc_bsdf = acc + P.n_hot * 22, *acc_emit = acc_bsdf + T.n_bsdfs * 3;
-    float *acc_env = acc_emit + T.n_emitters * 3;        // [env_lds] texel adjoints of a small environment map (every sample of a wave hits the same few texels)
-    if (threadIdx.x < kAdjMisc) acc_cam[threadIdx.x] = 0.f;
-    for (int i = threadIdx.x; i < T.n_bsdfs * mrow; i += kBlock) acc_mat[i] = 0.f;
-    __syncthreads();
+    float *acc_cam = A.cam, *acc_mat = A.mat, *acc = A.tri, *acc_bsdf = A.bsdf, *acc_emit = A.emit;
+    const int mrow = L.mat_row;
+    float *acc_env = A.env;              // [env_lds] texel adjoints of a small environment map (every sample of a wave hits the same few texels)
     S.mode = 0; S.probe_kind = 0;
 
     auto add_row = [&](const VtxGeom &g, int comp, float val) {
@@ -450,13 +442,13 @@ PSDR_DEV void run_interior_adjoint_sweep_mat(SceneView<LDS> &S, const SensorDev 
                         else atomicAdd(&P.g_env[3ll * idx[k] + c], lb[c] * E.scale * wt[k]);
                     }
             }
-            if (P.g_env_scale != nullptr) { const float sb = lb[0] * rgb0[0] + lb[1] * rgb0[1] + lb[2] * rgb0[2]; if (sb != 0.f && finite_(sb)) atomicAdd(&acc_cam[12], sb); }
-            if (P.g_uv_xf != nullptr) { const float ob[3] = {lb[0] * E.scale, lb[1] * E.scale, lb[2] * E.scale}; env_xf_adjoint(E, uu, ww, ob, &acc_cam[28]); }
+            if (P.g_env_scale != nullptr) { const float sb = lb[0] * rgb0[0] + lb[1] * rgb0[1] + lb[2] * rgb0[2]; if (sb != 0.f && finite_(sb)) atomicAdd(&acc_cam[kAdjEnvScale], sb); }
+            if (P.g_uv_xf != nullptr) { const float ob[3] = {lb[0] * E.scale, lb[1] * E.scale, lb[2] * E.scale}; env_xf_adjoint(E, uu, ww, ob, &acc_cam[kAdjEnvUv]); }
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
                 if (!finite_(vb[r])) vb[r] = 0.f;
                 if (P.g_env_xf != nullptr)
-                    for (int c = 0; c < 3; ++c) { const float val = vb[r] * dv[c]; if (val != 0.f) atomicAdd(&acc_cam[16 + 4 * r + c], val); }
+                    for (int c = 0; c < 3; ++c) { const float val = vb[r] * dv[c]; if (val != 0.f) atomicAdd(&acc_cam[kAdjEnvXf + 4 * r + c], val); }
             }
             dirb = Vec3f(E.from_world.m[0] * vb[0] + E.from_world.m[4] * vb[1] + E.from_world.m[8] * vb[2],
                          E.from_world.m[1] * vb[0] + E.from_world.m[5] * vb[1] + E.from_world.m[9] * vb[2],
@@ -732,12 +724,12 @@ PSDR_DEV void run_interior_adjoint_sweep_mat(SceneView<LDS> &S, const SensorDev 
                     }
                     auto bsdf_primal = [&](const Vec3f &w) -> Vec3f {
                         const Vec3f wo_l(dot(w, fs), dot(w, ft), dot(w, gk.ns));
-                        return bsdf_value_and_adjoint<LDS>(S, bid, wi_l, wo_l, tu, tv, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, __float_as_int(vr[0]), bary_u, bary_v, nullptr, &dpdu_k, nullptr);
+                        return bsdf_value_and_adjoint<LDS>(S, bid, wi_l, wo_l, tu, tv, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, __float_as_int(vr[0]), bary_u, bary_v, nullptr, &dpdu_k, nullptr);
                     };
                     auto bsdf_back = [&](const Vec3f &w, const Vec3f &Fb) -> Vec3f {
                         const Vec3f wo_l(dot(w, fs), dot(w, ft), dot(w, gk.ns));
                         float wib_l[3], wob_l[3], dpb_l[3] = {0.f, 0.f, 0.f};
-                        bsdf_value_and_adjoint<LDS>(S, bid, wi_l, wo_l, tu, tv, &Fb, wib_l, wob_l, P.skip_bsdf ? nullptr : acc_bsdf, acc_mat, P.g_tex, (k == 0 && T.tex != nullptr) ? uvb : nullptr,
+                        bsdf_value_and_adjoint<LDS>(S, bid, wi_l, wo_l, tu, tv, &Fb, wib_l, wob_l, P.skip_bsdf ? nullptr : acc_bsdf, acc_mat, mrow, P.g_tex, (k == 0 && T.tex != nullptr) ? uvb : nullptr,
                                                     __float_as_int(vr[0]), bary_u, bary_v, k == 0 ? bcb : nullptr, &dpdu_k, dpb_l);
                         dpdu_b = dpdu_b + Vec3f(dpb_l[0], dpb_l[1], dpb_l[2]);
                         wib_w = wib_w + fs * wib_l[0] + ft * wib_l[1] + gk.ns * wib_l[2];
@@ -902,7 +894,7 @@ PSDR_DEV void run_interior_adjoint_sweep_mat(SceneView<LDS> &S, const SensorDev 
 #pragma unroll
                             for (int c = 0; c < 4; ++c) {
                                 const float val = obv[r] * oc[c] + dbv[r] * dc[c];
-                                if (val != 0.f && finite_(val)) atomicAdd(&acc_cam[4 * r + c], val);
+                                if (val != 0.f && finite_(val)) atomicAdd(&acc_cam[kAdjCam + 4 * r + c], val);
                             }
                     }
                 }
@@ -940,22 +932,7 @@ PSDR_DEV void run_interior_adjoint_sweep_mat(SceneView<LDS> &S, const SensorDev 
             for (int q = 0; q < 12; ++q) pe_val[q] = 0.f;
         }
     }
-    __syncthreads();
-    if (P.g_cam != nullptr && threadIdx.x < 12 && acc_cam[threadIdx.x] != 0.f) atomicAdd(&P.g_cam[threadIdx.x], acc_cam[threadIdx.x]);
-    if (P.g_env_scale != nullptr && threadIdx.x == 12 && acc_cam[12] != 0.f) atomicAdd(P.g_env_scale, acc_cam[12]);
-    if (P.g_env_xf != nullptr && threadIdx.x >= 16 && threadIdx.x < 27 && acc_cam[threadIdx.x] != 0.f) atomicAdd(&P.g_env_xf[threadIdx.x - 16], acc_cam[threadIdx.x]);
-    for (int i = threadIdx.x; i < P.n_hot * 22; i += kBlock) if (acc[i] != 0.f) atomicAdd(&P.g_tri[P.hot_inv[i / 22] * 22 + i % 22], acc[i]);
-    for (int i = threadIdx.x; i < T.n_bsdfs * 3; i += kBlock) if (acc_bsdf[i] != 0.f) atomicAdd(&P.g_bsdf[i], acc_bsdf[i]);
-    if (P.g_mat != nullptr)
-        for (int i = threadIdx.x; i < T.n_bsdfs * kMatOut; i += kBlock) { const float v = acc_mat[(i / kMatOut) * mrow + i % kMatOut]; if (v != 0.f) atomicAdd(&P.g_mat[i], v); }
-    if (P.g_uv_xf != nullptr) {          // uv transforms: three bitmaps per BSDF, then the environment map's
-        for (int i = threadIdx.x; i < T.n_bsdfs * 12; i += kBlock) { const float v = acc_mat[(i / 12) * mrow + kMatOut + i % 12]; if (v != 0.f) atomicAdd(&P.g_uv_xf[i], v); }
-        if (threadIdx.x >= 28 && threadIdx.x < 32 && acc_cam[threadIdx.x] != 0.f) atomicAdd(&P.g_uv_xf[12 * T.n_bsdfs + threadIdx.x - 28], acc_cam[threadIdx.x]);
-    }
-    for (int i = threadIdx.x; i < T.n_emitters * 3; i += kBlock) if (acc_emit[i] != 0.f) atomicAdd(&P.g_emitter[i], acc_emit[i]);
-    for (int i = threadIdx.x; i < P.env_lds; i += kBlock) if (acc_env[i] != 0.f) atomicAdd(&P.g_env[i], acc_env[i]);
+    adj_flush(scratch, T, P);
 }
-
-
 
 } // namespace psdr

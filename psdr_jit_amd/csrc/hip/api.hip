@@ -193,6 +193,15 @@ static size_t smem_for(const psdr_hip_scene *sc, int cls) {
     return (cls == 1 || cls == 3) ? sc->smem_bytes : sc->smem_bytes - blob;
 #endif
 }
+// ... of a reverse-mode kernel other than k_paths: the cold path-state rows of brute-force scenes belong to run_paths, the adjoint kernels get tables without them
+static int adj_cold_rows(const SceneTables &T) {
+#ifdef PSDR_NO_ASYNC
+    return kColdRows;
+#else
+    return T.n_tris > kBruteForceMax ? 0 : kColdRows;
+#endif
+}
+static size_t smem_for_adjoint(const psdr_hip_scene *sc, int cls) { return smem_for(sc, cls) - (size_t) adj_cold_rows(sc->T) * kBlock * sizeof(int); }
 // persistent workgroups over `n_lanes` work items with `smem` bytes of dynamic LDS / with the LDS of scene class `cls_`
 #define LAUNCH_SM(kernel, sc, n_lanes, smem, stream, ...) \
     hipLaunchKernelGGL(kernel, dim3(grid_for(sc, n_lanes)), dim3(kBlock), smem, (hipStream_t) (stream), __VA_ARGS__)
@@ -455,7 +464,6 @@ static int render_bwd_impl(const psdr_hip_scene *sc, const psdr_render_args *a, 
         if (g->g_sec_edges && sc->E.n > 0) HIPCHK(hipMemsetAsync(g->g_sec_edges, 0, sizeof(float) * 6 * (size_t) sc->E.n, st));
         if (g->g_prim_edges && cam.n_edges > 0) HIPCHK(hipMemsetAsync(g->g_prim_edges, 0, sizeof(float) * 4 * (size_t) cam.n_edges, st));
     }
-    const bool lds_acc = true;
     const bool with_lookups = T.tex != nullptr || T.pv != nullptr || T.env_emitter >= 0;
     // PSDR_ADJ_GLOBAL=1: run the interior adjoint of an LDS-class scene from global memory (no blob copy in LDS: more workgroups per CU)
 #ifdef PSDR_DEV_KNOBS
@@ -464,18 +472,8 @@ static int render_bwd_impl(const psdr_hip_scene *sc, const psdr_render_args *a, 
     constexpr bool adj_global = false;
 #endif
     const int adj_cls = (cls == 1 && adj_global) ? 2 : cls;
-    // LDS: [blob (class 1)] [stacks] [per-lane records] [camera / env / material accumulators] [hot triangle rows, colours, emitters];
-    // the number of hot triangle rows is what is left of the 160 KB
-    // (the cold path-state rows of brute-force scenes belong to run_paths, i.e. to k_paths: the adjoint kernels get tables without them)
-#ifdef PSDR_NO_ASYNC
-    const int cold_rows = kColdRows;
-#else
-    const int cold_rows = T.n_tris > kBruteForceMax ? 0 : kColdRows;
-#endif
-    const size_t cold_bytes = (size_t) cold_rows * kBlock * sizeof(int);
     SceneTables Ta = T;
-    Ta.stack_depth -= cold_rows;
-    const size_t smem_base = (adj_cls == 1 ? sc->smem_bytes : sc->smem_bytes - ((sc->lds || sc->lds_mat) ? (size_t) T.blob_words * 16 : 0)) - cold_bytes;
+    Ta.stack_depth -= adj_cold_rows(T);
     const int adj_depth = s.depth;
     // Diffuse BSDFs + area lights / an environment map under PathTracer: the reverse sweep (adjoint.h); everything else: record and probe
     const bool no_sweep = std::getenv("PSDR_ADJ_PROBE") != nullptr;                // measurement / test knob, read per call: force the probe form
@@ -490,33 +488,17 @@ static int render_bwd_impl(const psdr_hip_scene *sc, const psdr_render_args *a, 
             return fail("g_uv_xf in the record-and-probe form needs g_tex (BSDF bitmaps) / g_env (environment map) beside it");
     }
     const bool sweep_mat = !no_sweep && !sweep && adj_cls == 0 && sc->simple_mats && (a->field_mode > 0 || T.mat != nullptr || T.tex != nullptr || T.pv != nullptr || sc->has_nmap);
-    const int lane_words = (sweep || sweep_mat) ? adj_sweep_words(adj_depth) : adj_lane_words(adj_depth, with_lookups);
-    // the per-lane records (hits, light samples, lookups of one path: 14 D + 3 words for the sweep) live in LDS when they fit beside
-    // the accumulators, else in a global array of the scene (any depth works, at global-memory latency)
-    // a small environment map (<= 32 KB of texel adjoints, e.g. 64 x 32) accumulates in LDS: all samples of a wave look up the same few
-    // texels, and same-address atomics in global memory serialise (sweeps only)
-    size_t env_lds = 0;
-    if ((sweep || sweep_mat) && T.env_emitter >= 0 && g->g_env != nullptr && (size_t) T.env.width * T.env.height * 3 * sizeof(float) <= 32 * 1024)
-        env_lds = (size_t) T.env.width * T.env.height * 3;
-    const size_t mat_row = g->g_uv_xf ? kMatRow : kMatOut;      // (the uv transforms' twelve floats per BSDF only when they are wanted)
-    const size_t acc_fixed = sizeof(float) * ((size_t) kAdjMisc + (size_t) T.n_bsdfs * mat_row + (size_t) T.n_bsdfs * 3 + (size_t) T.n_emitters * 3 + env_lds);
-    // ... unless they are what keeps a SECOND workgroup off the CU: the kernels need <= 256 registers (two waves per SIMD fit), and one wave per SIMD cannot hide the
-    // latency of the sweep's traces (config 5, depth 3: 40 KB of traversal rows + 45 KB of records; round 4 measured this with a 314-register kernel, where it could not help)
-    const size_t rec_bytes = sizeof(float) * (size_t) lane_words * kBlock, min_hot = 64 * 22 * sizeof(float);
-    const bool two_wg_with_rec = smem_base + rec_bytes + acc_fixed + min_hot <= 80 * 1024, two_wg_without = smem_base + acc_fixed + min_hot <= 80 * 1024;
-    const bool rec_in_lds = (two_wg_with_rec || !two_wg_without || PSDR_ADJ_REC_LDS) && smem_base + rec_bytes + acc_fixed + min_hot <= 160 * 1024;
-    const size_t fixed_bytes = acc_fixed + (rec_in_lds ? sizeof(float) * (size_t) lane_words * kBlock : 0);
-    if (smem_base + fixed_bytes > 160 * 1024) return fail("scene too large for the adjoint kernel's LDS accumulators");
-    // two workgroups per CU (80 KB each) when the fixed part allows it - one wave per SIMD cannot hide the global-memory latency of
-    // the replays -, with at least 64 hot rows (emitters + the largest triangles)
-    const size_t budget = (smem_base + fixed_bytes + 64 * 22 * sizeof(float) <= 80 * 1024) ? 80 * 1024 : 160 * 1024;
-    const int n_hot_used = (int) std::min<size_t>((size_t) sc->n_hot, (budget - smem_base - fixed_bytes) / (22 * sizeof(float)));
-    const size_t n_acc = (size_t) n_hot_used * 22 + (size_t) T.n_bsdfs * 3 + (size_t) T.n_emitters * 3 + env_lds;
-    const size_t adj_bytes = sizeof(float) * ((rec_in_lds ? (size_t) lane_words * kBlock : 0) + kAdjMisc + (size_t) T.n_bsdfs * mat_row + (lds_acc ? n_acc : 0));
-    const size_t smem = smem_base + adj_bytes;
-    if (smem > 160 * 1024) return fail("scene too large for the adjoint kernel's LDS records");
+    // the LDS behind the traversal rows - where the per-lane records live, how many hot triangle rows fit, a small environment map's texels: adj_layout.h
+    AdjPlanIn pin;
+    pin.smem_base = smem_for_adjoint(sc, adj_cls);
+    pin.depth = adj_depth; pin.with_lookups = with_lookups; pin.form = sweep ? kAdjSweep : (sweep_mat ? kAdjSweepMat : kAdjProbe);
+    pin.n_bsdfs = T.n_bsdfs; pin.n_emitters = T.n_emitters; pin.n_hot = sc->n_hot;
+    pin.env_texels = T.env_emitter >= 0 ? (size_t) T.env.width * T.env.height : 0;
+    pin.want_env = T.env_emitter >= 0 && g->g_env != nullptr; pin.want_uv_xf = g->g_uv_xf != nullptr; pin.rec_lds_knob = PSDR_ADJ_REC_LDS;
+    const AdjPlan plan = adj_plan(pin);
+    if (plan.error) return fail(plan.error);
     if (!sc->adj_attr_set) {         // (per scene = per device and context; a process-wide flag would skip the second device)
-#define LDS_160K(kernel) HIPCHK(hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
+#define LDS_160K(kernel) HIPCHK(hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) kAdjLdsCap))
         IF_CLS1(LDS_160K(k_interior_adjoint<1>));
         IF_CLS0(LDS_160K(k_interior_adjoint<0>));
         IF_CLS0(LDS_160K(k_interior_adjoint_mat<0>));
@@ -530,7 +512,7 @@ static int render_bwd_impl(const psdr_hip_scene *sc, const psdr_render_args *a, 
     if ((terms & PSDR_TERM_INTERIOR) && T.spp > 0) {
         AdjointParams P = sampler_params<AdjointParams>(a, s, 0, npx * T.spp, a->pix_ids ? (long long) T.spp : (long long) T.width * T.spp);
         P.pix_ids = a->pix_ids;
-        P.w = d_rgb; P.g_tri = g->g_triangles; P.g_bsdf = g->g_bsdf; P.g_emitter = g->g_emitter; P.hot_map = sc->hot_map.as<int>(); P.hot_inv = sc->hot_inv.as<int>(); P.n_hot = n_hot_used;
+        P.w = d_rgb; P.g_tri = g->g_triangles; P.g_bsdf = g->g_bsdf; P.g_emitter = g->g_emitter; P.hot_map = sc->hot_map.as<int>(); P.hot_inv = sc->hot_inv.as<int>(); P.n_hot = plan.n_hot_used;
         P.mesh_filter = g->mesh_filter; P.skip_bsdf = g->skip_bsdf; P.skip_emitter = g->skip_emitter;
         P.g_tex = sc->tex_total > 0 ? g->g_tex : nullptr;
 #ifdef PSDR_SWEEP_DUMP
@@ -545,12 +527,12 @@ static int render_bwd_impl(const psdr_hip_scene *sc, const psdr_render_args *a, 
             if (next_queue(sc, st, P.counter)) return 1;
             const int grid = grid_for(sc, P.n_local);
             P.hit_words = adj_hit_words(adj_depth); P.ext_words = adj_ext_words(adj_depth); P.lk_words = with_lookups ? 3 * adj_lk_entries(adj_depth) : 0;
-            P.sweep = sweep ? 1 : (sweep_mat ? 2 : 0);
-            if (sweep || sweep_mat) { P.hit_words = lane_words; P.ext_words = 0; P.lk_words = 0; }
-            P.env_lds = (int) env_lds;
+            P.sweep = pin.form;
+            if (sweep || sweep_mat) { P.hit_words = plan.lane_words; P.ext_words = 0; P.lk_words = 0; }
+            P.env_lds = plan.env_lds;
             P.rec_global = nullptr;
-            if (!rec_in_lds) {
-                const size_t need = sizeof(float) * (size_t) grid * (size_t) lane_words * kBlock;
+            if (!plan.rec_in_lds) {
+                const size_t need = sizeof(float) * (size_t) grid * (size_t) plan.lane_words * kBlock;
                 if (need > sc->adj_rec_bytes) {
                     // (every earlier user of the records was ordered before this stream by the guard: its completion is this stream's)
                     if (sc->adj_rec.p) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(sc->adj_rec.p)); sc->adj_rec.p = nullptr; sc->adj_rec_bytes = 0; }
@@ -559,8 +541,8 @@ static int render_bwd_impl(const psdr_hip_scene *sc, const psdr_render_args *a, 
                 }
                 P.rec_global = (float *) sc->adj_rec.p;
             }
-#define K_ADJOINT(C) LAUNCH_SM((k_interior_adjoint<C>), sc, P.n_local, smem, st, sc->blob.as<float4>(), Ta, cam, P)
-            if (sweep_mat) ON_CLS(0, LAUNCH_SM((k_interior_adjoint_mat<0>), sc, P.n_local, smem, st, sc->blob.as<float4>(), Ta, cam, P));       // (class 0 only: adj_cls == 0 here)
+#define K_ADJOINT(C) LAUNCH_SM((k_interior_adjoint<C>), sc, P.n_local, plan.smem, st, sc->blob.as<float4>(), Ta, cam, P)
+            if (sweep_mat) ON_CLS(0, LAUNCH_SM((k_interior_adjoint_mat<0>), sc, P.n_local, plan.smem, st, sc->blob.as<float4>(), Ta, cam, P));       // (class 0 only: adj_cls == 0 here)
             else LAUNCH_CLS_REV(adj_cls, K_ADJOINT);
 #undef K_ADJOINT
         }
@@ -580,11 +562,11 @@ static int render_bwd_impl(const psdr_hip_scene *sc, const psdr_render_args *a, 
     if (want_prim) {
         if (!g->g_prim_edges) return fail("g_prim_edges is required when the primary-edge term is requested");
         PathParams P = sampler_params<PathParams>(a, s, 1, npx_full * T.sppe, kBlock);
-        P.adj_w = edge_w; P.g_prim = g->g_prim_edges; P.n_prim = cam.n_edges; P.lds_acc = (cam.n_edges <= 2048) ? 1 : 0;
+        P.adj_w = edge_w; P.g_prim = g->g_prim_edges; P.n_prim = cam.n_edges; P.lds_acc = prim_adj_lds_floats(cam.n_edges) > 0 ? 1 : 0;
         P.prim_filter = g->prim_edge_filter;
         if (P.n_local > 0) {
             if (next_queue(sc, st, P.counter)) return 1;
-            const size_t sm = smem_for(sc, cls) + (P.lds_acc ? sizeof(float) * 4 * (size_t) cam.n_edges : 0);
+            const size_t sm = smem_for(sc, cls) + adj_lds_bytes(prim_adj_lds_floats(cam.n_edges));
 #define K_PRIMARY_ADJ(C) LAUNCH_SM((k_paths<false, C, false, 1, kGeneral>), sc, P.n_local, sm, st, sc->blob.as<float4>(), Tp, cam, P, (Counters *) nullptr)
             LAUNCH_CLS_REV(cls, K_PRIMARY_ADJ);
 #undef K_PRIMARY_ADJ
@@ -597,13 +579,11 @@ static int render_bwd_impl(const psdr_hip_scene *sc, const psdr_render_args *a, 
         P.adj_w = edge_w; P.g_sec = g->g_sec_edges; P.g_tri = g->g_triangles; P.n_sec = sc->E.n;
         P.g_cam = g->g_camera;
         P.sec_closed = no_sweep ? 0 : 1;
-        const size_t sec_acc = sizeof(float) * (6 * (size_t) sc->E.n + 22 * (size_t) T.n_tris);
-        P.lds_acc = (sec_acc <= 48 * 1024) ? 1 : 0;
-        // tables too large for LDS: the hot triangle rows still accumulate there (closed form only: it writes p0, e1, e2 = 9 floats per row)
-        constexpr int kSecHotMax = PSDR_SEC_HOT_MAX;
-        P.n_hot = (!P.lds_acc && P.sec_closed) ? std::min(sc->n_hot, kSecHotMax) : 0;
+        // both tables in LDS, or - too large - the hot triangle rows (closed form only): adj_layout.h
+        const SecAdjPlan sp = sec_adj_plan(sc->E.n, T.n_tris, sc->n_hot, P.sec_closed != 0, PSDR_SEC_HOT_MAX);
+        P.lds_acc = sp.lds_acc; P.n_hot = sp.n_hot;
         P.hot_map = sc->hot_map.as<int>(); P.hot_inv = sc->hot_inv.as<int>();
-        const size_t smem_sec = smem_for(sc, sc->lds ? 1 : 0) - cold_bytes + sizeof(float) * (size_t) kSecAdjScratch + (P.lds_acc ? sec_acc : sizeof(float) * 9 * (size_t) P.n_hot);
+        const size_t smem_sec = smem_for_adjoint(sc, sc->lds ? 1 : 0) + sp.bytes;
         const GuidingDev G = a->guiding ? a->guiding->G : GuidingDev{};
         const int use_g = a->guiding ? 1 : 0;
         if (P.n_local > 0) {

@@ -138,7 +138,7 @@ __global__ __launch_bounds__(kBlock, PSDR_ADJ_WAVES(LDS)) void k_interior_adjoin
                                                              const AdjointParams P) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     SceneView<LDS> S = make_view<LDS>(blob, T, smem);
-    S.mis = P.mis; S.field = P.field; S.field_object = P.field_object; S.intensity = P.intensity; S.d_intensity = P.d_intensity;
+    S.mis = P.mis; S.field = P.field; S.field_object = P.field_object; S.intensity = P.intensity; S.d_intensity = P.d_intensity; S.uv_adj = P.g_uv_xf != nullptr;
     if constexpr (!has_mat(LDS)) { if (P.sweep) { run_interior_adjoint_sweep<LDS>(S, cam, P, scratch_base<LDS>(smem, T)); return; } }
     run_interior_adjoint<LDS>(S, cam, P, scratch_base<LDS>(smem, T));
 }
@@ -204,16 +204,16 @@ __global__ __launch_bounds__(kBlock, (ADJ ? PSDR_SEC_ADJ_WAVES : PSDR_SEC_WAVES)
     BoundarySegSampleDirect bss;
     bss.valid = false; bss.pdf = 1.f; bss.p0 = Vec3d(Dual(0.f)); bss.edge = bss.edge2 = bss.p2 = bss.n = Vec3f(0.f); bss.emitter_slot = -1; bss.edge_id = 0; bss.s1 = 0.f;
     float pdf0 = 1.f;
-    if constexpr (ADJ) if (P.lds_acc || P.n_hot > 0) {
-        float *acc = scratch_base<LDS>(smem, T) + kSecAdjScratch;
-        const int n_acc = P.lds_acc ? 6 * P.n_sec + 22 * T.n_tris : 9 * P.n_hot;
-        for (int i = threadIdx.x; i < n_acc; i += kBlock) acc[i] = 0.f;
-        __syncthreads();
-    }
-    // camera-pose adjoint: 12 entries every sample adds to - kept in LDS (behind the 3 recorded hits of this kernel)
-    float *acc_cam = scratch_base<LDS>(smem, T) + kSecAdjLaneWords * kBlock;
-    if constexpr (ADJ) if (P.g_cam != nullptr) {
-        if (threadIdx.x < 16) acc_cam[threadIdx.x] = 0.f;
+    // reverse mode (adj_layout.h): the three recorded hits of a lane; the camera-pose adjoint, 12 entries every sample adds to; `hot_acc`: both tables
+    // (lds_acc: g_sec and g_tri point into it) or the hot triangles' rows
+    float *sec_recs = nullptr, *acc_cam = nullptr, *hot_acc = nullptr, *g_sec = P.g_sec, *g_tri = P.g_tri;
+    if constexpr (ADJ) {
+        float *scratch = scratch_base<LDS>(smem, T);
+        const SecAdjLdsLayout L = sec_adj_lds_layout(P.lds_acc != 0, P.n_sec, T.n_tris, P.n_hot);
+        sec_recs = scratch + L.rec; acc_cam = scratch + L.cam; hot_acc = scratch + L.acc;
+        if (P.lds_acc) { g_sec = scratch + L.sec; g_tri = scratch + L.tri; }
+        for (int i = threadIdx.x; i < L.total - L.acc; i += kBlock) hot_acc[i] = 0.f;
+        if (P.g_cam != nullptr && threadIdx.x < 16) acc_cam[threadIdx.x] = 0.f;
         __syncthreads();
     }
     // Candidates: one in six passes the silhouette / light-facing test.
@@ -242,8 +242,6 @@ __global__ __launch_bounds__(kBlock, (ADJ ? PSDR_SEC_ADJ_WAVES : PSDR_SEC_WAVES)
     // and x1 = the camera ray's hit sliding along that ray - two adjoint solves instead of 21-33 replays
     auto scatter_closed = [&](int idx, const SecAdjInfo &I, const BoundarySegSampleDirect &seg, float pdf_seg) {
         if constexpr (ADJ) {
-            float *g_sec = P.lds_acc ? scratch_base<LDS>(smem, T) + kSecAdjScratch : P.g_sec;
-            float *g_tri = P.lds_acc ? g_sec + 6 * P.n_sec : P.g_tri;
             const float v0c[3] = {I.value0.x, I.value0.y, I.value0.z};
             float gsum = 0.f;
 #pragma unroll
@@ -260,7 +258,6 @@ __global__ __launch_bounds__(kBlock, (ADJ ? PSDR_SEC_ADJ_WAVES : PSDR_SEC_WAVES)
                     if (val.z != 0.f && finite_(val.z)) atomicAdd(&tab[row + 2], val.z);
                 };
                 // triangle rows: hot ones per workgroup in LDS (config 5: 93 -> 42 ms; 51 of the 93 were the scatter, most of it the 108 floats of the scene box)
-                float *hot_acc = scratch_base<LDS>(smem, T) + kSecAdjScratch;
                 auto add_tri = [&](int orig, int comp, const Vec3f &val) {
                     const int hot = (!P.lds_acc && P.n_hot > 0) ? P.hot_map[orig] : -1;
                     if (hot >= 0 && hot < P.n_hot) add3(hot_acc, 9 * hot + comp, val); else add3(g_tri, 22 * orig + comp, val);
@@ -443,9 +440,7 @@ __global__ __launch_bounds__(kBlock, (ADJ ? PSDR_SEC_ADJ_WAVES : PSDR_SEC_WAVES)
         }
         if constexpr (ADJ) if (have) {
             // reverse mode: record the three rays once, then probe the quantities the tangent is linear in
-            float *rec = scratch_base<LDS>(smem, T) + threadIdx.x;
-            float *g_sec = P.lds_acc ? scratch_base<LDS>(smem, T) + kSecAdjScratch : P.g_sec;
-            float *g_tri = P.lds_acc ? g_sec + 6 * P.n_sec : P.g_tri;
+            float *rec = sec_recs + threadIdx.x;
             S.rec = rec; S.mode = 1; S.rec_n = 0; S.rec_i = 0; S.probe_kind = 0;
             BoundarySegSampleDirect b0 = bss;
             b0.p0 = promote(detach(bss.p0));
@@ -541,14 +536,12 @@ __global__ __launch_bounds__(kBlock, (ADJ ? PSDR_SEC_ADJ_WAVES : PSDR_SEC_WAVES)
         if (threadIdx.x < 12 && acc_cam[threadIdx.x] != 0.f) atomicAdd(&P.g_cam[threadIdx.x], acc_cam[threadIdx.x]);
     }
     if constexpr (ADJ) if (P.lds_acc) {
-        float *acc = scratch_base<LDS>(smem, T) + kSecAdjScratch;
         __syncthreads();
-        for (int i = threadIdx.x; i < 6 * P.n_sec; i += kBlock) if (acc[i] != 0.f) atomicAdd(&P.g_sec[i], acc[i]);
-        for (int i = threadIdx.x; i < 22 * T.n_tris; i += kBlock) if (acc[6 * P.n_sec + i] != 0.f) atomicAdd(&P.g_tri[i], acc[6 * P.n_sec + i]);
+        for (int i = threadIdx.x; i < 6 * P.n_sec; i += kBlock) if (g_sec[i] != 0.f) atomicAdd(&P.g_sec[i], g_sec[i]);
+        for (int i = threadIdx.x; i < 22 * T.n_tris; i += kBlock) if (g_tri[i] != 0.f) atomicAdd(&P.g_tri[i], g_tri[i]);
     } else if (P.n_hot > 0) {
-        float *acc = scratch_base<LDS>(smem, T) + kSecAdjScratch;
         __syncthreads();
-        for (int i = threadIdx.x; i < 9 * P.n_hot; i += kBlock) if (acc[i] != 0.f) atomicAdd(&P.g_tri[22 * P.hot_inv[i / 9] + i % 9], acc[i]);
+        for (int i = threadIdx.x; i < 9 * P.n_hot; i += kBlock) if (hot_acc[i] != 0.f) atomicAdd(&P.g_tri[22 * P.hot_inv[i / 9] + i % 9], hot_acc[i]);
     }
     if (COUNT) flush_counters(S, ctr);
 }

@@ -526,6 +526,20 @@ def textured_ggx_scene(width=48, height=48, spp=4, sppe=0, sppse=0, kind="roughc
     return spec
 
 
+def with_bsdf_last(spec, index):
+    """The same scene with spec.bsdfs[index] moved to the last row: the BSDFs behind it move up, and the meshes' BSDF ids and the NormalMaps' nested ids follow."""
+    n = len(spec.bsdfs)
+    order = [i for i in range(n) if i != index] + [index]
+    new_id = {old: new for new, old in enumerate(order)}
+    spec.bsdfs = [spec.bsdfs[i] for i in order]
+    for m in spec.meshes:
+        m.bsdf = new_id[m.bsdf]
+    for b in spec.bsdfs:
+        if getattr(b, "nested", -1) >= 0:
+            b.nested = new_id[b.nested]
+    return spec
+
+
 def hdr_step_square_scene(width=64, height=64, spp=0, sppe=128, a=20.0, d=100.0, fov=60.0, L_pos=100.0, L_neg=1.5):
     """A black, flat-shaded square (half-size a, depth d, facing the camera at the origin that looks down -z) moving along x by
     100 P in front of a lat-long map that is L_pos where the direction has x > 0 and L_neg where x < 0: the closed-form case of the

@@ -658,3 +658,82 @@ def test_uv_transform_adjoints_in_one_pass(env, orc, monkeypatch, case, probe):
     gu = g_uv.cpu().numpy().astype(np.float64)
     rhs = float((gu[:3 * len(spec.bsdfs)].reshape(len(spec.bsdfs), 3, 4) * d_tex).sum() + (gu[3 * n_b] * d_env).sum())
     assert abs(lhs) > 1e-3 * scale and abs(lhs - rhs) <= 1e-3 * scale, (case, probe, lhs, rhs, scale)
+
+
+_UV_SHARE = {
+    # scene, forced probe form (the GGX bitmap scenes take it by default)
+    "roughconductor": (lambda: scenes.textured_ggx_scene(40, 40, 8, 0, 0, kind="roughconductor"), False),
+    "roughdielectric": (lambda: scenes.textured_ggx_scene(40, 40, 8, 0, 0, kind="roughdielectric"), False),
+    "microfacet": (lambda: scenes.textured_microfacet_scene(40, 40, 8, 0, 0), True),
+}
+
+
+@pytest.mark.parametrize("last", [False, True])
+@pytest.mark.parametrize("case", list(_UV_SHARE))
+def test_uv_adjoints_do_not_share_words_with_other_buffers(env, orc, monkeypatch, case, last):
+    """The record-and-probe form keeps a BSDF's uv-transform adjoints behind its g_mat row in LDS (adj_layout.h: 28 words per BSDF with g_uv_xf, else 16).  A kernel that
+    carves 16-word rows while it writes uv adjoints puts those of BSDF b into the g_mat row of BSDF b + 1, or - the last BSDF - into the first hot triangle row.  So: the
+    textured BSDF in row 0 with a RoughConductor of constants behind it (a live g_mat row), and moved to the last row; one launch with g_uv_xf and one without.
+    (a) g_triangles, g_mat, g_bsdf and g_tex do not depend on whether g_uv_xf is asked for (1e-5 of a buffer's L1 norm: float atomics reorder sums, as in
+    test_every_adjoint_kernel_is_the_same_in_every_run); (b) g_uv_xf satisfies <J^T w, v> = <w, J v> against the oracle's forward mode at 1e-3 x scale.
+    Measured on the build before the single layout (same scenes, same seeds): the two GGX bitmap scenes passed in both positions (every figure <= 1.4e-7: by default
+    they evidently do not run through the 16-word rows).  The Microfacet scene under PSDR_ADJ_PROBE failed: textured BSDF in row 0 - g_mat off by 3.17 of its L1 norm
+    and |lhs - rhs| = 0.135 x scale; in the last row - g_triangles off by 0.39 of its L1 norm (the identity held there, 1.0e-4 x scale).  With the single layout every
+    buffer agrees to <= 1.6e-7 and the identity holds to <= 1.7e-7 x scale in all six cases."""
+    torch, psdr, cabi = env
+    make, force_probe = _UV_SHARE[case]
+    spec = make()
+    spec.bsdfs[1] = scenes.BsdfSpec(name="gold", type=2, alpha_u=0.15, alpha_v=0.35, eta=(0.14, 0.37, 1.44), k=(3.98, 2.38, 1.60), specular=(1.0, 0.9, 0.8))
+    if last:
+        spec = scenes.with_bsdf_last(spec, 0)
+    tex_row = len(spec.bsdfs) - 1 if last else 0
+    rng = np.random.default_rng(5)
+    d_tex = np.zeros((len(spec.bsdfs), 3, 4))
+    d_tex[tex_row] = rng.uniform(-1.0, 1.0, size=(3, 4))
+    spec.bsdfs[tex_row].tex_xf, spec.bsdfs[tex_row].d_tex_xf = _UV_XF, d_tex[tex_row]
+    _img, d_img = orc.OracleScene(spec, [0]).render_d(max_depth=3, seeds=(7, 8, 9), terms=1)
+    n = spec.width * spec.height
+    gen = torch.Generator(device="cpu").manual_seed(3)
+    w = (torch.rand((n, 3), generator=gen) + 0.5).to("cuda")
+    lhs = float((torch.from_numpy(d_img).to("cuda").double() * w.double()).sum())
+    scale = float((torch.from_numpy(d_img).to("cuda").double().abs() * w.double()).sum()) + 1e-12
+    if force_probe:
+        monkeypatch.setenv("PSDR_ADJ_PROBE", "1")
+    else:
+        monkeypatch.delenv("PSDR_ADJ_PROBE", raising=False)
+    sc = product.build_scene(spec)
+    snap = sc._snapshot()
+    n_tris = np.asarray(snap["d_triangles"]).shape[0]
+    n_b = len(snap["bsdf_rows"]) if "bsdf_rows" in snap else len(spec.bsdfs)
+    offs = (C.c_int64 * (3 * max(1, n_b)))(); total = C.c_int64(0)
+    cabi.check(cabi.lib().psdr_hip_scene_tex_layout(C.c_void_p(sc._hip_handle()), offs, C.byref(total)))
+    assert total.value > 0
+
+    def launch(with_uv):
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device="cuda")
+        out = {"tri": z(n_tris, 22), "bsdf": z(max(1, n_b), 3), "emitter": z(max(1, len(spec.emitters)), 3), "sec": z(1, 6), "prim": z(1, 4),
+               "mat": z(max(1, n_b), 16), "tex": z(total.value), "uv": z(3 * n_b + 1, 4)}
+        g = cabi.Grads(out["tri"].data_ptr(), out["bsdf"].data_ptr(), out["emitter"].data_ptr(), out["sec"].data_ptr(), out["prim"].data_ptr())
+        g.g_mat, g.g_tex = out["mat"].data_ptr(), out["tex"].data_ptr()
+        if with_uv:
+            g.g_uv_xf = out["uv"].data_ptr()
+        a = cabi.make_args(max_depth=3, seeds=(7, 8, 9), terms=1)
+        cabi.check(cabi.lib().psdr_hip_render_d_bwd(sc._hip_handle(), C.byref(a), w.data_ptr(), C.byref(g), None))
+        torch.cuda.synchronize()
+        return {k: v.cpu().numpy().astype(np.float64) for k, v in out.items()}
+
+    with_uv, without = launch(True), launch(False)
+    monkeypatch.delenv("PSDR_ADJ_PROBE", raising=False)
+    gu = with_uv["uv"]
+    rhs = float((gu[:3 * len(spec.bsdfs)].reshape(len(spec.bsdfs), 3, 4) * d_tex).sum())
+    errs = {}
+    for k in ("tri", "mat", "bsdf", "tex"):
+        ref = np.abs(without[k]).sum()
+        errs[k] = np.abs(with_uv[k] - without[k]).sum() / ref if ref > 0.0 else np.abs(with_uv[k]).sum()
+    print("uv share", case, "last" if last else "first", "errs", errs, "L1 mat", np.abs(without["mat"]).sum(), "L1 tri", np.abs(without["tri"]).sum(),
+          "lhs", lhs, "rhs", rhs, "scale", scale, "rel", abs(lhs - rhs) / scale)
+    assert np.abs(without["mat"]).sum() > 0.0 and np.abs(without["tri"]).sum() > 0.0 and np.abs(without["tex"]).sum() > 0.0, (case, last)       # the rows next to the uv adjoints are live
+    assert np.abs(without["uv"]).sum() == 0.0, (case, last)
+    for k, err in errs.items():
+        assert err <= 1e-5, (case, last, k, err)
+    assert abs(lhs) > 1e-3 * scale and abs(lhs - rhs) <= 1e-3 * scale, (case, last, lhs, rhs, scale)
