@@ -384,7 +384,9 @@ def test_every_reverse_form_against_the_probe_form(env, monkeypatch, family):
 def test_environment_sweep_equals_the_probe_form(env, monkeypatch, balls):
     """class-2 reverse sweep against record-and-probe with EVERY optional buffer requested (texels, scale and rotation of the map, camera pose): round 4 found
     the probe form losing the y / z components of the vertex-normal adjoints (and those of every hit behind the camera's) as soon as a path had recorded
-    lookups - its stage-3 loop ran again in stage 6 (adjoint.h) -, which no dot-product test saw because translations leave the normals' tangents zero"""
+    lookups - its stage-3 loop ran again in stage 6 (adjoint.h) -, which no dot-product test saw because translations leave the normals' tangents zero.
+    (The normals' tangents are probed since: by the rotations of test_interior_adjoint_rotation_of_a_smooth_mesh, one dot product each, and against the oracle
+    vertex by vertex - one-hot vertex tangents on the smooth balls - in tests/test_gpu_vertex_adjoint.py, whose sphere family also runs under PSDR_ADJ_PROBE.)"""
     spec = scenes.envmap_scene(40, 40, 8, 0, 0, param="box_rot_x", area_light=True, balls=balls)
     sw = _all_adjoint_buffers(env, spec, 3, monkeypatch, probe=False)
     pr = _all_adjoint_buffers(env, spec, 3, monkeypatch, probe=True)
