@@ -544,6 +544,32 @@ int psdr_hip_adaptive_merge(const int32_t *offsets, int32_t n, int64_t total, in
 int psdr_hip_adaptive_merge_adj(const int32_t *offsets, int32_t n, int64_t total, int32_t channels, const float *d_out, float rows_n, float base_n, float *d_rows,
                                 float *d_base, void *stream);
 
+/* EDGE-AVOIDING A-TROUS DENOISER AND ITS TRANSPOSE (csrc/hip/denoise.hip; psdr_jit_amd/denoise.py).  Device pointers throughout, plain launches on
+ * `stream` (one per level), no synchronisation, no atomics (the same input gives the same bits).  Every call checks its arguments BEFORE any device call and returns non-zero
+ * with psdr_hip_last_error text for a NULL pointer, W or H < 1, W H > 2^24, L outside [1, 8], C outside [1, 4], G outside [0, 8], in == out.  Added under ABI 16 like the
+ * adaptive entry points: nothing existing changed.
+ *
+ * The operator.  The frame is W x H, pixel p = y W + x (the order renderC returns).  The image x is [W H, C] float32, the guides g are [W H, G] float32 and PRE-SCALED: the
+ * kernel knows nothing of what a channel means.  Level l = 0 .. L - 1 has stride s = 2^l and the taps (i, j) in {-2 .. 2}^2 with h = [1, 4, 6, 4, 1] / 16.
+ *     the tap q = p + s (i, j) exists only if q lies inside the frame (taps outside are dropped, not clamped)
+ *     d2 = sum_k (g_k(p) - g_k(q))^2,    w_l(p, q) = h(i) h(j) exp(-d2) if d2 is finite, otherwise 0;   the centre tap always has weight h(0)^2, whatever the guides hold
+ *     N_l(p) = sum_q w_l(p, q) >= 9/64 (no guard is needed),    A_l x (p) = sum_q w_l(p, q) x(q) / N_l(p)
+ * A_l is linear in x and row-stochastic; the guides carry no gradient.  The filter is D = A_{L-1} ... A_0.
+ * The transpose.  w_l is symmetric in (p, q) (h and d2 are, and p and q are both in-frame), so A_l^T y (q) = sum_p w_l(q, p) (y(p) / N_l(p)): the same gather over the same
+ * taps with the source pre-divided and no division at the end; D^T = A_0^T ... A_{L-1}^T.  No scatter.
+ * In float32 as written: d2 by G subtractions, squares and additions in channel order (no fused multiply-add), expf, the 25 taps added row by row (j outer, i inner),
+ * 1 / N_l by one IEEE division when the handle is made, and one multiplication by it per element (apply: of the sum; transpose: of the source).
+ *
+ * create copies the guides into planes, computes the L planes of 1 / N_l and allocates two work frames: the guides may be released once the stream has passed the call.
+ * G == 0 takes guides == NULL and gives the plain B3-spline a-trous smoother.  The handle holds the work frames: one apply or apply_adj at a time per handle. */
+typedef struct psdr_hip_denoise psdr_hip_denoise;
+int psdr_hip_denoise_create(const float *guides, int32_t G, int32_t W, int32_t H, int32_t L, psdr_hip_denoise **out, void *stream);
+/* out = D in; in and out are [W H, C] and may not alias */
+int psdr_hip_denoise_apply(psdr_hip_denoise *denoise, const float *in, int32_t C, float *out, void *stream);
+/* d_in = D^T d_out; the same shapes, the same rule */
+int psdr_hip_denoise_apply_adj(psdr_hip_denoise *denoise, const float *d_out, int32_t C, float *d_in, void *stream);
+int psdr_hip_denoise_destroy(psdr_hip_denoise *denoise);
+
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);
 int psdr_hip_sampler_floats(uint64_t seed_value, uint64_t lane, uint64_t skip, int32_t n, float *out_dev, void *stream);

@@ -1641,3 +1641,5 @@ def samples_behind(scene, term):
 from .precond import laplacian_csr, LaplacianPreconditioner, AdamUniform  # noqa: E402,F401
 # adaptive sampling: a sample budget placed by the noise estimate of render_c_sq (adaptive.py; kernels: csrc/hip/adaptive.hip)
 from .adaptive import adaptive_weights, PixelPlan, render_c_adaptive  # noqa: E402,F401
+# the edge-avoiding a-trous denoiser guided by first-hit fields, and its transpose (denoise.py; kernels: csrc/hip/denoise.hip)
+from .denoise import Denoiser, first_hit_guides  # noqa: E402,F401

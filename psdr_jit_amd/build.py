@@ -26,7 +26,8 @@ UNITS_SRC = os.path.join(CSRC, "hip", "render_units.hip")       # the ten kernel
 SCENE_SRC = os.path.join(CSRC, "hip", "scene_build.hip")        # psdr_hip_scene_create / _update: tree build and refit, uploads (blob_layout.h, blob_rows.h: the blob's layout and row formats)
 PRECOND_SRC = os.path.join(CSRC, "hip", "precond.hip")         # psdr_hip_precond_*: the Laplacian vertex preconditioner, its matrix-vector product and CG solver
 ADAPTIVE_SRC = os.path.join(CSRC, "hip", "adaptive.hip")       # psdr_hip_adaptive_*: sample counts from a weight map (scan), the pixel list, the segment fold and its transpose
-HIP_SRCS = [API_SRC, UNITS_SRC, SCENE_SRC, PRECOND_SRC, ADAPTIVE_SRC]
+DENOISE_SRC = os.path.join(CSRC, "hip", "denoise.hip")         # psdr_hip_denoise_*: the edge-avoiding a-trous denoiser and its transpose, one LDS-tiled gather per level
+HIP_SRCS = [API_SRC, UNITS_SRC, SCENE_SRC, PRECOND_SRC, ADAPTIVE_SRC, DENOISE_SRC]
 BUILD_DEPS = [os.path.join(HERE, "isa_lint.py")]          # part of the recipe: a change of the lint re-builds (and re-lints) the library
 _H = lambda *names: [os.path.join(CSRC, "hip", f) for f in names]
 # every quoted #include a unit's source reaches is in that unit's list (tests/test_build_deps.py walks the include graph)
@@ -37,7 +38,8 @@ API_DEPS = sorted(set(COMMON_DEPS + KERNEL_DEPS))      # the host unit launches 
 SCENE_DEPS = COMMON_DEPS + _H("bvh.h", "filter.h", "blob_rows.h", "blob_layout.h") + [os.path.join(CSRC, "host", "hnum.h"), os.path.join(CSRC, "host", "edge_select.h")] + BUILD_DEPS
 PRECOND_DEPS = [os.path.join(ROOT, "include", "psdr_hip.h")] + BUILD_DEPS
 ADAPTIVE_DEPS = [os.path.join(ROOT, "include", "psdr_hip.h")] + BUILD_DEPS
-HIP_DEPS = sorted(set(API_DEPS + SCENE_DEPS + PRECOND_DEPS + ADAPTIVE_DEPS))
+DENOISE_DEPS = [os.path.join(ROOT, "include", "psdr_hip.h")] + BUILD_DEPS
+HIP_DEPS = sorted(set(API_DEPS + SCENE_DEPS + PRECOND_DEPS + ADAPTIVE_DEPS + DENOISE_DEPS))
 HOST_SRCS = [os.path.join(CSRC, "host", f) for f in ("scene_host.cpp", "bindings.cpp", "exr_piz.cpp")]
 HOST_DEPS = [os.path.join(CSRC, "host", f) for f in ("scene_host.h", "hnum.h", "edge_select.h", "exr_piz.h")] + [os.path.join(ROOT, "include", "psdr_hip.h"), os.path.join(CSRC, "common", "envmath.h"), os.path.join(CSRC, "common", "threads.h")]
 
@@ -87,8 +89,8 @@ UNIT_CLASS_BIT = {1: 1, 2: 1, 6: 1, 8: 1, 3: 2, 9: 2, 4: 4, 7: 4, 10: 4, 5: 8}  
 
 
 def build_hip(force=False, extra_flags=(), target=None):
-    """Fourteen translation units compiled in parallel - api.hip (the host code with the small kernels), render_units.hip ten times (-DPSDR_TU=k:
-    unit k only instantiates list k of the heavy kernel templates, one scene class each), scene_build.hip, precond.hip and adaptive.hip - and linked into one
+    """Fifteen translation units compiled in parallel - api.hip (the host code with the small kernels), render_units.hip ten times (-DPSDR_TU=k:
+    unit k only instantiates list k of the heavy kernel templates, one scene class each), scene_build.hip, precond.hip, adaptive.hip and denoise.hip - and linked into one
     library: ~4 minutes of wall time instead of ~10 for a single unit (PSDR_BUILD_JOBS=1 compiles them one after the other)."""
     os.makedirs(LIBDIR, exist_ok=True)
     flags = [f for f in HIP_FLAGS if f != "-shared"] + list(extra_flags)
@@ -153,14 +155,15 @@ def _lint_units(hipcc, flags, units, objdir):
 def hip_units(flags=()):
     """the translation units of the library as (name, source, defines, dependencies): object api_<name>.o is compiled again when its source, one of
     its dependencies or a flag changed - the host unit `main` from api.hip, the kernel units `tu<k>` from render_units.hip (NOT from api.hip: an
-    edit of the host code leaves them alone), `scene` from scene_build.hip, `precond` from precond.hip, `adaptive` from adaptive.hip"""
+    edit of the host code leaves them alone), `scene` from scene_build.hip, `precond` from precond.hip, `adaptive` from adaptive.hip, `denoise` from denoise.hip"""
     # development builds (-DPSDR_CLS_MASK=m: the host code launches the kernels of those scene classes only) skip the other classes' units
     mask = 15
     for f in flags:
         if f.startswith("-DPSDR_CLS_MASK="):
             mask = int(f.split("=")[1])
     return [("main", API_SRC, [], API_DEPS)] + [("tu%d" % k, UNITS_SRC, ["-DPSDR_TU=%d" % k], KERNEL_DEPS) for k in (1, 6, 8, 2, 4, 10, 7, 5, 3, 9) if UNIT_CLASS_BIT[k] & mask] + \
-           [("scene", SCENE_SRC, [], SCENE_DEPS), ("precond", PRECOND_SRC, [], PRECOND_DEPS), ("adaptive", ADAPTIVE_SRC, [], ADAPTIVE_DEPS)]
+           [("scene", SCENE_SRC, [], SCENE_DEPS), ("precond", PRECOND_SRC, [], PRECOND_DEPS), ("adaptive", ADAPTIVE_SRC, [], ADAPTIVE_DEPS),
+            ("denoise", DENOISE_SRC, [], DENOISE_DEPS)]
 
 
 def _compile_hip(flags, target, objdir):

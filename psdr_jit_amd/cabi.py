@@ -13,6 +13,7 @@ SYMBOLS = [
     "psdr_hip_guiding_destroy", "psdr_hip_tea64", "psdr_hip_sampler_floats",
     "psdr_hip_precond_create", "psdr_hip_precond_destroy", "psdr_hip_precond_apply", "psdr_hip_precond_solve",
     "psdr_hip_adaptive_scratch_bytes", "psdr_hip_adaptive_bits", "psdr_hip_adaptive_counts", "psdr_hip_adaptive_expand", "psdr_hip_adaptive_merge", "psdr_hip_adaptive_merge_adj",
+    "psdr_hip_denoise_create", "psdr_hip_denoise_apply", "psdr_hip_denoise_apply_adj", "psdr_hip_denoise_destroy",
 ]
 
 
@@ -91,6 +92,10 @@ def lib():
         L.psdr_hip_adaptive_expand.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
         L.psdr_hip_adaptive_merge.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]
         L.psdr_hip_adaptive_merge_adj.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.psdr_hip_denoise_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p]
+        L.psdr_hip_denoise_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.psdr_hip_denoise_apply_adj.argtypes = L.psdr_hip_denoise_apply.argtypes
+        L.psdr_hip_denoise_destroy.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
