@@ -107,17 +107,25 @@ def _columns(orc, spec, mesh, vertices, term):
 def reference(orc, spec, mesh, vertices, term):
     """The oracle's record of one term of one family.
     -> {term, vertices, mask [K, N] (True: the pixel is settled in all three columns of the vertex), w [K, N, 3] float32 (= w_k),
-        G, S, S_full, r [K, 3], nonzero, resolved [K, 3], Q50, G_nudged [8, K, 3], kept_share [K, 3] (S / S_full)}"""
+        G, S, S_full, r [K, 3], nonzero, resolved [K, 3], Q50, G_nudged [8, K, 3], kept_share [K, 3] (S / S_full), lit [K, 3] (pixels in which the column is not zero)}"""
     assert (spec.width, spec.height, spec.spp, spec.sppe, spec.sppse) == (RES, RES, SPP, SPP, SPP)
     spec = clear_tangents(copy.deepcopy(spec))
     vertices = tuple(int(k) for k in vertices)
     delta = lp.rounding_delta(orc.OracleScene(spec, [0]), spec)
     base = _columns(orc, spec, mesh, vertices, term)
     nudges = [_columns(orc, lp.nudged(spec, n, delta), mesh, vertices, term) for n in range(len(lp.NUDGES))]
-    K = len(vertices)
+    return measure(base, nudges, term, vertices)
+
+
+def measure(base, nudges, term, rows):
+    """The record of K rows of A columns each (a vertex and its three axes; a texel, a vertex or a constant and its channels, tests/value_adjoint.py)
+    from their forward-derivative columns: base [K, A, N, 3] on the scene itself, nudges the same on each of the eight nudged scenes -> reference()'s record"""
+    base = np.asarray(base, np.float64)
+    K, A = base.shape[:2]
+    assert base.shape == (K, A, N, 3) and len(rows) == K and all(nd.shape == base.shape for nd in nudges)
     mask = np.ones((K, N), bool)
     for i in range(K):
-        for a in range(3):
+        for a in range(A):
             col = base[i, a]
             spread = np.zeros(N)
             for nd in nudges:
@@ -139,12 +147,12 @@ def reference(orc, spec, mesh, vertices, term):
     safe = np.where(S > 0, S, 1.0)
     r = np.where(S > 0, np.abs(G_nudged - G[None]).max(axis=0) / safe, 0.0)
     Q50 = float(np.median(r[resolved])) if resolved.any() else 0.0
-    return dict(term=term, vertices=vertices, mask=mask, w=w, G=G, S=S, S_full=S_full, r=r, nonzero=nonzero, resolved=resolved, Q50=Q50,
-                G_nudged=G_nudged, kept_share=np.where(nonzero, S / np.where(nonzero, S_full, 1.0), 0.0))
+    return dict(term=term, vertices=tuple(rows), mask=mask, w=w, G=G, S=S, S_full=S_full, r=r, nonzero=nonzero, resolved=resolved, Q50=Q50,
+                G_nudged=G_nudged, kept_share=np.where(nonzero, S / np.where(nonzero, S_full, 1.0), 0.0), lit=(np.abs(base).max(axis=3) > 0).sum(axis=2))
 
 
 def compare(got, rec):
-    """got [K, 3]: the gradient of sum(img * w_k) with respect to vertex rec["vertices"][k], against reference()'s record.
+    """got [K, 3] (in general [K, A], A the record's columns per row): the gradient of sum(img * w_k) with respect to vertex rec["vertices"][k], against reference()'s record.
     -> {term, entries (non-zero), resolved, p50, Q50, ratio50, worst (the largest e / max(r, Q50, floor) of one entry), worst_entry (vertex, axis),
         unresolved: [(vertex, axis, got, G, kept share)], failures: [str]}; the comparison passes when failures is empty."""
     fails = []
@@ -158,9 +166,10 @@ def compare(got, rec):
         fails.append("%s: %d entries are not finite" % (rec["term"], int((~np.isfinite(g)).sum())))
         return row
     V = rec["vertices"]
+    what, col = rec.get("labels", ("vertex", "axis"))           # (tests/value_adjoint.py names its rows and columns itself)
     for i, a in zip(*np.nonzero(~rec["nonzero"])):                # zero in the oracle: zero here
         if g[i, a] != 0.0:
-            fails.append("%s: vertex %d axis %d is identically zero in the oracle, got %.3g" % (rec["term"], V[i], a, g[i, a]))
+            fails.append("%s: %s %s %s %d is identically zero in the oracle, got %.3g" % (rec["term"], what, V[i], col, a, g[i, a]))
     for i, a in zip(*np.nonzero(rec["nonzero"] & ~rec["resolved"])):
         row["unresolved"].append((V[i], int(a), float(g[i, a]), float(rec["G"][i, a]), float(rec["kept_share"][i, a])))
     res = rec["resolved"]
@@ -173,8 +182,8 @@ def compare(got, rec):
     i, a = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
     row["worst"], row["worst_entry"] = float(ratio[i, a]), (V[i], int(a))
     for i, a in zip(*np.nonzero(res & ~(e <= bound))):
-        fails.append("%s: vertex %d axis %d: got %.9g, oracle %.9g, |difference| / S = %.3g > %g x max(r = %.3g, Q50 = %.3g, %.3g)"
-                     % (rec["term"], V[i], a, g[i, a], rec["G"][i, a], e[i, a], lp.MARGIN, rec["r"][i, a], rec["Q50"], lp.ULP_FLOOR))
+        fails.append("%s: %s %s %s %d: got %.9g, oracle %.9g, |difference| / S = %.3g > %g x max(r = %.3g, Q50 = %.3g, %.3g)"
+                     % (rec["term"], what, V[i], col, a, g[i, a], rec["G"][i, a], e[i, a], lp.MARGIN, rec["r"][i, a], rec["Q50"], lp.ULP_FLOOR))
     row["p50"] = float(np.median(e[res]))
     row["ratio50"] = row["p50"] / base50
     if row["p50"] > lp.MARGIN * base50:
