@@ -570,6 +570,60 @@ int psdr_hip_denoise_apply(psdr_hip_denoise *denoise, const float *in, int32_t C
 int psdr_hip_denoise_apply_adj(psdr_hip_denoise *denoise, const float *d_out, int32_t C, float *d_in, void *stream);
 int psdr_hip_denoise_destroy(psdr_hip_denoise *denoise);
 
+/* VARIANCE-GUIDED A-TROUS DENOISER, ITS FROZEN OPERATOR AND THAT OPERATOR'S TRANSPOSE (csrc/hip/vdenoise.hip; psdr_jit_amd/vdenoise.py).  The denoiser
+ * above stops at edges of the guides only; this one also stops where two pixels' luminances differ by more than their variances explain (Dammertz et al.'s colour weight,
+ * normalised by variance as in SVGF, Schied et al. 2017), so that an illumination edge without a guide edge survives.  Device pointers throughout except `lum`, plain launches
+ * on `stream` (apply: two per level, frozen and frozen_adj: one per level), no synchronisation, no atomics (the same input gives the same bits).  Every call checks its
+ * arguments BEFORE any device call and returns non-zero with psdr_hip_last_error text for a NULL pointer, W or H < 1, W H > 2^24, L outside [1, 8], G outside [0, 8], C other
+ * than 1 or 3, in == out, var == var_out, k negative or not finite, eps not positive or not finite, a luminance coefficient that is not finite, and a frozen, frozen_adj or
+ * record call on a handle that holds no record.  Added under ABI 16 like the adaptive and denoise entry points: nothing existing changed.
+ *
+ * The operator.  Frame W x H, pixel p = y W + x.  Image x [W H, C] float32, C in {1, 3}; variance v [W H] float32, the variance of the pixel's LUMINANCE estimate; guides g
+ * [W H, G] float32, pre-scaled as for psdr_hip_denoise; luminance coefficients a[C] on the host; k = 1 / sigma_l^2 >= 0; eps > 0.  The state is (x_l, v_l), x_0 = x, v_0 = v.
+ * Level l = 0 .. L - 1 has stride s = 2^l and the taps (i, j) in {-2 .. 2}^2 with h = [1, 4, 6, 4, 1] / 16, exactly as above:
+ *     lum_l(p) = a_0 x_l,0(p) + a_1 x_l,1(p) + a_2 x_l,2(p)          (this order, no contraction; C = 1: a_0 x_l,0(p))
+ *     vt_l(p)  = 3 x 3 prefilter of v_l at UNIT stride: coefficients [1, 2, 1] x [1, 2, 1] / 16 over the taps inside the frame, divided by the sum of the coefficients that
+ *                were inside
+ *     the tap q = p + s (i, j) exists only inside the frame
+ *     d2 = sum_k (g_k(p) - g_k(q))^2                                 (as above)
+ *     z  = k (lum_l(p) - lum_l(q))^2 / (vt_l(p) + vt_l(q) + eps)
+ *     w_l(p, q) = h(i) h(j) exp(-(d2 + z)) if 0 <= d2 + z < inf and vt_l(p) + vt_l(q) + eps is finite, otherwise 0
+ *     the centre tap always has weight h(0)^2, whatever the inputs hold
+ *     N_l(p) = sum_q w_l(p, q) >= 9/64
+ *     x_{l+1}(p) = sum_q w_l(p, q) x_l(q) / N_l(p)
+ *     v_{l+1}(p) = sum_q w_l(p, q)^2 v_l(q) / N_l(p)^2
+ * A tap whose weight is 0 adds nothing to either sum, whatever x_l(q) and v_l(q) hold.  So a NaN or Inf in x or a guide at q cuts q off - no tap reaches it or leaves it - and
+ * q's own centre tap hands its value through; a NaN or Inf in v at q makes vt_l non-finite on q's 3 x 3 unit-stride neighbourhood and cuts those (up to nine) pixels off
+ * (the second condition on w_l is there for v = Inf, which would otherwise give z = 0 and let the infinite variance spread).
+ * z is the squared difference of two estimates over the variance of that difference, in units of sigma_l^2.  w_l is symmetric in (p, q).  With k = 0 the image part is the
+ * operator of psdr_hip_denoise, bit for bit.  v_{l+1} is the exact variance of x_{l+1}'s luminance for ONE level with independent pixels and the weights held fixed; over
+ * several levels a level's inputs are correlated and it is SVGF's approximation, not a variance.
+ * In float32 as written: lum by C multiplications and C - 1 additions; vt by nine multiply-and-adds row by row with the integer coefficients 1 2 1 / 2 4 2 / 1 2 1 and one
+ * division by their sum; d2 as above; z = (k * (dl * dl)) / ((vt(p) + vt(q)) + eps) with dl = lum(p) - lum(q); expf(-(d2 + z)); the 25 taps added row by row; 1 / N_l by one
+ * IEEE division, then one multiplication by it per channel, and two for v_{l+1}.
+ *
+ * The record and the frozen operator.  The weights depend on the image, so the map x -> x_L is not linear.  apply RECORDS what the weights were formed from: three planes per
+ * level, lum_l, vt_l and 1 / N_l, beside k and eps.  With these held fixed, D_x = A_{L-1} ... A_0, A_l u (p) = (sum_q w_l(p, q) u(q)) (1 / N_l)(p), is linear; frozen applies
+ * it to any image (C need not be the recording's) and frozen_adj applies D_x^T = A_0^T ... A_{L-1}^T, A_l^T y (q) = sum_p w_l(q, p) (y(p) (1 / N_l)(p)): the same gather with
+ * the source pre-multiplied, no scatter.  Both form z and w from the record with apply's float32 expression sequence: frozen(x) after apply(x, v) returns apply's bits.
+ * D_x^T g is the EXACT TRANSPOSE OF THE FROZEN OPERATOR, which is what a loss that treats the weights as constants (stop-gradient) differentiates; it is NOT the derivative of
+ * the nonlinear map x -> x_L, and v receives no gradient.
+ *
+ * create copies the guides into planes and allocates the record and the work frames: (G + 3 L + 8) W H floats.  The record alone is 12 L W H bytes: 252 MB at 2048 x 2048
+ * and L = 5.  G == 0 takes guides == NULL.  The handle holds the work frames: one call at a time per handle.  A new apply replaces the record. */
+typedef struct psdr_hip_vdenoise psdr_hip_vdenoise;
+int psdr_hip_vdenoise_create(const float *guides, int32_t G, int32_t W, int32_t H, int32_t L, psdr_hip_vdenoise **out, void *stream);
+/* out = x_L, var_out = v_L (may be NULL); `lum`: C floats on the HOST; in / out and var / var_out may not alias; records */
+int psdr_hip_vdenoise_apply(psdr_hip_vdenoise *vdenoise, const float *in, int32_t C, const float *var, const float *lum, float k, float eps, float *out, float *var_out,
+                            void *stream);
+/* out = D_x in with the last apply's record */
+int psdr_hip_vdenoise_frozen(psdr_hip_vdenoise *vdenoise, const float *in, int32_t C, float *out, void *stream);
+/* d_in = D_x^T d_out */
+int psdr_hip_vdenoise_frozen_adj(psdr_hip_vdenoise *vdenoise, const float *d_out, int32_t C, float *d_in, void *stream);
+/* out [L][3][W H] = the record: lum_l, vt_l, 1 / N_l for l = 0 .. L - 1 (a device-to-device copy; what the tests feed the restatement) */
+int psdr_hip_vdenoise_record(psdr_hip_vdenoise *vdenoise, float *out, void *stream);
+int psdr_hip_vdenoise_destroy(psdr_hip_vdenoise *vdenoise);
+
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);
 int psdr_hip_sampler_floats(uint64_t seed_value, uint64_t lane, uint64_t skip, int32_t n, float *out_dev, void *stream);

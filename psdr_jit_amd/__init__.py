@@ -1643,3 +1643,5 @@ from .precond import laplacian_csr, LaplacianPreconditioner, AdamUniform  # noqa
 from .adaptive import adaptive_weights, PixelPlan, render_c_adaptive  # noqa: E402,F401
 # the edge-avoiding a-trous denoiser guided by first-hit fields, and its transpose (denoise.py; kernels: csrc/hip/denoise.hip)
 from .denoise import Denoiser, first_hit_guides  # noqa: E402,F401
+# the variance-guided a-trous denoiser that keeps illumination edges, its frozen operator and that operator's transpose (vdenoise.py; kernels: csrc/hip/vdenoise.hip)
+from .vdenoise import VarianceDenoiser, luminance_variance  # noqa: E402,F401
