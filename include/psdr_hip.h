@@ -624,6 +624,41 @@ int psdr_hip_vdenoise_frozen_adj(psdr_hip_vdenoise *vdenoise, const float *d_out
 int psdr_hip_vdenoise_record(psdr_hip_vdenoise *vdenoise, float *out, void *stream);
 int psdr_hip_vdenoise_destroy(psdr_hip_vdenoise *vdenoise);
 
+/* MESH SUBDIVISION AS A LINEAR OPERATOR AND ITS TRANSPOSE (csrc/hip/subdiv.hip; psdr_jit_amd/subdiv.py).  One level of Loop or midpoint subdivision
+ * takes the n_in coarse vertices to n_out = n_in + (number of edges) fine ones; on any per-vertex array (positions, uv pairs, scalar or RGB values) that is the product with
+ * a sparse matrix S (n_out x n_in, rows that sum to 1), and the gradient of a loss on the fine array reaches the coarse one through S^T.  One level is one handle; levels
+ * are chained by the caller.  Device pointers in apply / apply_adj, one plain launch on `stream` each, no synchronisation, no copy to the host, no atomics (the same input
+ * gives the same bits).  Added under ABI 16 like the denoise entry points: nothing existing changed.
+ *
+ * The matrices.  create takes S and S^T, BOTH as CSR in HOST arrays (copied; the caller's again when the call returns):
+ *     row_begin[n_out + 1], col[nnz] in [0, n_in),  weight[nnz]          row r of S   is the entries k in [row_begin[r], row_begin[r + 1])
+ *     t_row_begin[n_in + 1], t_col[nnz] in [0, n_out), t_weight[nnz]     row j of S^T likewise: the inverted index of S, every list in a fixed (ascending) order
+ * The topology, the float32 weights (Warren's Loop weights, crease and corner rules, or the midpoint rule) and the transpose are the host's business
+ * (psdr_jit_amd/subdiv.py: subdivision_level); the device never forms a transpose and never scatters.  The price is a second copy of the pattern: 16 nnz bytes of
+ * indices and weights in all, beside the two row_begin arrays.
+ * create validates the host arrays BEFORE any device call and returns non-zero with psdr_hip_last_error text unless: out and both row_begin arrays are not NULL; n_in and
+ * n_out are positive and 4 n_out, 4 n_in < 2^31; both row_begin arrays start at 0 and are monotonic; both end at the same nnz (an int32, so < 2^31); col, weight, t_col,
+ * t_weight are not NULL when nnz > 0; every col is in [0, n_in) and every t_col in [0, n_out); every weight is finite.  No bad index reaches a kernel.
+ * create does NOT check that the second CSR is the transpose of the first: two unrelated matrices of the same nnz are accepted, and apply_adj is then simply the product
+ * with the second one.  The Python layer builds both from one list of entries and is what guarantees it.
+ *
+ * The product.  x, y, d_y, d_x are row-major [rows, C] float32, C in [1, 4]; input and output may not alias.  Both directions are the same kernel over a different CSR: one
+ * lane owns one output row r and computes, per channel c and in float32,
+ *     acc = 0;   for k = row_begin[r] .. row_begin[r + 1] - 1 in this order:  acc = fmaf(weight[k], x[col[k] C + c], acc);   y[r C + c] = acc
+ * (an empty row gives 0).  Rows beyond one pass of the 1024 x 256 grid are taken by a grid-stride loop.  A lane walks its row alone: a launch takes as long as its longest
+ * row, which is accepted for meshes (valence is bounded almost everywhere; the transpose row of a vertex of valence d has about 3 d + 1 entries).
+ * Other C, a NULL pointer, a NULL handle or x == y return non-zero before anything is launched. */
+typedef struct psdr_hip_subdiv psdr_hip_subdiv;
+int psdr_hip_subdiv_create(int32_t n_in, int32_t n_out,
+        const int32_t *row_begin, const int32_t *col, const float *weight,         /* S   : n_out rows, columns < n_in  */
+        const int32_t *t_row_begin, const int32_t *t_col, const float *t_weight,   /* S^T : n_in rows,  columns < n_out */
+        psdr_hip_subdiv **out, void *stream);
+/* y[n_out, C] = S x, x [n_in, C] */
+int psdr_hip_subdiv_apply(const psdr_hip_subdiv *s, const float *x, int32_t C, float *y, void *stream);
+/* d_x[n_in, C] = S^T d_y, d_y [n_out, C] */
+int psdr_hip_subdiv_apply_adj(const psdr_hip_subdiv *s, const float *d_y, int32_t C, float *d_x, void *stream);
+int psdr_hip_subdiv_destroy(psdr_hip_subdiv *s);
+
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);
 int psdr_hip_sampler_floats(uint64_t seed_value, uint64_t lane, uint64_t skip, int32_t n, float *out_dev, void *stream);

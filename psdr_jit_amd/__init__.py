@@ -1645,3 +1645,5 @@ from .adaptive import adaptive_weights, PixelPlan, render_c_adaptive  # noqa: E4
 from .denoise import Denoiser, first_hit_guides  # noqa: E402,F401
 # the variance-guided a-trous denoiser that keeps illumination edges, its frozen operator and that operator's transpose (vdenoise.py; kernels: csrc/hip/vdenoise.hip)
 from .vdenoise import VarianceDenoiser, luminance_variance  # noqa: E402,F401
+# Loop / midpoint mesh subdivision as a differentiable operator on per-vertex arrays, and its transpose (subdiv.py; kernels: csrc/hip/subdiv.hip)
+from .subdiv import Subdivision, subdivision_level  # noqa: E402,F401

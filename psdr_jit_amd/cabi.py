@@ -15,6 +15,7 @@ SYMBOLS = [
     "psdr_hip_adaptive_scratch_bytes", "psdr_hip_adaptive_bits", "psdr_hip_adaptive_counts", "psdr_hip_adaptive_expand", "psdr_hip_adaptive_merge", "psdr_hip_adaptive_merge_adj",
     "psdr_hip_denoise_create", "psdr_hip_denoise_apply", "psdr_hip_denoise_apply_adj", "psdr_hip_denoise_destroy",
     "psdr_hip_vdenoise_create", "psdr_hip_vdenoise_apply", "psdr_hip_vdenoise_frozen", "psdr_hip_vdenoise_frozen_adj", "psdr_hip_vdenoise_record", "psdr_hip_vdenoise_destroy",
+    "psdr_hip_subdiv_create", "psdr_hip_subdiv_apply", "psdr_hip_subdiv_apply_adj", "psdr_hip_subdiv_destroy",
 ]
 
 
@@ -103,6 +104,10 @@ def lib():
         L.psdr_hip_vdenoise_frozen_adj.argtypes = L.psdr_hip_vdenoise_frozen.argtypes
         L.psdr_hip_vdenoise_record.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.psdr_hip_vdenoise_destroy.argtypes = [C.c_void_p]
+        L.psdr_hip_subdiv_create.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.POINTER(C.c_void_p), C.c_void_p]
+        L.psdr_hip_subdiv_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.psdr_hip_subdiv_apply_adj.argtypes = L.psdr_hip_subdiv_apply.argtypes
+        L.psdr_hip_subdiv_destroy.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
