@@ -24,12 +24,6 @@ CORE_LIB = os.path.join(HERE, "_psdr_core" + (sysconfig.get_config_var("EXT_SUFF
 API_SRC = os.path.join(CSRC, "hip", "api.hip")                  # the host unit: the render entry points (C ABI) and the small kernels
 UNITS_SRC = os.path.join(CSRC, "hip", "render_units.hip")       # the ten kernel units: the heavy kernel templates of render_kernels.h, one list of instantiations each (see hip_units)
 SCENE_SRC = os.path.join(CSRC, "hip", "scene_build.hip")        # psdr_hip_scene_create / _update: tree build and refit, uploads (blob_layout.h, blob_rows.h: the blob's layout and row formats)
-PRECOND_SRC = os.path.join(CSRC, "hip", "precond.hip")         # psdr_hip_precond_*: the Laplacian vertex preconditioner, its matrix-vector product and CG solver
-ADAPTIVE_SRC = os.path.join(CSRC, "hip", "adaptive.hip")       # psdr_hip_adaptive_*: sample counts from a weight map (scan), the pixel list, the segment fold and its transpose
-DENOISE_SRC = os.path.join(CSRC, "hip", "denoise.hip")         # psdr_hip_denoise_*: the edge-avoiding a-trous denoiser and its transpose, one LDS-tiled gather per level
-VDENOISE_SRC = os.path.join(CSRC, "hip", "vdenoise.hip")       # psdr_hip_vdenoise_*: the variance-guided a-trous denoiser, its recorded (frozen) operator and that operator's transpose
-SUBDIV_SRC = os.path.join(CSRC, "hip", "subdiv.hip")           # psdr_hip_subdiv_*: one level of Loop / midpoint subdivision as a sparse operator (CSR from the host) and its transpose
-HIP_SRCS = [API_SRC, UNITS_SRC, SCENE_SRC, PRECOND_SRC, ADAPTIVE_SRC, DENOISE_SRC, VDENOISE_SRC, SUBDIV_SRC]
 BUILD_DEPS = [os.path.join(HERE, "isa_lint.py")]          # part of the recipe: a change of the lint re-builds (and re-lints) the library
 _H = lambda *names: [os.path.join(CSRC, "hip", f) for f in names]
 # every quoted #include a unit's source reaches is in that unit's list (tests/test_build_deps.py walks the include graph)
@@ -38,12 +32,17 @@ COMMON_DEPS = DEVICE_DEPS + _H("scene_obj.h") + [os.path.join(ROOT, "include", "
 KERNEL_DEPS = DEVICE_DEPS + _H("render_kernels.h", "sampler.h", "shade.h", "edges.h", "paths.h", "adj_layout.h", "adjoint.h", "adjoint_mat.h", "isect_ad.h", "microfacet.h") + [os.path.join(CSRC, "common", "envmath.h")] + BUILD_DEPS
 API_DEPS = sorted(set(COMMON_DEPS + KERNEL_DEPS))      # the host unit launches the heavy kernels: it sees their header, they do not see api.hip
 SCENE_DEPS = COMMON_DEPS + _H("bvh.h", "filter.h", "blob_rows.h", "blob_layout.h") + [os.path.join(CSRC, "host", "hnum.h"), os.path.join(CSRC, "host", "edge_select.h")] + BUILD_DEPS
-PRECOND_DEPS = [os.path.join(ROOT, "include", "psdr_hip.h")] + BUILD_DEPS
-ADAPTIVE_DEPS = [os.path.join(ROOT, "include", "psdr_hip.h")] + BUILD_DEPS
-DENOISE_DEPS = [os.path.join(ROOT, "include", "psdr_hip.h")] + BUILD_DEPS
-VDENOISE_DEPS = [os.path.join(ROOT, "include", "psdr_hip.h")] + BUILD_DEPS
-SUBDIV_DEPS = [os.path.join(ROOT, "include", "psdr_hip.h")] + BUILD_DEPS
-HIP_DEPS = sorted(set(API_DEPS + SCENE_DEPS + PRECOND_DEPS + ADAPTIVE_DEPS + DENOISE_DEPS + VDENOISE_DEPS + SUBDIV_DEPS))
+# the stand-alone operators, one source file each: (unit, source, what it holds, the headers of csrc/hip it includes beside include/psdr_hip.h); compiled in this order
+OPERATOR_UNITS = [
+    ("precond", "precond.hip", "psdr_hip_precond_*: the Laplacian vertex preconditioner, its matrix-vector product and CG solver", ()),
+    ("adaptive", "adaptive.hip", "psdr_hip_adaptive_*: sample counts from a weight map (scan), the pixel list, the segment fold and its transpose", ()),
+    ("denoise", "denoise.hip", "psdr_hip_denoise_*: the edge-avoiding a-trous denoiser and its transpose, one LDS-tiled gather per level", ("atrous.h",)),
+    ("vdenoise", "vdenoise.hip", "psdr_hip_vdenoise_*: the variance-guided a-trous denoiser, its recorded (frozen) operator and that operator's transpose", ("atrous.h",)),
+    ("subdiv", "subdiv.hip", "psdr_hip_subdiv_*: one level of Loop / midpoint subdivision as a sparse operator (CSR from the host) and its transpose", ()),
+]
+OPERATOR_TUS = [(name, _H(src)[0], [], [os.path.join(ROOT, "include", "psdr_hip.h")] + _H(*headers) + BUILD_DEPS) for name, src, _what, headers in OPERATOR_UNITS]      # hip_units()'s tuples
+HIP_SRCS = [API_SRC, UNITS_SRC, SCENE_SRC] + [u[1] for u in OPERATOR_TUS]
+HIP_DEPS = sorted(set(API_DEPS + SCENE_DEPS + [d for u in OPERATOR_TUS for d in u[3]]))
 HOST_SRCS = [os.path.join(CSRC, "host", f) for f in ("scene_host.cpp", "bindings.cpp", "exr_piz.cpp")]
 HOST_DEPS = [os.path.join(CSRC, "host", f) for f in ("scene_host.h", "hnum.h", "edge_select.h", "exr_piz.h")] + [os.path.join(ROOT, "include", "psdr_hip.h"), os.path.join(CSRC, "common", "envmath.h"), os.path.join(CSRC, "common", "threads.h")]
 
@@ -93,9 +92,9 @@ UNIT_CLASS_BIT = {1: 1, 2: 1, 6: 1, 8: 1, 3: 2, 9: 2, 4: 4, 7: 4, 10: 4, 5: 8}  
 
 
 def build_hip(force=False, extra_flags=(), target=None):
-    """Seventeen translation units compiled in parallel - api.hip (the host code with the small kernels), render_units.hip ten times (-DPSDR_TU=k:
-    unit k only instantiates list k of the heavy kernel templates, one scene class each), scene_build.hip, precond.hip, adaptive.hip, denoise.hip, vdenoise.hip and subdiv.hip - and linked into one
-    library: ~4 minutes of wall time instead of ~10 for a single unit (PSDR_BUILD_JOBS=1 compiles them one after the other)."""
+    """The translation units of hip_units() compiled in parallel - render_units.hip ten times (-DPSDR_TU=k: unit k only instantiates list k of the heavy kernel
+    templates, one scene class each) - and linked into one library: ~4 minutes of wall time instead of ~10 for a single unit (PSDR_BUILD_JOBS=1 compiles them one
+    after the other)."""
     os.makedirs(LIBDIR, exist_ok=True)
     flags = [f for f in HIP_FLAGS if f != "-shared"] + list(extra_flags)
     if target is not None:
@@ -159,15 +158,14 @@ def _lint_units(hipcc, flags, units, objdir):
 def hip_units(flags=()):
     """the translation units of the library as (name, source, defines, dependencies): object api_<name>.o is compiled again when its source, one of
     its dependencies or a flag changed - the host unit `main` from api.hip, the kernel units `tu<k>` from render_units.hip (NOT from api.hip: an
-    edit of the host code leaves them alone), `scene` from scene_build.hip, `precond` from precond.hip, `adaptive` from adaptive.hip, `denoise` from denoise.hip, `vdenoise` from vdenoise.hip, `subdiv` from subdiv.hip"""
+    edit of the host code leaves them alone), `scene` from scene_build.hip, and the rows of OPERATOR_UNITS"""
     # development builds (-DPSDR_CLS_MASK=m: the host code launches the kernels of those scene classes only) skip the other classes' units
     mask = 15
     for f in flags:
         if f.startswith("-DPSDR_CLS_MASK="):
             mask = int(f.split("=")[1])
     return [("main", API_SRC, [], API_DEPS)] + [("tu%d" % k, UNITS_SRC, ["-DPSDR_TU=%d" % k], KERNEL_DEPS) for k in (1, 6, 8, 2, 4, 10, 7, 5, 3, 9) if UNIT_CLASS_BIT[k] & mask] + \
-           [("scene", SCENE_SRC, [], SCENE_DEPS), ("precond", PRECOND_SRC, [], PRECOND_DEPS), ("adaptive", ADAPTIVE_SRC, [], ADAPTIVE_DEPS),
-            ("denoise", DENOISE_SRC, [], DENOISE_DEPS), ("vdenoise", VDENOISE_SRC, [], VDENOISE_DEPS), ("subdiv", SUBDIV_SRC, [], SUBDIV_DEPS)]
+           [("scene", SCENE_SRC, [], SCENE_DEPS)] + OPERATOR_TUS
 
 
 def _compile_hip(flags, target, objdir):

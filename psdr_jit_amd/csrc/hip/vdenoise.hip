@@ -11,35 +11,27 @@
 // An apply RECORDS lum_l, vt_l and 1 / N_l, three planes per level.  The frozen operator D_x = A_{L-1} ... A_0 forms the weights from the record and is linear in what it
 // is applied to; w_l is symmetric, so A_l^T y (q) = sum_p w_l(q, p) (y(p) / N_l(p)): the same gather with the source pre-multiplied by 1 / N_l, no scatter, no atomics.
 //
-// k_prefilter: v_l -> vt_l, one thread per pixel, nine cached loads.  k_vlevel<G, C, mode>: one launch per level; as in denoise.hip a 256-thread workgroup owns a 32 x 8
-// tile of one coset x = a, y = b (mod s) and stages the 36 x 12 halo as planes in LDS: the G guides, the C values, lum, vt and, in apply mode, v - at most 14 planes of
-// 432 words, 24.2 KB, six workgroups to a CU.  Apply mode forms lum while it stages; the frozen modes read the recorded plane, and form z and w with the SAME float32
-// expression sequence (one function, weight()), so that frozen(x) after apply(x, v) gives apply's bits.  The 25 taps are unrolled and added in one order (j outer, i inner).
-// No fast-math, no contraction in this unit: with k = 0 the image part gives the bits of denoise.hip.
+// k_prefilter: v_l -> vt_l, one thread per pixel, nine cached loads.  k_vlevel<G, C, mode>: one launch per level, on the tile scheme of atrous.h; it stages the G guides,
+// the C values, lum, vt and, in apply mode, v - at most 14 planes of 432 words, 24.2 KB, six workgroups to a CU.  Apply mode forms lum while it stages; the frozen modes
+// read the recorded plane, and form z and w with the SAME float32 expression sequence (one function, weight()), so that frozen(x) after apply(x, v) gives apply's bits.
+// The 25 taps are unrolled and added in one order (j outer, i inner).  No fast-math, no contraction in this unit: with k = 0 the image part gives the bits of denoise.hip.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
 #include <string>
 
 #include "../../../include/psdr_hip.h"
+#include "atrous.h"
 
-namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
-#define VCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return psdr::api_fail(std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+using namespace psdr::atrous;
 
 namespace {
 
-constexpr int kThreads = 256;                               // 4 waves
-constexpr int kTX = 32, kTY = 8;                            // a workgroup's tile of a coset
-constexpr int kHX = kTX + 4, kHY = kTY + 4, kHalo = kHX * kHY;          // 36 x 12 = 432 words per plane
-constexpr int kMaxG = 8, kMaxC = 3, kMaxL = 8;
-constexpr int kMaxPixels = 1 << 24;
+constexpr int kMaxC = 3;
 
 enum { kApply = 0, kFrozen = 1, kFrozenAdj = 2 };
 
-struct VLevel {
-    int W, H, s;
-    int tiles_x;                  // blockIdx.x = tile row * tiles_x + tile column, sized for coset (0, 0), the largest
-    int cosets_x;                 // min(s, W): blockIdx.y = b cosets_x + a
+struct VLevel : Frame {
     const float *guides;          // [G][W H]
     const float *src;             // [W H, C]
     const float *v;               // [W H], v_l (kApply only)
@@ -51,11 +43,6 @@ struct VLevel {
     float a[3];                   // luminance coefficients (kApply only)
     float k, eps;
 };
-
-__device__ inline float tap_weight(int i, int j) {          // h(i) h(j), exact: k / 256
-    const int hi = i == 0 ? 6 : ((i == 1 || i == -1) ? 4 : 1), hj = j == 0 ? 6 : ((j == 1 || j == -1) ? 4 : 1);
-    return (float) (hi * hj) * (1.f / 256.f);
-}
 
 // exp(-(d2 + z)), the one expression sequence of all three modes
 __device__ inline float weight(float d2, float lp, float lq, float vp, float vq, float k, float eps) {
@@ -70,17 +57,10 @@ template <int G, int C, int MODE> __global__ void __launch_bounds__(kThreads) k_
     constexpr int kLum = G + C, kVt = G + C + 1, kV = G + C + 2;
     constexpr int kPlanes = G + C + (MODE == kApply ? 3 : 2);
     __shared__ float lds[kPlanes * kHalo];
-    const int s = A.s, n = A.W * A.H;
-    const int a = (int) blockIdx.y % A.cosets_x, b = (int) blockIdx.y / A.cosets_x;
-    const int wd = (A.W - a + s - 1) / s, hd = (A.H - b + s - 1) / s;          // the coset's decimated image (a < W, b < H: at least 1 x 1)
-    const int tx0 = ((int) blockIdx.x % A.tiles_x) * kTX, ty0 = ((int) blockIdx.x / A.tiles_x) * kTY;
-    if (tx0 >= wd || ty0 >= hd) return;                                        // a smaller coset than (0, 0): the whole workgroup leaves
+    ATROUS_TILE(A, blockIdx, return);                                          // s, n, the coset (a, b), wd x hd, the tile's origin (tx0, ty0)
     for (int idx = threadIdx.x; idx < kHalo; idx += kThreads) {
-        const int hx = tx0 - 2 + idx % kHX, hy = ty0 - 2 + idx / kHX;
-        const bool inside = hx >= 0 && hx < wd && hy >= 0 && hy < hd;
-        const int q = inside ? (b + hy * s) * A.W + a + hx * s : 0;            // (inside: a frame pixel, below 2^24)
-#pragma unroll
-        for (int g = 0; g < G; ++g) lds[g * kHalo + idx] = inside ? A.guides[(size_t) g * n + q] : 0.f;
+        ATROUS_HALO_SLOT(A, idx);                                              // inside, q
+        ATROUS_STAGE_GUIDES(G, lds, A.guides, idx);
         const float scale = MODE == kFrozenAdj ? (inside ? A.inv_n[q] : 0.f) : 1.f;
         float x[C];
 #pragma unroll
@@ -100,14 +80,7 @@ template <int G, int C, int MODE> __global__ void __launch_bounds__(kThreads) k_
         lds[kVt * kHalo + idx] = inside ? A.vt[q] : 0.f;
     }
     __syncthreads();
-    const int lx = threadIdx.x % kTX, ly = threadIdx.x / kTX;
-    const int dx = tx0 + lx, dy = ty0 + ly;
-    if (dx >= wd || dy >= hd) return;                                          // (after the only barrier)
-    const int p = (b + dy * s) * A.W + a + dx * s;                             // the thread's pixel
-    const int centre = (ly + 2) * kHX + lx + 2;                                // and its word in a halo plane
-    bool okx[5], oky[5];                                                       // tap column i - 2 / row j - 2 lies inside the frame
-#pragma unroll
-    for (int t = 0; t < 5; ++t) { okx[t] = (unsigned) (dx + t - 2) < (unsigned) wd; oky[t] = (unsigned) (dy + t - 2) < (unsigned) hd; }
+    ATROUS_PIXEL(A, threadIdx.x, return);                                      // the thread's pixel p, its halo word `centre`, okx / oky
     float gc[G > 0 ? G : 1];
 #pragma unroll
     for (int g = 0; g < G; ++g) gc[g] = lds[g * kHalo + centre];
@@ -120,15 +93,10 @@ template <int G, int C, int MODE> __global__ void __launch_bounds__(kThreads) k_
 #pragma unroll
         for (int i = -2; i <= 2; ++i) {
             const bool ok = okx[i + 2] && oky[j + 2];
-            const int slot = centre + j * kHX + i;                                  // always inside the halo; a tap outside the frame weighs 0
+            const int slot = centre + j * kHX + i;                                  // a tap outside the frame weighs 0
             float e = 1.f;
             if (i != 0 || j != 0) {
-                float d2 = 0.f;
-#pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    const float d = gc[g] - lds[g * kHalo + slot];
-                    d2 += d * d;
-                }
+                const float d2 = guide_d2<G>(gc, lds, slot);
                 e = weight(d2, lc, lds[kLum * kHalo + slot], vc, lds[kVt * kHalo + slot], A.k, A.eps);
             }
             const float w = ok ? tap_weight(i, j) * e : 0.f;
@@ -176,22 +144,9 @@ __global__ void __launch_bounds__(kThreads) k_prefilter(const float *v, int W, i
     vt[p] = acc / sum;
 }
 
-// guides [n, G] -> planes [G][n]
-__global__ void __launch_bounds__(kThreads) k_vplanes(const float *guides, int n, int G, float *planes) {
-    const long long t = (long long) blockIdx.x * kThreads + threadIdx.x;
-    if (t >= (long long) n * G) return;
-    const int k = (int) (t / n), p = (int) (t % n);
-    planes[t] = guides[(size_t) p * G + k];
-}
-
-template <int G, int C, int MODE> void launch_form(const VLevel &A, hipStream_t st) {
-    VLevel B = A;
-    const int wd = (A.W + A.s - 1) / A.s, hd = (A.H + A.s - 1) / A.s;          // coset (0, 0)
-    B.tiles_x = (wd + kTX - 1) / kTX;
-    B.cosets_x = A.s < A.W ? A.s : A.W;
-    const int cosets_y = A.s < A.H ? A.s : A.H;          // (at most 128 x 128 cosets: below the 65535 of a grid's y dimension)
-    const long long tiles = (long long) B.tiles_x * ((hd + kTY - 1) / kTY);
-    k_vlevel<G, C, MODE><<<dim3((unsigned) tiles, (unsigned) (B.cosets_x * cosets_y)), kThreads, 0, st>>>(B);
+template <int G, int C, int MODE> void launch_form(VLevel A, hipStream_t st) {
+    const Grid grid = level_grid(A);
+    k_vlevel<G, C, MODE><<<dim3(grid.x, grid.y), kThreads, 0, st>>>(A);
 }
 
 template <int G, int MODE> void launch_c(int C, const VLevel &A, hipStream_t st) {
@@ -200,28 +155,15 @@ template <int G, int MODE> void launch_c(int C, const VLevel &A, hipStream_t st)
 }
 
 template <int MODE> void launch_level(int G, int C, const VLevel &A, hipStream_t st) {
-    switch (G) {
-        case 0: launch_c<0, MODE>(C, A, st); break;
-        case 1: launch_c<1, MODE>(C, A, st); break;
-        case 2: launch_c<2, MODE>(C, A, st); break;
-        case 3: launch_c<3, MODE>(C, A, st); break;
-        case 4: launch_c<4, MODE>(C, A, st); break;
-        case 5: launch_c<5, MODE>(C, A, st); break;
-        case 6: launch_c<6, MODE>(C, A, st); break;
-        case 7: launch_c<7, MODE>(C, A, st); break;
-        default: launch_c<8, MODE>(C, A, st); break;
-    }
+    dispatch_g(G, [&](auto g) { launch_c<decltype(g)::value, MODE>(C, A, st); });
 }
 
 } // namespace
 
-struct psdr_hip_vdenoise {
-    int W = 0, H = 0, G = 0, L = 0;
+struct psdr_hip_vdenoise : Handle {          // the block: guide planes [G][n] | record [L][3][n]: lum_l, vt_l, 1 / N_l | two work frames [n, kMaxC] | two variance frames [n]
     bool recorded = false;
     float k = 0.f, eps = 0.f;          // of the record
-    float *d_mem = nullptr;            // guide planes [G][n] | record [L][3][n]: lum_l, vt_l, 1 / N_l | two work frames [n, kMaxC] | two variance frames [n]
-    float *planes = nullptr, *record = nullptr, *work[2] = {nullptr, nullptr}, *vwork[2] = {nullptr, nullptr};
-    ~psdr_hip_vdenoise() { if (d_mem) (void) hipFree(d_mem); }
+    float *record = nullptr, *work[2] = {nullptr, nullptr}, *vwork[2] = {nullptr, nullptr};
 };
 
 namespace {
@@ -235,19 +177,14 @@ const char *check_frozen(const psdr_hip_vdenoise *h, const float *in, int32_t C,
     return nullptr;
 }
 
-// the recorded levels in the order of D_x (kFrozen: 0 .. L - 1) or of D_x^T (kFrozenAdj: L - 1 .. 0), ping-pong through the work frames; the last launch writes `out`
+// D_x (kFrozen: the recorded levels 0 .. L - 1) or D_x^T (kFrozenAdj: L - 1 .. 0)
 template <int MODE> int run_frozen(psdr_hip_vdenoise *h, const float *in, int C, float *out, hipStream_t st) {
-    const size_t n = (size_t) h->W * h->H;
-    const float *src = in;
-    for (int i = 0; i < h->L; ++i) {
-        const int l = MODE == kFrozen ? i : h->L - 1 - i;
-        float *dst = i == h->L - 1 ? out : h->work[i & 1];
+    const size_t n = h->pixels();
+    ping_pong(h->L, MODE == kFrozen, in, out, h->work, [&](int l, const float *src, float *dst) {
         float *rec = h->record + (size_t) l * 3 * n;
-        VLevel A{h->W, h->H, 1 << l, 0, 0, h->planes, src, nullptr, rec + n, rec, rec + 2 * n, dst, nullptr, {0.f, 0.f, 0.f}, h->k, h->eps};
-        launch_level<MODE>(h->G, C, A, st);
-        src = dst;
-    }
-    VCHK(hipGetLastError());
+        launch_level<MODE>(h->G, C, VLevel{{h->W, h->H, 1 << l, 0, 0}, h->planes, src, nullptr, rec + n, rec, rec + 2 * n, dst, nullptr, {0.f, 0.f, 0.f}, h->k, h->eps}, st);
+    });
+    ATROUS_CHK(hipGetLastError());
     return 0;
 }
 
@@ -256,30 +193,23 @@ template <int MODE> int run_frozen(psdr_hip_vdenoise *h, const float *in, int C,
 extern "C" {
 
 int psdr_hip_vdenoise_create(const float *guides, int32_t G, int32_t W, int32_t H, int32_t L, psdr_hip_vdenoise **out, void *stream) {
-    const std::string me = "psdr_hip_vdenoise_create: ";
-    if (!out) return psdr::api_fail(me + "out is NULL");
-    *out = nullptr;
-    if (G < 0 || G > kMaxG) return psdr::api_fail(me + "G = " + std::to_string(G) + ", must lie in [0, 8]");
-    if (G > 0 && !guides) return psdr::api_fail(me + "guides is NULL");
-    if (W < 1 || H < 1) return psdr::api_fail(me + "W = " + std::to_string(W) + ", H = " + std::to_string(H) + ", must be positive");
-    if ((int64_t) W * H > kMaxPixels) return psdr::api_fail(me + "W H = " + std::to_string((int64_t) W * H) + " is above 2^24");
-    if (L < 1 || L > kMaxL) return psdr::api_fail(me + "L = " + std::to_string(L) + ", must lie in [1, 8]");
+    const char *me = "psdr_hip_vdenoise_create";
+    const std::string why = check_create(me, guides, G, W, H, L, out);
+    if (out) *out = nullptr;
+    if (!why.empty()) return psdr::api_fail(why);
     // the arguments are sound: from here on the device is touched
-    hipStream_t st = (hipStream_t) stream;
     psdr_hip_vdenoise *h = new psdr_hip_vdenoise();
-    h->W = W; h->H = H; h->G = G; h->L = L;
-    const size_t n = (size_t) W * H;
-    const hipError_t e = hipMalloc((void **) &h->d_mem, ((size_t) G + 3 * (size_t) L + 2 * kMaxC + 2) * n * sizeof(float));
-    if (e != hipSuccess) { delete h; return psdr::api_fail(me + hipGetErrorString(e)); }
-    h->planes = h->d_mem;
-    h->record = h->planes + (size_t) G * n;
-    h->work[0] = h->record + 3 * (size_t) L * n;
-    h->work[1] = h->work[0] + (size_t) kMaxC * n;
-    h->vwork[0] = h->work[1] + (size_t) kMaxC * n;
-    h->vwork[1] = h->vwork[0] + n;
-    if (G > 0) k_vplanes<<<(unsigned) ((n * G + kThreads - 1) / kThreads), kThreads, 0, st>>>(guides, (int) n, G, h->planes);
-    const hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) { delete h; return psdr::api_fail(me + hipGetErrorString(e2)); }
+    hipError_t e = h->init(guides, G, W, H, L, 3 * (size_t) L + 2 * kMaxC + 2, (hipStream_t) stream);
+    if (e == hipSuccess) {
+        const size_t n = h->pixels();
+        h->record = h->planes + (size_t) G * n;
+        h->work[0] = h->record + 3 * (size_t) L * n;
+        h->work[1] = h->work[0] + (size_t) kMaxC * n;
+        h->vwork[0] = h->work[1] + (size_t) kMaxC * n;
+        h->vwork[1] = h->vwork[0] + n;
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { delete h; return psdr::api_fail(std::string(me) + ": " + hipGetErrorString(e)); }
     *out = h;
     return 0;
 }
@@ -316,7 +246,7 @@ int psdr_hip_vdenoise_apply(psdr_hip_vdenoise *h, const float *in, int32_t C, co
         src = dst;
         vsrc = vdst;
     }
-    VCHK(hipGetLastError());
+    ATROUS_CHK(hipGetLastError());
     h->k = k; h->eps = eps;
     h->recorded = true;
     return 0;
@@ -337,7 +267,7 @@ int psdr_hip_vdenoise_record(psdr_hip_vdenoise *h, float *out, void *stream) {
     if (!h) return psdr::api_fail(me + "handle is NULL");
     if (!out) return psdr::api_fail(me + "NULL argument");
     if (!h->recorded) return psdr::api_fail(me + "the handle holds no record: an apply makes one");
-    VCHK(hipMemcpyAsync(out, h->record, 3 * (size_t) h->L * h->W * h->H * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    ATROUS_CHK(hipMemcpyAsync(out, h->record, 3 * (size_t) h->L * h->W * h->H * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t) stream));
     return 0;
 }
 

@@ -34,16 +34,35 @@ def _single_gpu(what):
 
 
 class _Handle:
-    """owner of a psdr_hip_denoise"""
+    """owner of a psdr_hip_denoise or a psdr_hip_vdenoise: `prefix` + "_create" / "_destroy" are its entry points"""
 
-    def __init__(self, guides, n_guides, width, height, levels, stream):
-        self.ptr = _C.c_void_p()
-        _cabi.check(_cabi.lib().psdr_hip_denoise_create(guides.data_ptr() if guides is not None else None, n_guides, width, height, levels, _C.byref(self.ptr), stream))
+    def __init__(self, prefix, guides, n_guides, width, height, levels, stream):
+        self.ptr, self._destroy = _C.c_void_p(), prefix + "_destroy"
+        _cabi.check(getattr(_cabi.lib(), prefix + "_create")(guides.data_ptr() if guides is not None else None, n_guides, width, height, levels, _C.byref(self.ptr), stream))
 
     def __del__(self):
         if getattr(self, "ptr", None) and _cabi is not None:           # (None: the interpreter is shutting down and has cleared the module)
-            _cabi.lib().psdr_hip_denoise_destroy(self.ptr)
+            getattr(_cabi.lib(), self._destroy)(self.ptr)
             self.ptr = None
+
+
+def _frame_guides(what, guides, width, height, levels):
+    """What the constructor of `what` (the class, for the messages) does with its frame, levels and guides: it refuses wrong ones, then a process group of several ranks,
+    and only then touches the device -> (device, the guides detached, in float32 and contiguous on it, or None without guides, their channel count)"""
+    from . import _device
+    if width < 1 or height < 1 or width * height > MAX_PIXELS:
+        raise ValueError("%s: a frame of %d x %d pixels; both must be positive and their product at most 2^24" % (what, width, height))
+    if not 1 <= levels <= MAX_LEVELS:
+        raise ValueError("%s: levels = %d, must lie in [1, %d]" % (what, levels, MAX_LEVELS))
+    if guides is not None:
+        if guides.dim() != 2 or int(guides.shape[0]) != width * height:
+            raise ValueError("%s: expected guides of shape [%d, G], got %s" % (what, width * height, tuple(guides.shape)))
+        if int(guides.shape[1]) > MAX_GUIDES:
+            raise ValueError("%s: %d guide channels, at most %d" % (what, int(guides.shape[1]), MAX_GUIDES))
+    _single_gpu(what)
+    n_guides = int(guides.shape[1]) if guides is not None else 0
+    device = _device()
+    return device, (guides.detach().to(device, _torch.float32).contiguous() if n_guides else None), n_guides
 
 
 class _DenoiseFn(_torch.autograd.Function):
@@ -74,24 +93,12 @@ class Denoiser:
     The handle owns two work frames: calls on one Denoiser must follow each other on one stream."""
 
     def __init__(self, guides, width, height, levels=5):
-        from . import _device, _stream_ptr
+        from . import _stream_ptr
         width, height, levels = int(width), int(height), int(levels)
-        if width < 1 or height < 1 or width * height > MAX_PIXELS:
-            raise ValueError("Denoiser: a frame of %d x %d pixels; both must be positive and their product at most 2^24" % (width, height))
-        if not 1 <= levels <= MAX_LEVELS:
-            raise ValueError("Denoiser: levels = %d, must lie in [1, %d]" % (levels, MAX_LEVELS))
-        if guides is not None:
-            if guides.dim() != 2 or int(guides.shape[0]) != width * height:
-                raise ValueError("Denoiser: expected guides of shape [%d, G], got %s" % (width * height, tuple(guides.shape)))
-            if int(guides.shape[1]) > MAX_GUIDES:
-                raise ValueError("Denoiser: %d guide channels, at most %d" % (int(guides.shape[1]), MAX_GUIDES))
-        _single_gpu("Denoiser")
+        self._device, g, self.n_guides = _frame_guides("Denoiser", guides, width, height, levels)
         self.width, self.height, self.levels = width, height, levels
-        self.n_guides = int(guides.shape[1]) if guides is not None else 0
-        self._device = _device()
-        g = guides.detach().to(self._device, _torch.float32).contiguous() if self.n_guides else None
         with _torch.cuda.device(self._device):
-            self._handle = _Handle(g, self.n_guides, width, height, levels, _stream_ptr())
+            self._handle = _Handle("psdr_hip_denoise", g, self.n_guides, width, height, levels, _stream_ptr())
 
     def _run(self, x, adjoint):
         from . import _stream_ptr

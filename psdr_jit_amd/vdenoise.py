@@ -34,7 +34,7 @@ import math as _math
 import torch as _torch
 
 from . import cabi as _cabi
-from .denoise import MAX_GUIDES, MAX_LEVELS, MAX_PIXELS, _single_gpu
+from .denoise import _Handle, _frame_guides, _single_gpu
 
 REC709 = (0.2126, 0.7152, 0.0722)
 
@@ -46,19 +46,6 @@ def _coefficients(what, luminance, channels):
     if len(a) != channels or not all(_math.isfinite(c) for c in a):
         raise ValueError("%s: luminance = %r, expected %d finite coefficients" % (what, luminance, channels))
     return a
-
-
-class _Handle:
-    """owner of a psdr_hip_vdenoise"""
-
-    def __init__(self, guides, n_guides, width, height, levels, stream):
-        self.ptr = _C.c_void_p()
-        _cabi.check(_cabi.lib().psdr_hip_vdenoise_create(guides.data_ptr() if guides is not None else None, n_guides, width, height, levels, _C.byref(self.ptr), stream))
-
-    def __del__(self):
-        if getattr(self, "ptr", None) and _cabi is not None:           # (None: the interpreter is shutting down and has cleared the module)
-            _cabi.lib().psdr_hip_vdenoise_destroy(self.ptr)
-            self.ptr = None
 
 
 class _VDenoiseFn(_torch.autograd.Function):
@@ -96,12 +83,8 @@ class VarianceDenoiser:
     on one stream, and a backward must run before the next den(img, var)."""
 
     def __init__(self, guides, width, height, levels=5, sigma_l=2.0, eps=1e-12, luminance=None):
-        from . import _device, _stream_ptr
+        from . import _stream_ptr
         width, height, levels = int(width), int(height), int(levels)
-        if width < 1 or height < 1 or width * height > MAX_PIXELS:
-            raise ValueError("VarianceDenoiser: a frame of %d x %d pixels; both must be positive and their product at most 2^24" % (width, height))
-        if not 1 <= levels <= MAX_LEVELS:
-            raise ValueError("VarianceDenoiser: levels = %d, must lie in [1, %d]" % (levels, MAX_LEVELS))
         sigma_l, eps = float(sigma_l), float(eps)
         if not sigma_l > 0.0:
             raise ValueError("VarianceDenoiser: sigma_l = %r, must be positive (float('inf') switches the luminance weight off)" % sigma_l)
@@ -111,22 +94,14 @@ class VarianceDenoiser:
             luminance = tuple(float(c) for c in luminance)
             if len(luminance) not in (1, 3) or not all(_math.isfinite(c) for c in luminance):
                 raise ValueError("VarianceDenoiser: luminance = %r, expected 1 or 3 finite coefficients" % (luminance,))
-        if guides is not None:
-            if guides.dim() != 2 or int(guides.shape[0]) != width * height:
-                raise ValueError("VarianceDenoiser: expected guides of shape [%d, G], got %s" % (width * height, tuple(guides.shape)))
-            if int(guides.shape[1]) > MAX_GUIDES:
-                raise ValueError("VarianceDenoiser: %d guide channels, at most %d" % (int(guides.shape[1]), MAX_GUIDES))
-        _single_gpu("VarianceDenoiser")
+        self._device, g, self.n_guides = _frame_guides("VarianceDenoiser", guides, width, height, levels)
         self.width, self.height, self.levels = width, height, levels
         self.sigma_l, self.eps, self.luminance = sigma_l, eps, luminance
         self.k = 0.0 if _math.isinf(sigma_l) else 1.0 / (sigma_l * sigma_l)
-        self.n_guides = int(guides.shape[1]) if guides is not None else 0
         self.variance = None
         self._serial = 0
-        self._device = _device()
-        g = guides.detach().to(self._device, _torch.float32).contiguous() if self.n_guides else None
         with _torch.cuda.device(self._device):
-            self._handle = _Handle(g, self.n_guides, width, height, levels, _stream_ptr())
+            self._handle = _Handle("psdr_hip_vdenoise", g, self.n_guides, width, height, levels, _stream_ptr())
 
     def _image(self, x):
         n = self.width * self.height
