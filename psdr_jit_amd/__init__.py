@@ -255,9 +255,9 @@ AreaLight.radiance = _make_param_property("radiance", _v3)
 #     t = scene.param_map["BSDF[0]"].uv_transform("reflectance");  t.rotate = torch.tensor(0.3, requires_grad=True)
 # (the reference spelling: scene.param_map["BSDF[0]"].reflectance.rotate = FloatD(0.3)).  The three members travel to the host
 # object as one leaf [rotate, scale, translate.x, translate.y] named "<parameter>@uv".
-_UV_SLOT = {"reflectance": 0, "diffuseReflectance": 0, "specularReflectance": 1, "roughness": 2, "normal_map": 0,
-            "eta": 0, "k": 1, "alpha_u": 2, "alpha_v": 2}
-_UV_SUFFIX = "@uv"
+from . import reverse as _reverse  # noqa: E402
+
+_UV_SLOT, _UV_SUFFIX = _reverse.SLOT, _reverse.UV_SUFFIX        # (the slot of a bitmap parameter inside its BSDF: stated once, beside the adjoint buffers it indexes)
 
 
 def _uv_push(obj, name, v, d):
@@ -837,7 +837,7 @@ def _unit_ray_intersect(self, ray, active=None):
     return its
 
 
-_GEO_NAMES = ("vertex_positions", "to_world_left", "to_world", "to_world_right")
+_GEO_NAMES = _reverse.GEO_NAMES
 # (first word, width) in the 24-float record of the outputs of _IntersectADFn, in IntersectionD's order: t, p, n, sh_frame.s / .t / .n, wi, uv
 _ITS_AD_OUT = ((2, 1), (4, 3), (7, 3), (10, 3), (13, 3), (16, 3), (19, 3), (22, 2))
 
@@ -870,7 +870,6 @@ class _IntersectADFn(_torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        from . import chain
         st = ctx.isect
         scene, dev = st["scene"], st["dev"]
         if scene.__dict__.get("_psdr_config_count", 0) != st["config"]:
@@ -885,14 +884,11 @@ class _IntersectADFn(_torch.autograd.Function):
         g_rec[~st["valid"]] = 0.0                                  # misses and inactive rays: no adjoint
         needs = ctx.needs_input_grad
         leaves = st["leaves"]
-        want_mesh = _np.zeros(max(1, scene.num_meshes), dtype=_np.uint8)
-        geo_wanted = []
-        for (obj, name, t), need in zip(leaves, needs[3:]):
-            if need:
-                want_mesh[_mesh_index(scene, obj)] = 1
-                geo_wanted.append((obj, name))
-        n_tris, n_sec = (int(x) for x in scene._snapshot_counts())
-        g_tri = _torch.zeros(n_tris * 22, dtype=_torch.float32, device=dev) if geo_wanted else None
+        layout = _reverse.Layout(scene)
+        want_mesh = _np.zeros(max(1, layout.n_meshes), dtype=_np.uint8)
+        geo_wanted = [(i, obj, name, t) for i, ((obj, name, t), need) in enumerate(zip(leaves, needs[3:])) if need]
+        want_mesh[[layout.mesh_row(obj) for _i, obj, _n, _t in geo_wanted]] = 1
+        g_tri = _torch.zeros(layout.n_tris * 22, dtype=_torch.float32, device=dev) if geo_wanted else None
         g_o = _torch.zeros((n, 3), dtype=_torch.float32, device=dev) if needs[1] else None
         g_d = _torch.zeros((n, 3), dtype=_torch.float32, device=dev) if needs[2] else None
         mesh_filter = _torch.from_numpy(want_mesh).to(dev)
@@ -902,14 +898,11 @@ class _IntersectADFn(_torch.autograd.Function):
                                      ptr(g_tri), ptr(g_o), ptr(g_d), _stream_ptr())
         out = [None] * len(leaves)
         if geo_wanted:
-            if "Sensor[0]" not in scene.param_map:
+            if layout.edge_mesh is None:
                 raise RuntimeError("unit_ray_intersectAD: the chain rule to the mesh parameters needs a configured scene with a sensor")
-            n_prim = int(_np.asarray(scene.param_map["Sensor[0]"]._primary_edge_ids()).reshape(-1, 3).shape[0])
-            geo = chain.native_geometry_grads(scene, 0, geo_wanted, g_tri.cpu().numpy(), _np.zeros(6 * n_sec, _np.float32),
-                                              _np.zeros(4 * n_prim, _np.float32), None)
-            for i, ((obj, name, t), need) in enumerate(zip(leaves, needs[3:])):
-                if need:
-                    out[i] = _torch.as_tensor(_np.ascontiguousarray(geo[(id(obj), name)])).reshape(t.shape).to(t.device, t.dtype)
+            geo = _reverse.geometry_grads(layout, geo_wanted, g_tri.cpu().numpy(), _np.zeros(6 * layout.n_sec, _np.float32), _np.zeros(4 * layout.n_prim, _np.float32), None)
+            for i, g in geo.items():
+                out[i] = g
         o_in, d_in = st["o_in"], st["d_in"]
         go = g_o.reshape(o_in.shape).to(o_in.device, o_in.dtype) if g_o is not None else None
         gd = g_d.reshape(d_in.shape).to(d_in.device, d_in.dtype) if g_d is not None else None
@@ -1201,50 +1194,10 @@ def _render_d_raw(self, scene, sensor_id, seed, batch_pix, terms, distributed=No
     return _render_terms(render, n, dev, world, terms, split_ok=pix is None, tile=tile)
 
 
-def _bsdf_index(scene, obj):
-    """row of a BSDF in the configured snapshot: the scene's own BSDFs in order, then the BSDFs nested in normal maps"""
-    pm = scene.param_map
-    nb = sum(1 for k in pm if k.startswith("BSDF[") and not k.startswith("BSDF[id="))
-    hidden = nb
-    for k in range(nb):
-        b = pm["BSDF[%d]" % k]
-        if b is obj:
-            return k
-        if isinstance(b, NormalMapBSDF):
-            if b._nested is obj:
-                return hidden
-            hidden += 1
-    raise RuntimeError("BSDF is not part of the scene")
-
-
-def _mesh_index(scene, mesh):
-    for i in range(scene.num_meshes):
-        if scene.param_map.get("Mesh[%d]" % i) is mesh:
-            return i
-    raise RuntimeError("mesh is not part of the scene")
-
-
-class _intra_op_threads:
-    """caps torch's intra-op thread pool for a block of small CPU tensor work and restores it on every way out"""
-
-    def __init__(self, cap):
-        self.cap = cap
-
-    def __enter__(self):
-        self.n = _torch.get_num_threads()
-        if self.n > self.cap:
-            _torch.set_num_threads(self.cap)
-
-    def __exit__(self, *exc):
-        if self.n > self.cap:
-            _torch.set_num_threads(self.n)
-        return False
-
-
 class _RenderDFn(_torch.autograd.Function):
     """Autograd node of renderD.  forward = primal image; backward = the reverse-mode kernels
-    (psdr_hip_render_d_bwd: adjoints of the configured snapshot) followed by the host chain rule of
-    chain.py down to the leaf tensors (mesh transforms, vertex positions, reflectances, radiances)."""
+    (psdr_hip_render_d_bwd: adjoints of the configured snapshot) followed by the routes of reverse.py from
+    the buffers down to the leaf tensors (mesh transforms and vertex positions through chain.py, reflectances, radiances, ...)."""
 
     @staticmethod
     def forward(ctx, state, *leaf_tensors):
@@ -1253,176 +1206,45 @@ class _RenderDFn(_torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_img):
-        from . import chain
         st = ctx.state
         integ, scene = st["integrator"], st["scene"]
         scene.__dict__["_psdr_fwd_hint"] = None          # this scene's images go to reverse mode: renderD makes no forward-mode launch ahead of time
-        leaves = st["leaves"]
-        needs = ctx.needs_input_grad[1:]
-        want_cam = any(need and isinstance(obj, Sensor) for (obj, name, t), need in zip(leaves, needs))
         dev = grad_img.device
         g_img = grad_img.contiguous().to(_torch.float32)
-        n_tris, n_sec = (int(x) for x in scene._snapshot_counts())
-        cam = scene.param_map["Sensor[%d]" % st["sensor_id"]]
-        n_prim = int(_np.asarray(cam._primary_edge_ids()).reshape(-1, 3).shape[0])
-        pm = scene.param_map
-        nb = sum(1 for k in pm if k.startswith("BSDF[") and not k.startswith("BSDF[id="))
-        ne = sum(1 for k in pm if k.startswith("Emitter[") and not k.startswith("Emitter[id="))
-        # BSDF rows of the snapshot: the scene's own, then the ones nested in normal maps
-        n_hidden = sum(1 for k in range(nb) if isinstance(pm["BSDF[%d]" % k], NormalMapBSDF))
-        sizes = [n_tris * 22, max(1, nb + n_hidden) * 3, max(1, ne) * 3, max(1, n_sec) * 6, max(1, n_prim) * 4]
-        flat = _torch.zeros(sum(sizes), dtype=_torch.float32, device=dev)
+        # 1. plan: one route per leaf; which buffers, filters and terms the launch needs follows from the routes (reverse.py)
+        layout = _reverse.Layout(scene, st["sensor_id"])
+        plan = _reverse.plan(layout, integ, st["leaves"], ctx.needs_input_grad[1:], st["terms"], lambda: _core._tex_layout(scene))
+        # 2. allocate: the five row buffers in one flat allocation (one all-reduce, one copy to the host), the optional ones each on its own
+        shapes = layout.shapes(plan.tex_total, plan.env_texels)
         offs = [0]
-        for z in sizes:
-            offs.append(offs[-1] + z)
-        ptr = [flat.data_ptr() + 4 * o for o in offs[:-1]]
+        for name in _reverse.ROW_BUFFERS:
+            offs.append(offs[-1] + int(_np.prod(shapes[name])))
+        flat = _torch.zeros(offs[-1], dtype=_torch.float32, device=dev)
+        extra = {name: _torch.zeros(int(_np.prod(shapes[name])), dtype=_torch.float32, device=dev) for name in plan.buffers}
+        mesh_filter = _torch.from_numpy(plan.mesh_filter).to(dev)
+        prim_filter = _torch.from_numpy(plan.prim_edge_filter).to(dev) if plan.prim_edge_filter is not None else None
+        bpix = _pix(st["batch_pix"], dev)             # batch rendering: the adjoint image is [len(batch_pix), 3]
+        ptr = lambda x: x.data_ptr() if x is not None else 0
         if st["seed"] != -1:
             seeds, skips = [st["seed"]] * 3, [0, 0, 0]
         else:
             seeds, skips = [s[2] for s in st["samplers"]], [s[3] for s in st["samplers"]]
         rank, world = _shard()
-        # requires_grad at the level of the configured snapshot: which meshes' triangle rows, and whether any BSDF colour /
-        # emitter radiance, are wanted.  The interior adjoint probes only those (psdr_grads.mesh_filter / skip_*).
-        want_mesh = _np.zeros(max(1, scene.num_meshes), dtype=_np.uint8)
-        want_bsdf = want_em = False
-        for (obj, name, t), need in zip(leaves, needs):
-            if not need:
-                continue
-            if isinstance(obj, Mesh):
-                want_mesh[_mesh_index(scene, obj)] = 1
-            elif isinstance(obj, _core.BSDF):
-                want_bsdf = want_bsdf or (t.dim() < 2 and name in ("reflectance", "diffuseReflectance"))     # (the rest: g_tex / g_mat)
-            elif isinstance(obj, _core.Emitter):
-                want_em = want_em or not isinstance(obj, EnvironmentMap)     # (the map's adjoints come back in g_env / g_env_scale)
-        mesh_filter = _torch.from_numpy(want_mesh).to(dev)
-        # bitmap parameters (a leaf of 2 or 3 dimensions on a BSDF) and per-vertex values: their adjoints come back in one flat buffer
-        tex_leaves = [i for i, ((obj, name, t), need) in enumerate(zip(leaves, needs)) if need and isinstance(obj, _core.BSDF) and (t.dim() >= 2 or isinstance(obj, MicrofacetBSDFPerVertex))]
-        # rotate / scale / translate of a bitmap: four scalars per bitmap, filled by the same pass (psdr_grads.g_uv_xf beside g_tex / g_env)
-        uv_leaves = [i for i, ((obj, name, t), need) in enumerate(zip(leaves, needs)) if need and name.endswith(_UV_SUFFIX)]
-        g_uv = _torch.zeros(4 * (3 * (nb + n_hidden) + 1), dtype=_torch.float32, device=dev) if uv_leaves else None
-        g_tex = None
-        if tex_leaves or any(isinstance(leaves[i][0], _core.BSDF) for i in uv_leaves):
-            tex_off, tex_total = _core._tex_layout(scene)
-            g_tex = _torch.zeros(max(1, int(tex_total)), dtype=_torch.float32, device=dev)
-        g_cam = _torch.zeros(16, dtype=_torch.float32, device=dev) if want_cam else None
-        bpix = _pix(st["batch_pix"], dev)             # batch rendering: the adjoint image is [len(batch_pix), 3]
-        # constant parameters of the GGX BSDFs: (row offset, length) inside the BSDF's 16-float row of psdr_grads.g_mat
-        mat_rows = {"MicrofacetBSDF": {"specularReflectance": (0, 3), "roughness": (3, 1)},
-                    "RoughConductorBSDF": {"alpha_u": (0, 1), "alpha_v": (1, 1), "eta": (2, 3), "k": (5, 3), "specular_reflectance": (8, 3)},
-                    "RoughDielectricBSDF": {"alpha_u": (0, 1), "alpha_v": (1, 1), "eta": (2, 1)}}
-        mat_leaves = [i for i, ((obj, name, t), need) in enumerate(zip(leaves, needs))
-                      if need and t.dim() < 2 and name in mat_rows.get(type(obj).__name__, {})]
-        g_mat = _torch.zeros(16 * max(1, nb + n_hidden), dtype=_torch.float32, device=dev) if mat_leaves else None
-        env_leaves = [i for i, ((obj, name, t), need) in enumerate(zip(leaves, needs)) if need and isinstance(obj, EnvironmentMap) and not name.endswith(_UV_SUFFIX)]
-        g_env = g_env_scale = g_env_xf = None
-        for i in env_leaves:
-            obj, name, t = leaves[i]
-            if name == "radiance":
-                g_env = _torch.zeros(t.numel(), dtype=_torch.float32, device=dev)
-            elif name == "scale":
-                g_env_scale = _torch.zeros(1, dtype=_torch.float32, device=dev)
-            else:               # to_world_left: through the adjoint of from_world = (to_world_left . to_world_raw)^-1
-                g_env_xf = _torch.zeros(16, dtype=_torch.float32, device=dev)
-        if g_env is None and any(isinstance(leaves[i][0], EnvironmentMap) for i in uv_leaves):
-            g_env = _torch.zeros(int(_np.prod(leaves[uv_leaves[0]][0]._get("radiance", False).shape)), dtype=_torch.float32, device=dev)
-        if g_env_scale is not None and g_env is None:        # the scale adjoint is assembled from the texel probes
-            g_env = _torch.zeros(int(_np.prod(leaves[env_leaves[0]][0]._get("radiance", False).shape)), dtype=_torch.float32, device=dev)
-        # the boundary terms' adjoints are rows of edges (g_sec / g_prim): nobody reads them unless a mesh or the camera is differentiated
-        bwd_terms = _derivative_terms(st["terms"], leaves, {id(t) for (_o, _n, t), need in zip(leaves, needs) if need}) & 7
-        # ... and the primary-edge samples add to the row of THEIR edge only: with some meshes differentiated and the camera (and the integrator) not, the samples
-        # on the other meshes' edges are not traced (psdr_grads.prim_edge_filter)
-        prim_filter = None
-        if (bwd_terms & TERM_PRIMARY) and n_prim > 0 and not any(need and not isinstance(obj, Mesh) and _moves_edges(obj, name) for (obj, name, t), need in zip(leaves, needs)):
-            edge_mesh = _np.asarray(cam._primary_edge_ids(), dtype=_np.int64).reshape(-1, 3)[:, 0]
-            prim_filter = _torch.from_numpy(_np.ascontiguousarray(want_mesh[edge_mesh])).to(dev)
+        # 3. launch: psdr_hip_render_d_bwd fills the adjoints of the configured snapshot
         integ._shard_mode = _shard_mode() if world > 1 else 0            # (the partition of the forward pass: the adjoints of all ranks are summed below, whatever the partition)
-        _core._render_d_bwd(integ, scene, st["sensor_id"], seeds, skips, g_img.data_ptr(), ptr[0], ptr[1], ptr[2], ptr[3], ptr[4],
-                            _stream_ptr(), rank, world, bwd_terms, mesh_filter.data_ptr(), not want_bsdf, not want_em,
-                            g_tex.data_ptr() if g_tex is not None else 0, g_cam.data_ptr() if g_cam is not None else 0,
-                            g_env.data_ptr() if g_env is not None else 0, g_env_scale.data_ptr() if g_env_scale is not None else 0,
-                            g_mat.data_ptr() if g_mat is not None else 0, g_env_xf.data_ptr() if g_env_xf is not None else 0,
-                            bpix.data_ptr() if bpix is not None else 0, int(bpix.numel()) if bpix is not None else 0,
-                            g_uv.data_ptr() if g_uv is not None else 0, prim_filter.data_ptr() if prim_filter is not None else 0,
-                            bool(st.get("batch_edges", False)) and bpix is not None)
+        _core._render_d_bwd(integ, scene, st["sensor_id"], seeds, skips, g_img.data_ptr(), *[flat.data_ptr() + 4 * o for o in offs[:-1]],
+                            _stream_ptr(), rank, world, plan.terms, mesh_filter.data_ptr(), plan.skip_bsdf, plan.skip_emitter,
+                            ptr(extra.get("g_tex")), ptr(extra.get("g_camera")), ptr(extra.get("g_env")), ptr(extra.get("g_env_scale")),
+                            ptr(extra.get("g_mat")), ptr(extra.get("g_env_from_world")), ptr(bpix), int(bpix.numel()) if bpix is not None else 0,
+                            ptr(extra.get("g_uv_xf")), ptr(prim_filter), bool(st.get("batch_edges", False)) and bpix is not None)
+        # 4. sum over the ranks (plan.buffers is in the order the collectives have always had)
         _all_reduce(flat, world > 1)
-        for extra in (g_env, g_env_scale, g_mat, g_env_xf, g_uv):
-            if extra is not None:
-                _all_reduce(extra, world > 1)
-        if g_cam is not None:
-            _all_reduce(g_cam, world > 1)
-        if g_tex is not None:
-            _all_reduce(g_tex, world > 1)
+        for name in plan.buffers:
+            _all_reduce(extra[name], world > 1)
+        # 5. gather: from the buffers to the leaves, one loop over the routes
         g = flat.to("cpu", _torch.float64)
-        g_bsdf_all = g[offs[1]:offs[2]].reshape(-1, 3)
-        g_tri, g_bsdf, g_em = g[offs[0]:offs[1]].reshape(n_tris, 22), g_bsdf_all[:nb], g[offs[2]:offs[3]].reshape(-1, 3)[:ne]
-        g_sec, g_prim = g[offs[3]:offs[4]].reshape(-1, 6)[:n_sec], g[offs[4]:offs[5]].reshape(-1, 4)[:n_prim]
-
-        # From the adjoints of the snapshot rows to the leaves: the per-triangle / per-edge part of the chain rule runs in the host core (Scene::chain_geometry through
-        # chain.native_geometry_grads: double arithmetic on host threads; rounds 1-4 differentiated a torch restatement of configure() here, 25 ms per step on config 5),
-        # colours and radiances are rows of g_bsdf / g_emitter.
-        grads = [None] * len(leaves)
-        g_np = g.numpy()
-        geo_wanted = [(obj, name) for (obj, name, t), need in zip(leaves, needs)
-                      if need and ((isinstance(obj, Mesh) and name in ("vertex_positions", "to_world_left", "to_world", "to_world_right")) or
-                                   (isinstance(obj, Sensor) and name in ("to_world_left", "to_world", "to_world_right")))]
-        if geo_wanted:
-            geo = chain.native_geometry_grads(scene, st["sensor_id"], geo_wanted, g_np[offs[0]:offs[1]], g_np[offs[3]:offs[3] + 6 * n_sec], g_np[offs[4]:offs[4] + 4 * n_prim],
-                                              g_cam.to("cpu", _torch.float64).numpy().reshape(4, 4) if g_cam is not None else None)
-        for i, ((obj, name, t), need) in enumerate(zip(leaves, needs)):
-            if not need:
-                continue
-            if (obj, name) in [(o, n) for o, n in geo_wanted] and (id(obj), name) in geo:
-                grads[i] = _torch.as_tensor(_np.ascontiguousarray(geo[(id(obj), name)])).reshape(t.shape).to(t.device, t.dtype)
-            elif isinstance(obj, _core.BSDF) and t.dim() < 2 and name == ("diffuseReflectance" if isinstance(obj, MicrofacetBSDF) else "reflectance") \
-                    and isinstance(obj, (DiffuseBSDF, MicrofacetBSDF)):
-                b = _bsdf_index(scene, obj)
-                if b < nb:                      # (a BSDF nested in a normal map: below)
-                    row = g_bsdf[b].to(_torch.float32)
-                    grads[i] = (row if t.numel() == 3 else row.sum().reshape(1)).reshape(t.shape).to(t.device, t.dtype)
-            elif isinstance(obj, AreaLight) and name == "radiance":
-                e = [k for k in range(ne) if pm.get("Emitter[%d]" % k) is obj]
-                if e:
-                    row = g_em[e[0]].to(_torch.float32)
-                    grads[i] = (row if t.numel() == 3 else row.sum().reshape(1)).reshape(t.shape).to(t.device, t.dtype)
-        for i in tex_leaves:          # the leaf IS the texel array: its gradient is its block of g_tex
-            obj, name, t = leaves[i]
-            b = _bsdf_index(scene, obj)
-            slot = {"reflectance": 0, "diffuseReflectance": 0, "specularReflectance": 1, "roughness": 2, "normal_map": 0,
-                    "eta": 0, "k": 1, "alpha_u": 2, "alpha_v": 2}[name]       # the three bitmap / per-vertex slots of a BSDF
-            off = int(tex_off[3 * b + slot])
-            grads[i] = _torch.zeros_like(t) if off < 0 else g_tex[off:off + t.numel()].reshape(t.shape).to(t.device, t.dtype)
-        for i, ((obj, name, t), need) in enumerate(zip(leaves, needs)):      # the colour of a BSDF nested in a normal map: its own g_bsdf row
-            if need and isinstance(obj, _core.BSDF) and t.dim() < 2 and name in ("reflectance", "diffuseReflectance"):
-                b = _bsdf_index(scene, obj)
-                if b >= nb:
-                    row = g_bsdf_all[b].to(_torch.float32)
-                    grads[i] = (row if t.numel() == 3 else row.sum().reshape(1)).reshape(t.shape).to(t.device, t.dtype)
-        for i in mat_leaves:          # a colour given as one number is the sum of its three components
-            obj, name, t = leaves[i]
-            b = _bsdf_index(scene, obj)
-            off, n = mat_rows[type(obj).__name__][name]
-            row = g_mat[16 * b + off:16 * b + off + n]
-            grads[i] = (row if t.numel() == n else row.sum().reshape(1)).reshape(t.shape).to(t.device, t.dtype)
-        for i, ((obj, name, t), need) in enumerate(zip(leaves, needs)):      # CollocatedIntegrator.m_intensity: the image is linear in it
-            if need and obj is integ and name == "m_intensity":
-                grads[i] = ((g_img * st["img"]).sum() / t.detach().to(dev).reshape(())).reshape(t.shape).to(t.device, t.dtype)
-        for i in env_leaves:
-            obj, name, t = leaves[i]
-            if name in ("radiance", "scale"):
-                src = g_env if name == "radiance" else g_env_scale
-                grads[i] = src.reshape(t.shape).to(t.device, t.dtype)
-            else:               # from_world = inverse(to_world_left . to_world_raw): d from = -from . d to . from
-                with _torch.enable_grad():
-                    L = t.detach().to("cpu", _torch.float64).reshape(4, 4).clone().requires_grad_(True)
-                    raw = _torch.as_tensor(_np.asarray(obj._get("to_world_raw", False), dtype=_np.float64))
-                    fw = _torch.linalg.inv(L @ raw)
-                    (gl,) = _torch.autograd.grad(fw, L, g_env_xf.to("cpu", _torch.float64).reshape(4, 4))
-                grads[i] = gl.reshape(t.shape).to(t.device, t.dtype)
-        for i in uv_leaves:           # [rotate, scale, translate.x, translate.y]: the bitmap's row of g_uv_xf (the last row is the environment map's)
-            obj, name, t = leaves[i]
-            row = 3 * (nb + n_hidden) if isinstance(obj, EnvironmentMap) else 3 * _bsdf_index(scene, obj) + _UV_SLOT[name[:-len(_UV_SUFFIX)]]
-            grads[i] = g_uv[4 * row:4 * row + 4].reshape(t.shape).to(t.device, t.dtype)
-        return (None,) + tuple(grads)
+        rows = {name: g[offs[k]:offs[k + 1]] for k, name in enumerate(_reverse.ROW_BUFFERS)}
+        return (None,) + _reverse.gather(plan, {**rows, **extra}, g_img, st["img"])
 
 
 def _moves_edges(obj, name):

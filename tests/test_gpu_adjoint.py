@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import adjoint_buffers
 import product
 import scenes
 
@@ -28,18 +29,12 @@ def env():
     return torch, psdr_jit_amd, cabi
 
 
-def _bwd(torch, cabi, sc, w, depth, seeds, terms, n_tris, n_bsdfs, n_emitters, n_sec, n_prim):
-    dev = "cuda"
-    g_tri = torch.zeros((n_tris, 22), dtype=torch.float32, device=dev)
-    g_bsdf = torch.zeros((max(1, n_bsdfs), 3), dtype=torch.float32, device=dev)
-    g_em = torch.zeros((max(1, n_emitters), 3), dtype=torch.float32, device=dev)
-    g_sec = torch.zeros((max(1, n_sec), 6), dtype=torch.float32, device=dev)
-    g_prim = torch.zeros((max(1, n_prim), 4), dtype=torch.float32, device=dev)
-    g = cabi.Grads(g_tri.data_ptr(), g_bsdf.data_ptr(), g_em.data_ptr(), g_sec.data_ptr(), g_prim.data_ptr())
+def _bwd(torch, cabi, sc, spec, w, depth, seeds, terms):
+    g, bufs, _ = adjoint_buffers.allocate(sc, spec)
     a = cabi.make_args(max_depth=depth, seeds=seeds, terms=terms)
     cabi.check(cabi.lib().psdr_hip_render_d_bwd(sc._hip_handle(), C.byref(a), w.data_ptr(), C.byref(g), None))
     torch.cuda.synchronize()
-    return [t.cpu().numpy().astype(np.float64) for t in (g_tri, g_bsdf, g_em, g_sec, g_prim)]
+    return [bufs[f].cpu().numpy().astype(np.float64) for f in adjoint_buffers.ROWS]
 
 
 @pytest.mark.parametrize("param", ["light_x", "box_x", "albedo", "radiance"])
@@ -64,8 +59,7 @@ def test_adjoint_dot_product(env, param, terms):
     gen = torch.Generator(device="cpu").manual_seed(3)
     w = (torch.rand((n, 3), generator=gen) + 0.5).to("cuda")
     lhs = float((buf[1].double() * w.double()).sum())
-    g_tri, g_bsdf, g_em, g_sec, g_prim = _bwd(torch, cabi, sc, w, depth, seeds, terms, d_tri.shape[0], len(spec.bsdfs), len(spec.emitters),
-                                              d_sec.shape[0], d_prim.shape[0])
+    g_tri, g_bsdf, g_em, g_sec, g_prim = _bwd(torch, cabi, sc, spec, w, depth, seeds, terms)
     rhs = (g_tri * d_tri).sum() + (g_bsdf[:len(spec.bsdfs)] * d_bsdf).sum() + (g_em[:len(spec.emitters)] * d_em).sum()
     rhs += (g_sec[:d_sec.shape[0]] * d_sec).sum() + (g_prim[:d_prim.shape[0]] * d_prim).sum()
     scale = float((buf[1].double().abs() * w.double()).sum()) + 1e-12
@@ -103,27 +97,10 @@ def _dot_product_case(env, spec, depth, terms, seeds=(7, 8, 9), with_camera=Fals
         _img, d_img = osc.render_d(max_depth=depth, seeds=seeds, terms=terms)
         buf[1].copy_(torch.from_numpy(d_img).to("cuda"))
     lhs = float((buf[1].double() * w.double()).sum())
-    dev = "cuda"
-    g_tri = torch.zeros((d_tri.shape[0], 22), dtype=torch.float32, device=dev)
-    n_hidden = sum(1 for b in spec.bsdfs if getattr(b, "type", 0) == 5)          # the BSDF nested in a normal map is a row of its own behind the scene's
-    g_bsdf = torch.zeros((max(1, len(spec.bsdfs) + n_hidden), 3), dtype=torch.float32, device=dev)
-    g_em = torch.zeros((max(1, len(spec.emitters)), 3), dtype=torch.float32, device=dev)
-    g_sec = torch.zeros((max(1, d_sec.shape[0]), 6), dtype=torch.float32, device=dev)
-    g_prim = torch.zeros((max(1, d_prim.shape[0]), 4), dtype=torch.float32, device=dev)
-    g_cam = torch.zeros(16, dtype=torch.float32, device=dev)
-    g = cabi.Grads(g_tri.data_ptr(), g_bsdf.data_ptr(), g_em.data_ptr(), g_sec.data_ptr(), g_prim.data_ptr())
-    if with_camera:
-        g.g_camera = g_cam.data_ptr()
-    g_mat = torch.zeros((max(1, len(spec.bsdfs) + n_hidden), 16), dtype=torch.float32, device=dev)
-    if with_mat:
-        g.g_mat = g_mat.data_ptr()
-    # bitmap parameters: the texel adjoints, laid out as psdr_hip_scene_tex_layout reports
-    n_b = len(snap["bsdf_rows"]) if "bsdf_rows" in snap else len(spec.bsdfs) + n_hidden      # (the BSDFs nested in normal maps are rows of their own)
-    offs = (C.c_int64 * (3 * max(1, n_b)))(); total = C.c_int64(0)
-    cabi.check(cabi.lib().psdr_hip_scene_tex_layout(C.c_void_p(sc._hip_handle()), offs, C.byref(total)))
-    g_tex = torch.zeros(max(1, total.value), dtype=torch.float32, device=dev)
-    if total.value > 0:
-        g.g_tex = g_tex.data_ptr()
+    # bitmap parameters: the texel adjoints, laid out as psdr_hip_scene_tex_layout reports (handed over only when the scene has texels)
+    g, bufs, offs = adjoint_buffers.allocate(sc, spec, ("g_tex",) + (("g_camera",) if with_camera else ()) + (("g_mat",) if with_mat else ()))
+    g_tri, g_bsdf, g_em, g_sec, g_prim = (bufs[f] for f in adjoint_buffers.ROWS)
+    g_cam, g_mat, g_tex, has_tex = bufs.get("g_camera"), bufs.get("g_mat"), bufs["g_tex"], g.g_tex is not None
     cabi.check(cabi.lib().psdr_hip_render_d_bwd(sc._hip_handle(), C.byref(a), w.data_ptr(), C.byref(g), None))
     torch.cuda.synchronize()
     rhs = (g_tri.cpu().numpy().astype(np.float64) * d_tri).sum() + (g_bsdf.cpu().numpy().astype(np.float64)[:len(spec.bsdfs)] * d_bsdf).sum()
@@ -132,7 +109,7 @@ def _dot_product_case(env, spec, depth, terms, seeds=(7, 8, 9), with_camera=Fals
     if with_camera:
         d_tw = np.asarray(cam._get("to_world_left", True), np.float64).reshape(4, 4) if hasattr(cam, "_get") else np.zeros((4, 4))
         rhs += (g_cam.cpu().numpy().astype(np.float64).reshape(4, 4)[:3] * d_tw[:3]).sum()
-    if total.value > 0:    # d texel / dP of the spec's bitmaps (reflectance / diffuse, specular, roughness)
+    if has_tex:    # d texel / dP of the spec's bitmaps (reflectance / diffuse, specular, roughness)
         gt = g_tex.cpu().numpy().astype(np.float64)
         for i, b in enumerate(spec.bsdfs):
             pv = getattr(b, "type", 0) == 4      # per-vertex arrays use the same three blocks: diffuse, specular, roughness
@@ -299,31 +276,14 @@ def _all_adjoint_buffers(env, spec, depth, monkeypatch, probe, field=-1, intensi
     else:
         monkeypatch.delenv("PSDR_ADJ_PROBE", raising=False)
     sc = product.build_scene(spec)
-    snap = sc._snapshot()
-    n_tris = np.asarray(snap["d_triangles"]).shape[0]
-    n_b = len(snap["bsdf_rows"]) if "bsdf_rows" in snap else len(spec.bsdfs)
-    z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device="cuda")
-    g_tri, g_bsdf, g_em, g_sec, g_prim, g_cam, g_mat = z(n_tris, 22), z(max(1, n_b), 3), z(max(1, len(spec.emitters)), 3), z(1, 6), z(1, 4), z(16), z(max(1, n_b), 16)
-    g = cabi.Grads(g_tri.data_ptr(), g_bsdf.data_ptr(), g_em.data_ptr(), g_sec.data_ptr(), g_prim.data_ptr())
-    g.g_camera, g.g_mat = g_cam.data_ptr(), g_mat.data_ptr()
-    offs = (C.c_int64 * (3 * max(1, n_b)))(); total = C.c_int64(0)
-    cabi.check(cabi.lib().psdr_hip_scene_tex_layout(C.c_void_p(sc._hip_handle()), offs, C.byref(total)))
-    g_tex = z(max(1, total.value))
-    if total.value > 0:
-        g.g_tex = g_tex.data_ptr()
-    out = {"tri": g_tri, "bsdf": g_bsdf, "emitter": g_em, "camera": g_cam, "mat": g_mat, "tex": g_tex}
-    env_em = [e for e in spec.emitters if getattr(e, "type", 0) == 1]
-    if env_em:
-        H, W = env_em[0].env_data.shape[:2]
-        out["env"], out["env_scale"], out["env_xf"] = z(H * W * 3), z(1), z(16)
-        g.g_env, g.g_env_scale, g.g_env_from_world = out["env"].data_ptr(), out["env_scale"].data_ptr(), out["env_xf"].data_ptr()
+    g, out, _ = adjoint_buffers.allocate(sc, spec, adjoint_buffers.OPTIONAL[:-1])          # (all but g_uv_xf)
     gen = torch.Generator(device="cpu").manual_seed(11)
     w = (torch.rand((spec.width * spec.height, 3), generator=gen) + 0.5).to("cuda")
     a = cabi.make_args(max_depth=depth, seeds=(7, 8, 9), terms=1, field=field, intensity=intensity)
     cabi.check(cabi.lib().psdr_hip_render_d_bwd(sc._hip_handle(), C.byref(a), w.data_ptr(), C.byref(g), None))
     torch.cuda.synchronize()
     monkeypatch.delenv("PSDR_ADJ_PROBE", raising=False)
-    return {k: v.cpu().numpy().astype(np.float64) for k, v in out.items()}
+    return adjoint_buffers.to_f64(out)
 
 
 def _assert_same_buffers(sw, pr, tol, what):
@@ -376,7 +336,7 @@ def test_every_reverse_form_against_the_probe_form(env, monkeypatch, family):
     pr = _all_adjoint_buffers(env, spec, 3, monkeypatch, probe=True)
     if any(getattr(e, "type", 0) == 1 for e in spec.emitters):
         for q in (sw, pr):
-            q["tri"][-12:] = 0.0          # rows of the environment map's bounding box (see test_environment_sweep_equals_the_probe_form)
+            q["g_triangles"][-12:] = 0.0          # rows of the environment map's bounding box (see test_environment_sweep_equals_the_probe_form)
     _assert_same_buffers(sw, pr, 5e-4, family)
 
 
@@ -391,7 +351,7 @@ def test_environment_sweep_equals_the_probe_form(env, monkeypatch, balls):
     sw = _all_adjoint_buffers(env, spec, 3, monkeypatch, probe=False)
     pr = _all_adjoint_buffers(env, spec, 3, monkeypatch, probe=True)
     for q in (sw, pr):
-        q["tri"][-12:] = 0.0          # the rows of the map's bounding box, appended last by Scene::configure (scene.cpp:434-485): fixed geometry, read by nobody - the
+        q["g_triangles"][-12:] = 0.0          # the rows of the map's bounding box, appended last by Scene::configure (scene.cpp:434-485): fixed geometry, read by nobody - the
                                       # sweep glues its vertices to their triangles, the probe form differentiates the box hit as a ray-plane solve
     _assert_same_buffers(sw, pr, 3e-4, "envmap balls=%s" % balls)
 
@@ -542,33 +502,15 @@ def test_every_adjoint_kernel_is_the_same_in_every_run(env, family):
     make, depth = _EVERY_RUN[family]
     spec = make()
     sc = product.build_scene(spec)
-    snap = sc._snapshot()
-    n_tris = np.asarray(snap["d_triangles"]).shape[0]
-    n_sec = np.asarray(snap["d_sec_edges"]).shape[0]
-    n_prim = np.asarray(sc.param_map["Sensor[0]"]._primary_edges(True)).shape[0]
-    n_b = len(snap["bsdf_rows"]) if "bsdf_rows" in snap else len(spec.bsdfs)
-    offs = (C.c_int64 * (3 * max(1, n_b)))(); total = C.c_int64(0)
-    cabi.check(cabi.lib().psdr_hip_scene_tex_layout(C.c_void_p(sc._hip_handle()), offs, C.byref(total)))
     gen = torch.Generator(device="cpu").manual_seed(11)
     w = (torch.rand((spec.width * spec.height, 3), generator=gen) + 0.5).to("cuda")
-    env_em = [e for e in spec.emitters if getattr(e, "type", 0) == 1]
 
     def launch(terms):
-        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device="cuda")
-        out = {"tri": z(n_tris, 22), "bsdf": z(max(1, n_b), 3), "emitter": z(max(1, len(spec.emitters)), 3), "sec": z(max(1, n_sec), 6), "prim": z(max(1, n_prim), 4),
-               "camera": z(16), "mat": z(max(1, n_b), 16), "tex": z(max(1, total.value))}
-        g = cabi.Grads(out["tri"].data_ptr(), out["bsdf"].data_ptr(), out["emitter"].data_ptr(), out["sec"].data_ptr(), out["prim"].data_ptr())
-        g.g_camera, g.g_mat = out["camera"].data_ptr(), out["mat"].data_ptr()
-        if total.value > 0:
-            g.g_tex = out["tex"].data_ptr()
-        if env_em:
-            H, W = env_em[0].env_data.shape[:2]
-            out["env"], out["env_scale"], out["env_xf"] = z(H * W * 3), z(1), z(16)
-            g.g_env, g.g_env_scale, g.g_env_from_world = out["env"].data_ptr(), out["env_scale"].data_ptr(), out["env_xf"].data_ptr()
+        g, out, _ = adjoint_buffers.allocate(sc, spec, adjoint_buffers.OPTIONAL[:-1])          # (all but g_uv_xf)
         a = cabi.make_args(max_depth=depth, seeds=(7, 8, 9), terms=terms)
         cabi.check(cabi.lib().psdr_hip_render_d_bwd(sc._hip_handle(), C.byref(a), w.data_ptr(), C.byref(g), None))
         torch.cuda.synchronize()
-        return {k: v.cpu().numpy().astype(np.float64) for k, v in out.items()}
+        return adjoint_buffers.to_f64(out)
 
     for terms in (1, 2, 4):
         first = launch(terms)
@@ -636,28 +578,13 @@ def test_uv_transform_adjoints_in_one_pass(env, orc, monkeypatch, case, probe):
     else:
         monkeypatch.delenv("PSDR_ADJ_PROBE", raising=False)
     sc = product.build_scene(spec)
-    snap = sc._snapshot()
-    n_tris = np.asarray(snap["d_triangles"]).shape[0]
-    n_b = len(snap["bsdf_rows"]) if "bsdf_rows" in snap else len(spec.bsdfs)
-    z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device="cuda")
-    keep = [z(n_tris, 22), z(max(1, n_b), 3), z(max(1, len(spec.emitters)), 3), z(1, 6), z(1, 4)]
-    g = cabi.Grads(*[t.data_ptr() for t in keep])
-    offs = (C.c_int64 * (3 * max(1, n_b)))(); total = C.c_int64(0)
-    cabi.check(cabi.lib().psdr_hip_scene_tex_layout(C.c_void_p(sc._hip_handle()), offs, C.byref(total)))
-    g_tex, g_uv = z(max(1, total.value)), z(3 * n_b + 1, 4)
-    if total.value > 0:
-        g.g_tex = g_tex.data_ptr()
-    g.g_uv_xf = g_uv.data_ptr()
-    env_em = [e for e in spec.emitters if getattr(e, "type", 0) == 1]
-    if env_em:
-        H, W = env_em[0].env_data.shape[:2]
-        g_env = z(H * W * 3)
-        g.g_env = g_env.data_ptr()
+    n_b = adjoint_buffers.n_bsdf_rows(spec)
+    g, keep, _ = adjoint_buffers.allocate(sc, spec, ("g_tex", "g_uv_xf", "g_env"))
     a = cabi.make_args(max_depth=3, seeds=(7, 8, 9), terms=1)
     cabi.check(cabi.lib().psdr_hip_render_d_bwd(sc._hip_handle(), C.byref(a), w.data_ptr(), C.byref(g), None))
     torch.cuda.synchronize()
     monkeypatch.delenv("PSDR_ADJ_PROBE", raising=False)
-    gu = g_uv.cpu().numpy().astype(np.float64)
+    gu = keep["g_uv_xf"].cpu().numpy().astype(np.float64)
     rhs = float((gu[:3 * len(spec.bsdfs)].reshape(len(spec.bsdfs), 3, 4) * d_tex).sum() + (gu[3 * n_b] * d_env).sum())
     assert abs(lhs) > 1e-3 * scale and abs(lhs - rhs) <= 1e-3 * scale, (case, probe, lhs, rhs, scale)
 
@@ -704,38 +631,29 @@ def test_uv_adjoints_do_not_share_words_with_other_buffers(env, orc, monkeypatch
     else:
         monkeypatch.delenv("PSDR_ADJ_PROBE", raising=False)
     sc = product.build_scene(spec)
-    snap = sc._snapshot()
-    n_tris = np.asarray(snap["d_triangles"]).shape[0]
-    n_b = len(snap["bsdf_rows"]) if "bsdf_rows" in snap else len(spec.bsdfs)
-    offs = (C.c_int64 * (3 * max(1, n_b)))(); total = C.c_int64(0)
-    cabi.check(cabi.lib().psdr_hip_scene_tex_layout(C.c_void_p(sc._hip_handle()), offs, C.byref(total)))
-    assert total.value > 0
+    assert adjoint_buffers.tex_layout(sc, spec)[1] > 0
 
     def launch(with_uv):
-        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device="cuda")
-        out = {"tri": z(n_tris, 22), "bsdf": z(max(1, n_b), 3), "emitter": z(max(1, len(spec.emitters)), 3), "sec": z(1, 6), "prim": z(1, 4),
-               "mat": z(max(1, n_b), 16), "tex": z(total.value), "uv": z(3 * n_b + 1, 4)}
-        g = cabi.Grads(out["tri"].data_ptr(), out["bsdf"].data_ptr(), out["emitter"].data_ptr(), out["sec"].data_ptr(), out["prim"].data_ptr())
-        g.g_mat, g.g_tex = out["mat"].data_ptr(), out["tex"].data_ptr()
-        if with_uv:
-            g.g_uv_xf = out["uv"].data_ptr()
+        g, out, _ = adjoint_buffers.allocate(sc, spec, ("g_mat", "g_tex", "g_uv_xf"))
+        if not with_uv:
+            g.g_uv_xf = None                  # (allocated, not handed over)
         a = cabi.make_args(max_depth=3, seeds=(7, 8, 9), terms=1)
         cabi.check(cabi.lib().psdr_hip_render_d_bwd(sc._hip_handle(), C.byref(a), w.data_ptr(), C.byref(g), None))
         torch.cuda.synchronize()
-        return {k: v.cpu().numpy().astype(np.float64) for k, v in out.items()}
+        return adjoint_buffers.to_f64(out)
 
     with_uv, without = launch(True), launch(False)
     monkeypatch.delenv("PSDR_ADJ_PROBE", raising=False)
-    gu = with_uv["uv"]
+    gu = with_uv["g_uv_xf"]
     rhs = float((gu[:3 * len(spec.bsdfs)].reshape(len(spec.bsdfs), 3, 4) * d_tex).sum())
     errs = {}
-    for k in ("tri", "mat", "bsdf", "tex"):
+    for k in ("g_triangles", "g_mat", "g_bsdf", "g_tex"):
         ref = np.abs(without[k]).sum()
         errs[k] = np.abs(with_uv[k] - without[k]).sum() / ref if ref > 0.0 else np.abs(with_uv[k]).sum()
-    print("uv share", case, "last" if last else "first", "errs", errs, "L1 mat", np.abs(without["mat"]).sum(), "L1 tri", np.abs(without["tri"]).sum(),
+    print("uv share", case, "last" if last else "first", "errs", errs, "L1 mat", np.abs(without["g_mat"]).sum(), "L1 tri", np.abs(without["g_triangles"]).sum(),
           "lhs", lhs, "rhs", rhs, "scale", scale, "rel", abs(lhs - rhs) / scale)
-    assert np.abs(without["mat"]).sum() > 0.0 and np.abs(without["tri"]).sum() > 0.0 and np.abs(without["tex"]).sum() > 0.0, (case, last)       # the rows next to the uv adjoints are live
-    assert np.abs(without["uv"]).sum() == 0.0, (case, last)
+    assert np.abs(without["g_mat"]).sum() > 0.0 and np.abs(without["g_triangles"]).sum() > 0.0 and np.abs(without["g_tex"]).sum() > 0.0, (case, last)       # the rows next to the uv adjoints are live
+    assert np.abs(without["g_uv_xf"]).sum() == 0.0, (case, last)
     for k, err in errs.items():
         assert err <= 1e-5, (case, last, k, err)
     assert abs(lhs) > 1e-3 * scale and abs(lhs - rhs) <= 1e-3 * scale, (case, last, lhs, rhs, scale)

@@ -16,6 +16,7 @@ import os
 import numpy as np
 import pytest
 
+import adjoint_buffers
 import product
 import scenes
 
@@ -258,23 +259,10 @@ def test_backward_equals_forward_grad_with_edge_terms(torch_cuda, psdr, orc, whi
 
 
 def _bwd_buffers(torch, cabi, sc, spec, fn, args, w):
-    snap = sc._snapshot()
-    n_tris = np.asarray(snap["d_triangles"]).shape[0]
-    n_sec = np.asarray(snap["d_sec_edges"]).shape[0]
-    n_prim = np.asarray(sc.param_map["Sensor[0]"]._primary_edges(True)).shape[0]
-    dev = "cuda"
-    g_tri = torch.zeros((n_tris, 22), dtype=torch.float32, device=dev)
-    g_bsdf = torch.zeros((max(1, len(spec.bsdfs)), 3), dtype=torch.float32, device=dev)
-    g_em = torch.zeros((max(1, len(spec.emitters)), 3), dtype=torch.float32, device=dev)
-    g_sec = torch.zeros((max(1, n_sec), 6), dtype=torch.float32, device=dev)
-    g_prim = torch.zeros((max(1, n_prim), 4), dtype=torch.float32, device=dev)
-    g_cam = torch.zeros(16, dtype=torch.float32, device=dev)
-    g = cabi.Grads(g_tri.data_ptr(), g_bsdf.data_ptr(), g_em.data_ptr(), g_sec.data_ptr(), g_prim.data_ptr())
-    g.g_camera = g_cam.data_ptr()
+    g, bufs, _ = adjoint_buffers.allocate(sc, spec, ("g_camera",))
     cabi.check(fn(sc._hip_handle(), C.byref(args), w.data_ptr(), C.byref(g), None))
     torch.cuda.synchronize()
-    return {"g_triangles": g_tri.cpu().numpy().astype(np.float64), "g_sec_edges": g_sec.cpu().numpy().astype(np.float64),
-            "g_prim_edges": g_prim.cpu().numpy().astype(np.float64), "g_camera": g_cam.cpu().numpy().astype(np.float64)}
+    return adjoint_buffers.to_f64(bufs)
 
 
 @pytest.mark.parametrize("scene", ["cbox", "sphere"])

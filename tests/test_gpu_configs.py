@@ -17,6 +17,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import adjoint_buffers
 import product
 import scenes
 
@@ -89,13 +90,10 @@ def test_primary_edge_samples_that_cannot_contribute_are_not_traced(env, scene):
     # reverse mode: only the rows of the moving edges are wanted
     gen = torch.Generator(device="cpu").manual_seed(5)
     w = (torch.rand((n, 3), generator=gen) + 0.5).to("cuda")
-    snap = sc._snapshot()
-    n_tris, n_sec = np.asarray(snap["d_triangles"]).shape[0], np.asarray(snap["d_sec_edges"]).shape[0]
     rows = []
     for filt in (None, torch.from_numpy(moving.astype(np.uint8)).to("cuda")):
-        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device="cuda")
-        g_tri, g_bsdf, g_em, g_sec, g_prim = z(n_tris, 22), z(max(1, len(spec.bsdfs)), 3), z(max(1, len(spec.emitters)), 3), z(max(1, n_sec), 6), z(moving.size, 4)
-        g = cabi.Grads(g_tri.data_ptr(), g_bsdf.data_ptr(), g_em.data_ptr(), g_sec.data_ptr(), g_prim.data_ptr())
+        g, bufs, _ = adjoint_buffers.allocate(sc, spec)
+        g_prim = bufs["g_prim_edges"]
         if filt is not None:
             g.prim_edge_filter = filt.data_ptr()
         a = cabi.make_args(max_depth=depth, seeds=seeds, terms=2)
@@ -131,10 +129,8 @@ def _oracle_pinned_backward(env, orc_mod, sc, spec, ref, depth, seeds, rank, cou
         _img, d_img = ref.render_d(max_depth=depth, seeds=seeds, terms=terms, shard_rank=rank, shard_count=count, guiding=guiding_ref)
         lhs = float((d_img.astype(np.float64) * wd).sum())
         scale = float((np.abs(d_img).astype(np.float64) * wd).sum()) + 1e-12
-        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device="cuda")
-        g_tri, g_bsdf, g_em = z(d_tri.shape[0], 22), z(max(1, len(spec.bsdfs)), 3), z(max(1, len(spec.emitters)), 3)
-        g_sec, g_prim = z(max(1, d_sec.shape[0]), 6), z(max(1, d_prim.shape[0]), 4)
-        g = cabi.Grads(g_tri.data_ptr(), g_bsdf.data_ptr(), g_em.data_ptr(), g_sec.data_ptr(), g_prim.data_ptr())
+        g, bufs, _ = adjoint_buffers.allocate(sc, spec)
+        g_tri, g_bsdf, g_em, g_sec, g_prim = (bufs[f] for f in adjoint_buffers.ROWS)
         if prim_filter:
             # psdr_grads.prim_edge_filter: only the rows of the edges that move are wanted (what the host core asks for); the oracle still traces every sample
             moving = torch.from_numpy((np.abs(d_prim).sum(axis=1) > 0).astype(np.uint8)).to("cuda")
