@@ -249,7 +249,22 @@ typedef struct psdr_counters {
 /* Threading / streams: every entry point that launches kernels takes the stream to launch on.  Calls on one stream are ordered by
  * the stream.  The launches of ONE scene share device scratch (work-queue ring, traversal-stack overflow, adjoint records), so calls
  * on the same scene from different streams or host threads are serialised by the library: a call first makes its stream wait for
- * the completion event of the scene's previous call (no host synchronisation).  Different scenes run concurrently. */
+ * the completion event of the scene's previous call (no host synchronisation).  Different scenes run concurrently.
+ *
+ * THE STREAM CONTRACT (tests/test_gpu_streams.py runs every entry point on a side stream behind a delay):
+ *   1. All device work of a call that takes a `stream` - kernels, clears, copies, the scratch it allocates inside the call - is issued to that stream or to streams
+ *      the call forks from it and joins into it before it returns (the edge terms of a BVH scene's renderD).  Nothing goes to the NULL stream, with which streams
+ *      created non-blocking (torch's pool streams) do not synchronise.
+ *   2. The caller's duty: every device input of the call is ready ON THE STREAM THAT IS PASSED (written by work queued on it earlier, or complete before the call),
+ *      and the outputs are read on that stream or after it has been waited for.
+ *   3. Every psdr_hip_*_create (scene, guiding_build, precond, denoise, vdenoise, subdiv) returns with the handle usable on ANY stream and with the caller's host and
+ *      device arrays free again: it synchronises `stream` (the scene calls: the NULL stream they work on) before it returns.  They are cold paths.
+ *   4. What the library serialises: calls on ONE SCENE from different streams (above).  psdr_hip_scene_update waits on the host for the scene's last call before it
+ *      rewrites anything, works on the NULL stream and synchronises it before it returns: a render queued before it sees the old state, one issued after it the new.
+ *   5. What it does not: a denoise / vdenoise / precond handle owns work frames, so calls on one such handle must follow each other on one stream or be ordered
+ *      by the caller; subdiv handles are read-only after the create and may be applied from any number of streams.
+ * "No call synchronises the device" (above) means hipDeviceSynchronize; the calls that wait for their own stream say so: the creates, psdr_hip_guiding_build,
+ * psdr_hip_precond_solve (it reads its residuals), the *_counted renders, and a render that has to grow the scene's scratch (first call, or a larger one). */
 const char *psdr_hip_last_error(void);
 int psdr_hip_abi_version(void);
 int psdr_hip_device_count(void);
@@ -335,6 +350,9 @@ int psdr_hip_scene_check_edges(const psdr_hip_scene *scene, const psdr_scene_sna
 int psdr_hip_scene_edge_path(const psdr_hip_scene *scene, int32_t *path, int64_t *edge_bytes);
 /* BVH statistics for DESIGN/bench: nodes, leaves, max depth, bytes resident in LDS per workgroup */
 int psdr_hip_scene_stats(const psdr_hip_scene *scene, int32_t *n_nodes, int32_t *n_leaves, int32_t *max_depth, int32_t *lds_bytes);
+/* bytes of the scene's global per-lane records of the interior adjoint: 0 until a psdr_hip_render_d_bwd whose records do not fit LDS (deep paths) has allocated them
+ * inside the call, on its stream - what a test reads to know that such a call took that path */
+int64_t psdr_hip_scene_adjoint_record_bytes(const psdr_hip_scene *scene);
 /* The live-pixel mask of a sensor (HOST bits[(width*height + 31) / 32], bit y*width + x; either pointer may be NULL): a pixel is dead when
  * no ray through its square can reach a triangle - the conservative screen-space coverage of the scene, built at scene creation.  The
  * interior term of every sample of a dead pixel is exactly zero (Integrator::__render, src/integrator/integrator.cpp:103-131: the
@@ -560,7 +578,7 @@ int psdr_hip_adaptive_merge_adj(const int32_t *offsets, int32_t n, int64_t total
  * In float32 as written: d2 by G subtractions, squares and additions in channel order (no fused multiply-add), expf, the 25 taps added row by row (j outer, i inner),
  * 1 / N_l by one IEEE division when the handle is made, and one multiplication by it per element (apply: of the sum; transpose: of the source).
  *
- * create copies the guides into planes, computes the L planes of 1 / N_l and allocates two work frames: the guides may be released once the stream has passed the call.
+ * create copies the guides into planes, computes the L planes of 1 / N_l and allocates two work frames: it waits for `stream`, so the guides are the caller's again when it returns.
  * G == 0 takes guides == NULL and gives the plain B3-spline a-trous smoother.  The handle holds the work frames: one apply or apply_adj at a time per handle. */
 typedef struct psdr_hip_denoise psdr_hip_denoise;
 int psdr_hip_denoise_create(const float *guides, int32_t G, int32_t W, int32_t H, int32_t L, psdr_hip_denoise **out, void *stream);

@@ -429,6 +429,12 @@ int psdr_hip_li_lanes(const psdr_hip_scene *sc, const psdr_render_args *a, int64
     return render_impl<false>(sc, a, false, nullptr, nullptr, out, lane_begin, lane_end, nullptr, stream);
 }
 
+int64_t psdr_hip_scene_adjoint_record_bytes(const psdr_hip_scene *sc) {
+    if (!sc) return 0;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    return (int64_t) sc->adj_rec_bytes;
+}
+
 int psdr_hip_scene_tex_layout(const psdr_hip_scene *sc, int64_t *offsets, int64_t *total) {
     if (!sc) return fail("null scene");
     if (total) *total = sc->tex_total;
@@ -536,7 +542,7 @@ static int render_bwd_impl(const psdr_hip_scene *sc, const psdr_render_args *a, 
                 if (need > sc->adj_rec_bytes) {
                     // (every earlier user of the records was ordered before this stream by the guard: its completion is this stream's)
                     if (sc->adj_rec.p) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(sc->adj_rec.p)); sc->adj_rec.p = nullptr; sc->adj_rec_bytes = 0; }
-                    if (sc->adj_rec.upload(nullptr, need)) return 1;
+                    if (sc->adj_rec.clear_on(need, st)) return 1;          // (on the caller's stream: a clear on the null stream is not ordered before the kernel below)
                     sc->adj_rec_bytes = need;
                 }
                 P.rec_global = (float *) sc->adj_rec.p;
@@ -709,7 +715,7 @@ int psdr_hip_guiding_build(const psdr_hip_scene *sc, int32_t sensor_id, int32_t 
     SCRATCH_GUARD(sc, stream);
     hipStream_t st = (hipStream_t) stream;
     DevBuf mass;
-    if (mass.upload(nullptr, sizeof(float) * cells)) return 1;
+    if (mass.clear_on(sizeof(float) * cells, st)) return 1;        // (on the caller's stream, as the rounds that add into it)
     const long long nl = cells * reso[3];
     for (int r = 0; r < nrounds; ++r)
         LAUNCH_RAYS(k_guiding_round, sc, nl, st, sc->blob.as<float4>(), sc->T, sc->E, sc->sensors[sensor_id], G, reso[3], seed, r, (float *) mass.p);
@@ -725,16 +731,18 @@ int psdr_hip_guiding_build(const psdr_hip_scene *sc, int32_t sensor_id, int32_t 
         sum += g->mass[i]; acc += (double) g->mass[i]; cmf[i] = (float) acc;
     }
     G.sum = sum;
-    if (g->pmf.upload(g->mass.data(), sizeof(float) * cells) || g->cmf.upload(cmf.data(), sizeof(float) * cells)) return 1;
+    // the tables go out on the caller's stream; the call returns after they have arrived (cmf and guide are locals), usable on any stream
+    if (g->pmf.upload_on(g->mass.data(), sizeof(float) * cells, st) || g->cmf.upload_on(cmf.data(), sizeof(float) * cells, st)) return 1;
     G.pmf = g->pmf.as<float>(); G.cmf = g->cmf.as<float>();
     {
         std::vector<int> guide;
         build_cdf_guide(cmf.data(), (int) cells, sum, guide);
         G.guide = nullptr; G.guide_n = 0;
         if (!guide.empty()) {
-            if (g->guide.upload(guide.data(), guide.size() * sizeof(int))) return 1;
+            if (g->guide.upload_on(guide.data(), guide.size() * sizeof(int), st)) return 1;
             G.guide = g->guide.as<int>(); G.guide_n = (int) guide.size() - 1;
         }
+        HIPCHK(hipStreamSynchronize(st));
     }
     *out = g.release();
     return 0;

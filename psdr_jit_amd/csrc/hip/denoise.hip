@@ -151,6 +151,7 @@ int psdr_hip_denoise_create(const float *guides, int32_t G, int32_t W, int32_t H
         h->work[1] = h->work[0] + (size_t) kMaxC * n;
         for (int l = 0; l < L; ++l) launch_level<kNorm>(G, 0, Level{{W, H, 1 << l, 0, 0}, h->planes, nullptr, nullptr, h->inv_n + (size_t) l * n}, st);
         e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);          // the handle is usable on any stream and `guides` is the caller's again when the call returns
     }
     if (e != hipSuccess) { delete h; return psdr::api_fail(std::string(me) + ": " + hipGetErrorString(e)); }
     *out = h;

@@ -49,6 +49,22 @@ struct DevBuf {
         if (src) HIPCHK(hipMemcpy(p, src, n, hipMemcpyHostToDevice)); else HIPCHK(hipMemset(p, 0, n));
         return 0;
     }
+    // The two forms above go through the NULL stream: for scene_sync and the synchronising test aids only.  An entry point that takes a stream orders
+    // its clears and copies on that stream (torch's pool streams do not synchronise with the null stream):
+    // n zero bytes, cleared on `st`
+    int clear_on(size_t n, hipStream_t st) {
+        if (n == 0) n = 16;
+        if (ensure(n)) return 1;
+        HIPCHK(hipMemsetAsync(p, 0, n, st));
+        return 0;
+    }
+    // n bytes of host memory, copied on `st`; `src` is the caller's again only after a synchronisation of `st`
+    int upload_on(const void *src, size_t n, hipStream_t st) {
+        if (n == 0) return ensure(0);
+        if (ensure(n)) return 1;
+        HIPCHK(hipMemcpyAsync(p, src, n, hipMemcpyHostToDevice, st));
+        return 0;
+    }
     template <typename T> const T *as() const { return reinterpret_cast<const T *>(p); }
 };
 

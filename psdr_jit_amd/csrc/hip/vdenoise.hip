@@ -208,6 +208,7 @@ int psdr_hip_vdenoise_create(const float *guides, int32_t G, int32_t W, int32_t 
         h->vwork[0] = h->work[1] + (size_t) kMaxC * n;
         h->vwork[1] = h->vwork[0] + n;
         e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t) stream);          // the handle is usable on any stream and `guides` is the caller's again when the call returns
     }
     if (e != hipSuccess) { delete h; return psdr::api_fail(std::string(me) + ": " + hipGetErrorString(e)); }
     *out = h;
