@@ -360,6 +360,13 @@ int64_t psdr_hip_scene_adjoint_record_bytes(const psdr_hip_scene *scene);
  * scenes, a triangle across the camera plane, 2^31 lanes or more, less than a quarter of the frame dead, PSDR_NO_LIVE_MASK=1 in the
  * environment). */
 int psdr_hip_scene_live_pixels(const psdr_hip_scene *scene, int32_t sensor_id, uint32_t *bits, int64_t *n_live);
+/* The camera-ray table of a sensor (ADDED under version 16; every pointer may be NULL): the same screen-space coverage kept apart per triangle - one 64-bit
+ * word per cell of *cell x *cell pixels (1, or the smallest power of two that keeps the table within 4 MB), HOST table[*cells_h * *cells_w], cell (y / *cell) *
+ * *cells_w + x / *cell, bit k = the triangle in device slot k (psdr_hip_ray_intersect_ad's out_hit) comes within a quarter of a pixel of the cell.  The interior
+ * term of psdr_hip_render_c / _d_fwd resolves a sample's camera ray against the triangles of its pixel's cell alone, with the tracer's own test and its
+ * (t, id) order, so the hit is the tracer's.  *cell = 0: no table (more than 64 triangles, an environment map, a triangle across the camera plane,
+ * an orthographic sensor, PSDR_NO_CAM_TABLE=1 in the environment: every camera ray goes through the tracer, as before the table existed). */
+int psdr_hip_scene_camera_table(const psdr_hip_scene *scene, int32_t sensor_id, int32_t *cell, int32_t *cells_w, int32_t *cells_h, uint64_t *table);
 /* bytes of one node of the 4-wide BVH this build walks (64: quantised child boxes, csrc/hip/bvh.h) - the unit of the algorithmic
  * bytes bench.py prices a node visit at */
 int psdr_hip_bvh_node_bytes(void);

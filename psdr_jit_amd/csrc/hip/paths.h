@@ -169,6 +169,14 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
     auto park_i = [&](int r, int v) { cold[r * kBlock] = __int_as_float(v); };
     static_assert(kColdRows >= 15, "scene_dev.h::kColdRows");
     static_assert(MODE == 0 || !AD, "the primary-edge paths are traced in C mode");
+    // CAMERA RAYS FROM THE SENSOR'S TRIANGLE TABLE (interior term).  Which triangles a camera ray can hit is known per pixel (SensorDev::cam_tab): a lane that takes a
+    // work item resolves its camera ray against those few triangles while it regenerates (trace_listed: the tracer's exact test and (t, id) order, without the filter
+    // pass over every primitive) and enters the loop AT its first vertex, instead of spending one iteration of the whole wave on a trace2 of the camera ray: one
+    // iteration in four of a depth-3 sample.  The PathTracer kernels of the LDS classes; the counted builds and the per-lane output keep the traced route, and so does a
+    // single lane whose pixel id lies outside the frame (batch lists) - both routes share a wave.  The primary-edge term (MODE 1) keeps the traced route: there the
+    // camera rays already share one trace2 pass, and resolving both from the table while regenerating cost more than the iteration it saved (LABNOTES).
+    constexpr bool kCamTab = in_lds(LDS) && !COUNT && MODE == 0;
+    const bool use_tab = kCamTab && cam.cam_tab != nullptr && P.max_depth > 0 && sw::lanes_out(P) == nullptr && sw::field(S) < 0 && !sw::ortho(cam);
 
 #if PSDR_DIAG == 6
     // phase timers (wave cycles, every lane adds the same delta): c_rays = fetch + regeneration, c_nodes = drawing the vertex's
@@ -199,6 +207,8 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
             const int n_need = __popcll(need);
             long long item = q_end;                       // the work item this lane starts (q_end: none)
             int n_taken;                                  // queue positions consumed
+            bool tab_on = false;                          // this lane's camera ray is resolved from the table: tab_m lists its candidate slots
+            unsigned long long tab_m = 0ull;
             if (MODE == 0 && !COUNT && cam.live != nullptr && sw::lanes_out(P) == nullptr && P.end < (1ll << 31)) {      // (the counted builds and the per-lane output see every sample)
                 // LIVE PIXELS ONLY (round 4): take_live_items above
                 item = take_live_items(T, cam, P, !busy, q_next, q_end, lane_id, lt_mask, n_taken);
@@ -220,6 +230,11 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                         const float bx = (float) (pix % T.width), by = (float) (pix / T.width);
                         const float jx = rng.next_1d(), jy = rng.next_1d();
                         ext = sample_primary_ray<AD, !sw::lean>(cam, (bx + jx) / (float) T.width, (by + jy) / (float) T.height);
+                        if constexpr (kCamTab) {
+                            if (use_tab && (unsigned) pix < (unsigned) (T.width * T.height)) {      // (a pixel id outside the frame - batch rendering - is left to the tracer)
+                                tab_on = true; tab_m = cam_tab_cell(cam, pix % T.width, pix / T.width);
+                            }
+                        }
                     } else {
                         // PerspectiveCamera::sample_primary_edge, reference perspective.cpp:200-226
                         rng.seed(P.seed + (unsigned long long) lane, (unsigned long long) lane, P.skip);
@@ -249,6 +264,21 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                 }
             }
             q_next += n_taken;
+            if constexpr (kCamTab) {
+                if (__ballot(tab_on) != 0ull) {
+                    // the camera hits of the lanes that have just started, and their first vertex (path.cpp:38-43) - what the first loop iteration did for them
+                    const Hit h0 = trace_listed<LDS>(S, detach(ext.o), detach(ext.d), tab_m);
+                    if (tab_on) {
+                        if (h0.slot < 0) busy = false;                // the camera ray leaves the scene: Li = 0, nothing to add
+                        else {
+                            const Its<AD> it0 = make_its<AD, LDS, true>(S, h0, ext, false);
+                            its = it0;
+                            if (!P.hide_emitters) res = eval_Le<AD, LDS>(S, it0, true);
+                            depth = 0;
+                        }
+                    }
+                }
+            }
         }
         PSDR_PHASE(c_rays);
         if (__ballot(busy) == 0ull) { if (exhausted && q_next >= q_end) break; continue; }

@@ -20,6 +20,7 @@
 #include "scene_obj.h"
 #include "bvh.h"
 #include "filter.h"
+#include "cam_table.h"
 #include "blob_rows.h"
 #include "blob_layout.h"
 #include "../host/hnum.h"
@@ -33,56 +34,43 @@ constexpr double kRebuildFactor = 1.4;          // a refitted tree whose SAH cos
 
 static inline double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
-// Conservative screen-space coverage of the scene for one sensor: bit (y * width + x) = some triangle's projection (world_to_sample, a projective map: the
-// image of a triangle in front of the camera is the triangle of its projected vertices) comes within a quarter of a pixel of the pixel's square.  Row by row:
-// the x-extent of the triangle inside the (padded) row slab.  false = no mask (a triangle crosses the camera plane: its image is not a triangle).
-static bool build_live_mask(const psdr_triangles &tr, const float *w2s, int W, int H, std::vector<unsigned> &mask) {
-    const double pad = 0.25;
+// The live-pixel mask of one sensor from the scene's screen-space coverage (cam_table.h): bit (y * width + x) = some triangle comes within a quarter of a pixel
+// of the pixel's square.
+static void fill_live_mask(const ScreenTris &st, int W, int H, std::vector<unsigned> &mask) {
     mask.assign(((size_t) W * H + 31) / 32, 0u);
-    for (int t = 0; t < tr.n_triangles; ++t) {
-        double X[3], Y[3];
-        int behind = 0;
-        for (int v = 0; v < 3; ++v) {
-            double p[3];
-            for (int c = 0; c < 3; ++c) p[c] = (double) tr.p0[3 * t + c] + (v == 1 ? (double) tr.e1[3 * t + c] : (v == 2 ? (double) tr.e2[3 * t + c] : 0.0));
-            if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))) return false;
-            const double x = w2s[0] * p[0] + w2s[1] * p[1] + w2s[2] * p[2] + w2s[3], y = w2s[4] * p[0] + w2s[5] * p[1] + w2s[6] * p[2] + w2s[7];
-            const double w = w2s[12] * p[0] + w2s[13] * p[1] + w2s[14] * p[2] + w2s[15];
-            if (!(w > 1e-9)) { ++behind; continue; }
-            X[v] = x / w * W; Y[v] = y / w * H;
+    cover_rows(st, W, H, [&](int, int row, int c0, int c1) {
+        // bits [b0, b1] of the mask, a word at a time (a wall of the Cornell box at 2048 x 2048 is four million pixels per triangle)
+        const size_t b0 = (size_t) row * W + c0, b1 = (size_t) row * W + c1;
+        for (size_t wi = b0 >> 5; wi <= (b1 >> 5); ++wi) {
+            const unsigned lo_bit = wi == (b0 >> 5) ? (unsigned) (b0 & 31) : 0u, hi_bit = wi == (b1 >> 5) ? (unsigned) (b1 & 31) : 31u;
+            const unsigned m_hi = hi_bit == 31u ? 0xffffffffu : ((1u << (hi_bit + 1u)) - 1u);
+            mask[wi] |= m_hi & ~((1u << lo_bit) - 1u);
         }
-        if (behind == 3) continue;              // behind the camera: no forward ray reaches it
-        if (behind != 0) return false;
-        const double ymin = std::min(Y[0], std::min(Y[1], Y[2])) - pad, ymax = std::max(Y[0], std::max(Y[1], Y[2])) + pad;
-        if (!(ymax >= 0.0 && ymin < (double) H)) continue;
-        const int r0 = (int) std::max(0.0, std::floor(ymin)), r1 = (int) std::min((double) (H - 1), std::floor(ymax));
-        for (int row = r0; row <= r1; ++row) {
-            const double lo = row - pad, hi = row + 1 + pad;
-            double xmin = 1e300, xmax = -1e300;
-            for (int v = 0; v < 3; ++v) {
-                if (Y[v] >= lo && Y[v] <= hi) { xmin = std::min(xmin, X[v]); xmax = std::max(xmax, X[v]); }
-                const int u = (v + 1) % 3;
-                const double dy = Y[u] - Y[v];
-                if (dy != 0.0)
-                    for (double yc : {lo, hi}) {
-                        const double s = (yc - Y[v]) / dy;
-                        if (s >= 0.0 && s <= 1.0) { const double xc = X[v] + s * (X[u] - X[v]); xmin = std::min(xmin, xc); xmax = std::max(xmax, xc); }
-                    }
-            }
-            if (xmin > xmax) continue;
-            xmin -= pad; xmax += pad;
-            if (!(xmax >= 0.0 && xmin < (double) W)) continue;
-            const int c0 = (int) std::max(0.0, std::floor(xmin)), c1 = (int) std::min((double) (W - 1), std::floor(xmax));
-            // bits [b0, b1] of the mask, a word at a time (a wall of the Cornell box at 2048 x 2048 is four million pixels per triangle)
-            const size_t b0 = (size_t) row * W + c0, b1 = (size_t) row * W + c1;
-            for (size_t wi = b0 >> 5; wi <= (b1 >> 5); ++wi) {
-                const unsigned lo_bit = wi == (b0 >> 5) ? (unsigned) (b0 & 31) : 0u, hi_bit = wi == (b1 >> 5) ? (unsigned) (b1 & 31) : 31u;
-                const unsigned m_hi = hi_bit == 31u ? 0xffffffffu : ((1u << (hi_bit + 1u)) - 1u);
-                mask[wi] |= m_hi & ~((1u << lo_bit) - 1u);
-            }
-        }
+    });
+}
+
+// The camera-ray table of one sensor (SensorDev::cam_tab, cam_table.h): the same coverage, one bit per traversal slot and cell, made where it is read - one thread
+// per cell, from the traversal rows of the blob (slot order) and the sensor's world_to_sample, in the host's own double arithmetic.  At most kBruteForceMax
+// triangles, none of them across the camera plane (the host has checked): their projections wait in LDS.
+struct W2S { float m[16]; };
+__global__ void k_cam_table(const float4 *__restrict__ blob, int trav_off, int n_tris, const W2S w2s, int W, int H, int shift, int cells_w, int cells_h,
+                            unsigned long long *__restrict__ table) {
+    __shared__ double sX[3 * kBruteForceMax], sY[3 * kBruteForceMax];
+    __shared__ int s_front[kBruteForceMax];
+    for (int k = threadIdx.x; k < n_tris; k += blockDim.x) {
+        const float4 a = blob[trav_off + 3 * k], b = blob[trav_off + 3 * k + 1], c = blob[trav_off + 3 * k + 2];
+        const float p0[3] = {a.x, a.y, a.z}, e1[3] = {a.w, b.x, b.y}, e2[3] = {b.z, b.w, c.x};
+        s_front[k] = project_triangle(w2s.m, p0, e1, e2, W, H, &sX[3 * k], &sY[3 * k]) == 0;
     }
-    return true;
+    __syncthreads();
+    const int cell = blockIdx.x * blockDim.x + threadIdx.x;
+    if (cell >= cells_w * cells_h) return;
+    const int g = 1 << shift, x0 = (cell % cells_w) << shift, y0 = (cell / cells_w) << shift;
+    const int x1 = x0 + g - 1 < W - 1 ? x0 + g - 1 : W - 1, y1 = y0 + g - 1 < H - 1 ? y0 + g - 1 : H - 1;
+    unsigned long long word = 0ull;
+    for (int k = 0; k < n_tris; ++k)
+        if (s_front[k] && covers_cell(&sX[3 * k], &sY[3 * k], W, H, x0, x1, y0, y1)) word |= 1ull << k;
+    table[cell] = word;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -828,6 +816,7 @@ struct SceneSync {
     bool blob_moved = false, dev_geo = false;
     int sec_cdf_mode = 0, edge_path = 0;
     int64_t sec_bytes = 0, edge_bytes = 0;          // sec_bytes: what goes up for the secondary-edge DISTRIBUTION (pmf, cmf, search table)
+    std::vector<int> tabs_to_fill;                  // sensors whose camera-ray table is made once the rows are on the device (launch_cam_tables)
     psdr_update_info info{};
 
     SceneSync(psdr_hip_scene *sc_, const psdr_scene_snapshot *s_, const EdgeRequest *ereq_, bool fresh_) : sc(sc_), s(s_), ereq(ereq_), fresh(fresh_), tr(s_->tris), T(sc_->T), E(sc_->E) {}
@@ -1152,12 +1141,19 @@ struct SceneSync {
         const bool same_view = od && !geo && 16 * (size_t) k + 16 <= w2s_old.size() && std::memcmp(&w2s_old[16 * (size_t) k], r.world_to_sample, 64) == 0 &&
                                Told.width == T.width && Told.height == T.height && (Told.env_emitter >= 0) == (T.env_emitter >= 0) &&
                                ((long long) Told.width * Told.height * std::max(1, Told.spp) < (1ll << 31)) == ((long long) T.width * T.height * std::max(1, T.spp) < (1ll << 31));
-        if (same_view) { d.live = od->live; return 0; }
-        d.live = nullptr;
+        // ... and so is the camera-ray table (brute-force scenes, perspective sensors), with the same lifetime
+        if (same_view && (od->ortho != 0) == (d.ortho != 0)) { d.live = od->live; d.cam_tab = od->cam_tab; d.tab_shift = od->tab_shift; d.tab_w = od->tab_w; return 0; }
+        d.live = nullptr; d.cam_tab = nullptr; d.tab_shift = 0; d.tab_w = 0;
         std::vector<unsigned> live;
         static const bool no_live = std::getenv("PSDR_NO_LIVE_MASK") != nullptr;       // documented switch (include/psdr_hip.h): render the provably-zero samples as well
-        bool use = !no_live && T.env_emitter < 0 && (long long) s->width * s->height * std::max(1, s->spp) < (1ll << 31) && build_live_mask(s->tris, r.world_to_sample, s->width, s->height, live);
+        static const bool no_tab = std::getenv("PSDR_NO_CAM_TABLE") != nullptr;        // documented switch (include/psdr_hip.h): every camera ray through the tracer
+        bool use = !no_live && T.env_emitter < 0 && (long long) s->width * s->height * std::max(1, s->spp) < (1ll << 31);
+        const bool use_tab = !no_tab && T.env_emitter < 0 && s->tris.n_triangles <= kBruteForceMax && !d.ortho;
+        ScreenTris st;
+        const bool projected = (use || use_tab) && project_tris(s->tris.p0, s->tris.e1, s->tris.e2, s->tris.n_triangles, r.world_to_sample, s->width, s->height, st);
+        use = use && projected;
         if (use) {       // worth a window of bit tests per regeneration only when a good part of the frame is dead (the sphere box, all of it live: +1.7 % with the mask)
+            fill_live_mask(st, s->width, s->height, live);
             long long n_set = 0;
             for (unsigned x : live) n_set += __builtin_popcount(x);
             use = n_set * 4 <= (long long) s->width * s->height * 3;
@@ -1165,6 +1161,17 @@ struct SceneSync {
         if (use) { if (sync_named(sc, "sensor." + std::to_string(k) + ".live", live.data(), live.size() * sizeof(unsigned), false, d.live, info)) return 1; }
         else live.clear();
         sc->live_host[(size_t) k].swap(live);
+        // (made on the device once the triangle rows of this state are there - launch_cam_tables: nothing is sent, and the allocation is scratch the device fills itself)
+        if (!sc->cam_tabs[(size_t) k]) sc->cam_tabs[(size_t) k] = std::make_unique<DevBuf>();
+        DevBuf &tab = *sc->cam_tabs[(size_t) k];
+        if (use_tab && projected) {
+            d.tab_shift = cam_table_shift(s->width, s->height);
+            d.tab_w = (s->width + (1 << d.tab_shift) - 1) >> d.tab_shift;
+            const size_t cells = (size_t) d.tab_w * (size_t) ((s->height + (1 << d.tab_shift) - 1) >> d.tab_shift);
+            if (tab.ensure(cells * sizeof(uint64_t))) return 1;
+            d.cam_tab = tab.as<unsigned long long>();
+            tabs_to_fill.push_back(k);
+        } else if (tab.p) { HIPCHK(hipFree(tab.p)); tab.p = nullptr; tab.bytes = 0; }
         return 0;
     }
 
@@ -1174,6 +1181,7 @@ struct SceneSync {
         sc->sensors.assign((size_t) s->n_sensors, SensorDev{});
         sc->sensor_w2s.assign(16 * (size_t) s->n_sensors, 0.f);
         sc->live_host.resize((size_t) s->n_sensors);
+        sc->cam_tabs.resize((size_t) s->n_sensors);
         sc->pe_ids.resize((size_t) s->n_sensors);
         edge_path = sec_cdf_mode;
         bool any_sensor_dev = false;
@@ -1354,6 +1362,20 @@ struct SceneSync {
         return 0;
     }
 
+    // the camera-ray tables the sensors asked for (sensor()), from the triangle rows of this state: after the sections were sent and the device's rows computed
+    int launch_cam_tables() {
+        for (int k : tabs_to_fill) {
+            const SensorDev &d = sc->sensors[(size_t) k];
+            const int cells_h = (s->height + (1 << d.tab_shift) - 1) >> d.tab_shift, cells = d.tab_w * cells_h;
+            W2S w2s;
+            std::memcpy(w2s.m, s->sensors[k].world_to_sample, 64);
+            hipLaunchKernelGGL(k_cam_table, dim3((cells + 255) / 256), dim3(256), 0, (hipStream_t) nullptr, sc->blob.as<float4>(), T.trav_off, T.n_tris, w2s, s->width, s->height,
+                               d.tab_shift, d.tab_w, cells_h, (unsigned long long *) sc->cam_tabs[(size_t) k]->p);
+        }
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+
     // scene class, launch geometry
     int launch_geometry() {
         const size_t stack_bytes = (size_t) T.stack_depth * kBlock * sizeof(int);
@@ -1447,6 +1469,7 @@ static int scene_sync(psdr_hip_scene *sc, const psdr_scene_snapshot *s, unsigned
         }
     }
     if (c.launch_geometry()) return 1;
+    if (c.launch_cam_tables()) return 1;
     HIPCHK(hipStreamSynchronize(nullptr));
     c.info.ms_total = ms_since(t_start);
     sc->edge_path = c.edge_path; sc->edge_bytes = c.edge_bytes;
@@ -1702,6 +1725,19 @@ int psdr_hip_scene_live_pixels(const psdr_hip_scene *sc, int32_t sensor_id, uint
         count += __builtin_popcount(w);
     }
     if (n_live) *n_live = count;
+    return 0;
+}
+
+int psdr_hip_scene_camera_table(const psdr_hip_scene *sc, int32_t sensor_id, int32_t *cell, int32_t *cells_w, int32_t *cells_h, uint64_t *table) {
+    if (!sc) return fail("null scene");
+    if (sensor_id < 0 || sensor_id >= (int) sc->sensors.size()) return fail("Invalid sensor id!");
+    const SensorDev &d = sc->sensors[(size_t) sensor_id];
+    const bool none = d.cam_tab == nullptr;
+    const int g = none ? 0 : 1 << d.tab_shift, ch = none ? 0 : (sc->T.height + g - 1) / g;
+    if (cell) *cell = g;
+    if (cells_w) *cells_w = none ? 0 : d.tab_w;
+    if (cells_h) *cells_h = ch;
+    if (table && !none) HIPCHK(hipMemcpy(table, d.cam_tab, sizeof(uint64_t) * (size_t) d.tab_w * (size_t) ch, hipMemcpyDeviceToHost));     // (a test aid: synchronises)
     return 0;
 }
 

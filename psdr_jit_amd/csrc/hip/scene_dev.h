@@ -125,6 +125,12 @@ struct SensorDev {
     // a sample of such a pixel contributes exactly zero to the interior term, so the kernels skip it before they seed it.  NULL = every pixel is live
     // (environment-lit scenes: the bounding cube fills the frame; a triangle that crosses the camera plane; more than 2^31 lanes)
     const unsigned *live;
+    // one 64-bit word per cell of the frame (a pixel, or a tile of 2^tab_shift x 2^tab_shift pixels; tab_w cells per row): bit k = the triangle in traversal slot k
+    // comes within a quarter of a pixel of the cell - the same coverage as `live`, kept apart per triangle (cam_table.h).  The interior term resolves a camera
+    // ray against these triangles alone (paths.h, trace_listed below).  NULL = no table (more than kBruteForceMax triangles, an environment map, a triangle that
+    // crosses the camera plane, an orthographic sensor).  Last in the struct: the fields above keep their kernel-argument offsets
+    const unsigned long long *cam_tab;
+    int tab_shift, tab_w;
 };
 
 struct Counters { unsigned long long rays, nodes, tris, hits; };
@@ -476,6 +482,59 @@ PSDR_DEV void trace2(SceneView<LDS> &S, const Vec3f &oA_, const Vec3f &dA, bool 
         PSDR_TPHASE(c_tris);
     }
 #undef PSDR_TPHASE
+}
+
+// the cell of the sensor's camera-ray table (SensorDev::cam_tab) that pixel (ix, iy) of the frame belongs to
+PSDR_DEV unsigned long long cam_tab_cell(const SensorDev &cam, int ix, int iy) {
+    return cam.cam_tab[(iy >> cam.tab_shift) * cam.tab_w + (ix >> cam.tab_shift)];
+}
+
+// The closest hit of a ray whose candidate triangles are LISTED: bit k of `list` = the triangle in traversal slot k may be hit (camera rays: SensorDev::cam_tab).
+// No filter pass - the exact rounds of trace2's second phase over the set bits, the same packed arithmetic in the same operand order, the same comparisons and
+// the same (t, id) order, so the ray finds the hit trace2 finds whenever its list holds that triangle.  The two packed halves carry two candidates of the one ray
+// (the even and the odd slots: a round tests one of each); the closer of the halves' hits wins, ties to the smaller id.  Called by the whole wave: a lane without
+// a ray passes an empty list.  Brute-force scenes only (at most 64 slots).
+template <int LDS>
+PSDR_DEV Hit trace_listed(const SceneView<LDS> &S, const Vec3f &o, const Vec3f &d, unsigned long long list) {
+#pragma clang fp contract(off)
+    Hit hA, hB;
+    hA.slot = -1; hA.u = hA.v = hA.t = 0.f;
+    hB.slot = -1; hB.u = hB.v = hB.t = 0.f;
+    unsigned long long mA = list & 0x5555555555555555ull, mB = list & 0xaaaaaaaaaaaaaaaaull;
+    const SceneTables &T = *S.T;
+    const f2 dx = {d.x, d.x}, dy = {d.y, d.y}, dz = {d.z, d.z};
+    const f2 rox = {o.x, o.x}, roy = {o.y, o.y}, roz = {o.z, o.z};
+    float btA = __builtin_inff(), btB = __builtin_inff();
+    int bidA = 0x7fffffff, bidB = 0x7fffffff;
+    for (;;) {
+        const bool moreA = mA != 0ull, moreB = mB != 0ull;
+        if (__ballot(moreA || moreB) == 0ull) break;
+        const int kA = moreA ? __builtin_ctzll(mA) : 0, kB = moreB ? __builtin_ctzll(mB) : 0;
+        mA &= mA - 1ull; mB &= mB - 1ull;
+        const float4 aA4 = S.ld(T.trav_off + 3 * kA), bA4 = S.ld(T.trav_off + 3 * kA + 1), cA4 = S.ld(T.trav_off + 3 * kA + 2);
+        const float4 aB4 = S.ld(T.trav_off + 3 * kB), bB4 = S.ld(T.trav_off + 3 * kB + 1), cB4 = S.ld(T.trav_off + 3 * kB + 2);
+        const f2 p0x = {aA4.x, aB4.x}, p0y = {aA4.y, aB4.y}, p0z = {aA4.z, aB4.z};
+        const f2 e1x = {aA4.w, aB4.w}, e1y = {bA4.x, bB4.x}, e1z = {bA4.y, bB4.y};
+        const f2 e2x = {bA4.z, bB4.z}, e2y = {bA4.w, bB4.w}, e2z = {cA4.x, cB4.x};
+        const f2 hx = pk_fma(dy, e2z, -(dz * e2y)), hy = pk_fma(dz, e2x, -(dx * e2z)), hz = pk_fma(dx, e2y, -(dy * e2x));
+        const f2 det = pk_fma(e1z, hz, pk_fma(e1y, hy, e1x * hx));
+        f2 f; f.x = 1.f / det.x; f.y = 1.f / det.y;
+        const f2 sx = rox - p0x, sy = roy - p0y, sz = roz - p0z;
+        const f2 u = f * pk_fma(sz, hz, pk_fma(sy, hy, sx * hx));
+        const f2 qx = pk_fma(sy, e1z, -(sz * e1y)), qy = pk_fma(sz, e1x, -(sx * e1z)), qz = pk_fma(sx, e1y, -(sy * e1x));
+        const f2 v = f * pk_fma(dz, qz, pk_fma(dy, qy, dx * qx));
+        const f2 t = f * pk_fma(e2z, qz, pk_fma(e2y, qy, e2x * qx));
+        const f2 uv = u + v;
+        const int iA = __float_as_int(cA4.y), iB = __float_as_int(cB4.y);
+        const bool okA = moreA & (u.x >= 0.f) & (v.x >= 0.f) & (uv.x <= 1.f) & (t.x > kRayEpsilon) & (t.x < kTraceTMax);
+        const bool okB = moreB & (u.y >= 0.f) & (v.y >= 0.f) & (uv.y <= 1.f) & (t.y > kRayEpsilon) & (t.y < kTraceTMax);
+        const bool betA = okA & ((t.x < btA) | ((t.x == btA) & (iA < bidA)));
+        const bool betB = okB & ((t.y < btB) | ((t.y == btB) & (iB < bidB)));
+        if (betA) { btA = t.x; bidA = iA; hA.slot = kA; hA.u = u.x; hA.v = v.x; hA.t = t.x; }
+        if (betB) { btB = t.y; bidB = iB; hB.slot = kB; hB.u = u.y; hB.v = v.y; hB.t = t.y; }
+    }
+    if (hB.slot >= 0 && (hA.slot < 0 || btB < btA || (btB == btA && bidB < bidA))) hA = hB;
+    return hA;
 }
 
 } // namespace psdr

@@ -138,7 +138,8 @@ struct psdr_hip_scene {
     int n_leaves = 0, max_depth = 0, grid = 0;
     long long tex_total = 0;             // floats of all bitmap parameters (psdr_grads.g_tex)
     std::vector<std::vector<unsigned>> live_host;      // per sensor: the live-pixel mask (empty = every pixel is live), kept for psdr_hip_scene_live_pixels
-    psdr::DevBuf hot_map, hot_inv;       // adjoint accumulators kept in LDS: emitter triangles first, then by area (adjoint.h)
+    std::vector<std::unique_ptr<psdr::DevBuf>> cam_tabs;      // per sensor: the camera-ray table (SensorDev::cam_tab; no allocation = none), filled on the device (scene_build.hip::k_cam_table)
+    psdr::DevBuf hot_map, hot_inv;      // adjoint accumulators kept in LDS: emitter triangles first, then by area (adjoint.h)
     int n_hot = 0;
     std::vector<long long> tex_layout;   // [3*n_bsdfs] offsets into g_tex, -1 = constant
 
