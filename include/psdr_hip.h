@@ -257,11 +257,11 @@ typedef struct psdr_counters {
  *      created non-blocking (torch's pool streams) do not synchronise.
  *   2. The caller's duty: every device input of the call is ready ON THE STREAM THAT IS PASSED (written by work queued on it earlier, or complete before the call),
  *      and the outputs are read on that stream or after it has been waited for.
- *   3. Every psdr_hip_*_create (scene, guiding_build, precond, denoise, vdenoise, subdiv) returns with the handle usable on ANY stream and with the caller's host and
+ *   3. Every psdr_hip_*_create (scene, guiding_build, precond, denoise, vdenoise, subdiv, msloss) returns with the handle usable on ANY stream and with the caller's host and
  *      device arrays free again: it synchronises `stream` (the scene calls: the NULL stream they work on) before it returns.  They are cold paths.
  *   4. What the library serialises: calls on ONE SCENE from different streams (above).  psdr_hip_scene_update waits on the host for the scene's last call before it
  *      rewrites anything, works on the NULL stream and synchronises it before it returns: a render queued before it sees the old state, one issued after it the new.
- *   5. What it does not: a denoise / vdenoise / precond handle owns work frames, so calls on one such handle must follow each other on one stream or be ordered
+ *   5. What it does not: a denoise / vdenoise / precond / msloss handle owns work frames, so calls on one such handle must follow each other on one stream or be ordered
  *      by the caller; subdiv handles are read-only after the create and may be applied from any number of streams.
  * "No call synchronises the device" (above) means hipDeviceSynchronize; the calls that wait for their own stream say so: the creates, psdr_hip_guiding_build,
  * psdr_hip_precond_solve (it reads its residuals), the *_counted renders, and a render that has to grow the scene's scratch (first call, or a larger one). */
@@ -683,6 +683,38 @@ int psdr_hip_subdiv_apply(const psdr_hip_subdiv *s, const float *x, int32_t C, f
 /* d_x[n_in, C] = S^T d_y, d_y [n_out, C] */
 int psdr_hip_subdiv_apply_adj(const psdr_hip_subdiv *s, const float *d_y, int32_t C, float *d_x, void *stream);
 int psdr_hip_subdiv_destroy(psdr_hip_subdiv *s);
+
+/* MULTI-SCALE IMAGE LOSS, VALUE AND GRADIENT IN ONE FUSED PASS (csrc/hip/msloss.hip; psdr_jit_amd/msloss.py).  A sum of per-level losses over an
+ * image pyramid of the weighted residual: the coarse levels carry a silhouette's error across the frame where a per-pixel loss has no signal.  Device pointers in eval and
+ * level, plain launches on `stream` (three with a gradient, two without), no host synchronisation, no copy to the host, no atomics: the same input gives the same bits.
+ * Added under ABI 16 like the subdiv entry points: nothing existing changed.
+ *
+ * The definition.  Frame W x H, pixel (x, y) at row y W + x.  img, target: float32 [W H, C], C in [1, 4].  weight: absent (weight_channels = 0: 1 everywhere), [W H]
+ * (weight_channels = 1) or [W H, C] (weight_channels = C); it gets no gradient.
+ *     level 0:      d_0 = weight (img - target)
+ *     level l + 1:  W_{l+1} x H_{l+1} = ceil(W_l / 2) x ceil(H_l / 2);  d_{l+1}(i, j) = the mean of those of d_l(2i .. 2i + 1, 2j .. 2j + 1) that exist: 4 pixels, 2 at an odd
+ *                   edge, 1 at an odd corner (the divisors are powers of two; in float32 ((a + b) + (c + d)) / count with missing pixels as 0)
+ *     levels:       L of them, l = 0 .. L - 1; the full depth ends at the 1 x 1 level, L_full = 1 + ceil(log2(max(W, H)))
+ *     level_loss_l = sum rho(d_l) / (C W_l H_l),   rho(x) = |x| with rho'(0) = 0 (PSDR_MSLOSS_L1) or x^2 (PSDR_MSLOSS_L2)
+ *     loss         = sum_l lambda_l level_loss_l,  lambda = level_weights (a HOST array of L floats, read during the call; NULL: all 1)
+ *     dloss / dimg = weight G_0,   G_l = (lambda_l / (C W_l H_l)) rho'(d_l) + G_{l+1}(parent) / (the number of the parent's children),   G_L = 0
+ *     dloss / dtarget is its negative (the caller negates).
+ * create(W, H, levels, C) owns the work frames: the residual pyramid (every d_l), per-tile partial sums and the coarse part of the gradient.  It is refused with
+ * psdr_hip_last_error text BEFORE any device call unless: out is not NULL; 1 <= W, H <= 16384 and W H <= 2^24; C in [1, 4]; levels in [1, L_full].
+ * eval writes out[0] = loss and out[1 .. L] = level_loss_l (device, L + 1 floats) and, if grad is not NULL, dloss / dimg [W H, C].  It is refused before any launch for a
+ * NULL handle, img, target or out, an unknown norm, a weight_channels not in {0, 1, C}, a NULL weight with weight_channels != 0, a level weight that is not finite, and a
+ * grad that is one of the other arrays.  grad = NULL gives the same loss bits.
+ * level(l) copies d_l of the handle's last eval, [W_l H_l, C], to `out` (device) on `stream`; refused for a NULL argument, l outside [0, L) and a handle never evaluated.
+ * The sums: a level's sum of rho is added per 32 x 32 tile (a lane's own elements, the wave, the workgroup's four waves, always in the same order), then over the tiles by
+ * one workgroup in a fixed order; levels above 5 are reduced by that one workgroup. */
+#define PSDR_MSLOSS_L1 0
+#define PSDR_MSLOSS_L2 1
+typedef struct psdr_hip_msloss psdr_hip_msloss;
+int psdr_hip_msloss_create(int32_t W, int32_t H, int32_t levels, int32_t C, psdr_hip_msloss **out, void *stream);
+int psdr_hip_msloss_eval(psdr_hip_msloss *m, const float *img, const float *target, const float *weight, int32_t weight_channels, int32_t norm,
+                         const float *level_weights, float *out, float *grad, void *stream);
+int psdr_hip_msloss_level(psdr_hip_msloss *m, int32_t level, float *out, void *stream);
+int psdr_hip_msloss_destroy(psdr_hip_msloss *m);
 
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);

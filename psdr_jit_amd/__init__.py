@@ -1469,3 +1469,5 @@ from .denoise import Denoiser, first_hit_guides  # noqa: E402,F401
 from .vdenoise import VarianceDenoiser, luminance_variance  # noqa: E402,F401
 # Loop / midpoint mesh subdivision as a differentiable operator on per-vertex arrays, and its transpose (subdiv.py; kernels: csrc/hip/subdiv.hip)
 from .subdiv import Subdivision, subdivision_level  # noqa: E402,F401
+# the multi-scale (image pyramid) loss, value and gradient in one fused pass (msloss.py; kernels: csrc/hip/msloss.hip)
+from .msloss import MultiScaleLoss, pyramid_shapes  # noqa: E402,F401
