@@ -295,6 +295,9 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
     }
     Counters *ctr = (Counters *) sc->counters.p;
     if (COUNT) HIPCHK(hipMemsetAsync(ctr, 0, sizeof(Counters), st));
+#if PSDR_DIAG == 13
+    if (!COUNT) HIPCHK(hipMemsetAsync(ctr, 0, sizeof(Counters), st));
+#endif
     const SensorDev &cam = sc->sensors[a->sensor_id];
     const int terms = s.terms, cls = s.cls;
 
@@ -327,6 +330,10 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
         PathParams P = sampler_params<PathParams>(a, s, 0, npx * T.spp, a->pix_ids ? (long long) T.spp : (long long) T.width * T.spp);
         P.pix_ids = a->pix_ids;
         P.out = out; P.dout = dout; P.lanes_out = lanes_out; P.sq = sq; P.dsq = dsq;
+        // the wave's start threshold (paths.h GROUPED STARTS; the kernel itself keeps 1 on the routes that trace the camera ray)
+        // (PSDR_GROUP_START: measurement / test knob, read per call - 0 = lane by lane, the schedule before the threshold; n = that threshold for both kernels)
+        P.group_start = ad ? kGroupStartAD : kGroupStartC;
+        if (const char *e = std::getenv("PSDR_GROUP_START")) P.group_start = std::max(1, std::min(64, std::atoi(e)));
         if (lanes_out) { P.begin = lane_b; P.end = lane_e; P.shard_rank = 0; P.shard_count = 1; P.n_local = local_lanes(P.end - P.begin, 0, 1); }
         if (P.n_local > 0) {
             if (fork) P.counter = q_int; else if (next_queue(sc, st, P.counter)) return 1;
@@ -335,6 +342,14 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
             if (ad) LAUNCH_CLS_FWD(cls, K_INTERIOR_AD); else LAUNCH_CLS_FWD(cls, K_INTERIOR_C);
 #undef K_INTERIOR_AD
 #undef K_INTERIOR_C
+#if PSDR_DIAG == 13
+            if (!COUNT) {      // the census of paths.h: one line per interior launch (development builds; the call waits for the kernel)
+                Counters h;
+                HIPCHK(hipMemcpyAsync(&h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                std::fprintf(stderr, "psdr census: ad %d G %d depth %d starts %llu started %llu bodies %llu busy %llu\n", (int) ad, P.group_start, P.max_depth, h.rays, h.nodes, h.tris, h.hits);
+            }
+#endif
         }
     }
     if (ad && (!a->pix_ids || batch_edges) && !lanes_out) {

@@ -16,6 +16,7 @@
 //         one edge sample = two consecutive paths (ray_n then ray_p) sharing the lane's RNG stream.
 #pragma once
 #include "edges.h"
+#include "group_start.h"
 
 namespace psdr {
 
@@ -51,6 +52,9 @@ struct PathParams {
     // per-pixel sums of squared sample contributions (psdr_hip_render_c_sq / _d_fwd_sq; NULL = none): whatever a sample adds to out / dout, its square is added here at the
     // same slot.  Last in the struct: the fields above keep their kernel-argument offsets
     float *sq, *dsq;
+    // interior term (MODE 0 of run_paths): a wave starts new samples once this many of its lanes are idle (GROUPED STARTS below; api.hip fills it per call, 1 = lane by
+    // lane).  The other kernels do not read it.  Appended last for the same reason
+    int group_start;
 };
 
 // KERNEL VARIANTS (the last template parameter of k_paths / run_paths / run_paths_async).  A launch is one kind of call - forward or reverse mode, PathTracer or a
@@ -83,23 +87,42 @@ template <int VAR> PSDR_DEV bool edge_sample_idle(const PathParams &P, int ei, f
 #endif
 constexpr int kFetchBatch = PSDR_FETCH_BATCH;      // work items a wave takes from the launch's queue per atomic
 static_assert(kFetchBatch % 64 == 0, "PSDR_FETCH_BATCH");
-#ifndef PSDR_REGEN_MIN
-#define PSDR_REGEN_MIN 1
+// GROUPED STARTS (interior term, MODE 0 of run_paths on the camera-table route).  Seeding a lane, finding its work item, drawing its camera ray and resolving it from
+// the sensor's table (the start block of run_paths) is issued for the whole wave under the mask of the lanes that start.  With a threshold of 1 the block runs in every
+// loop iteration for the lanes that have just ended a sample; with a threshold G it runs once G lanes are idle (or nobody is busy), and a start then fills EVERY idle
+// lane - across windows and across the boundary of a fetch batch (take_live_items_fill) - so the block's cost is shared by more samples, at the price of lanes that idle
+// between the end of their path and the next start.  The decision and the queue arithmetic are group_start.h's.  The threshold is a kernel argument
+// (PathParams::group_start): api.hip passes kGroupStartAD to the AD kernel and kGroupStartC to the C kernel (PSDR_GROUP_START=0 in the environment: 1, lane by lane;
+// -DPSDR_REGEN_MIN=n stages both defaults for a measurement).  The routes that keep the traced camera ray - and the primary-edge term - run with 1.
+#ifdef PSDR_REGEN_MIN
+constexpr int kGroupStartAD = PSDR_REGEN_MIN, kGroupStartC = PSDR_REGEN_MIN;
+#else
+// (C3 on one MI355X, LABNOTES: AD kernel 1.314 ms lane by lane, 1.261 / 1.250 / 1.285 / 1.350 / 1.352 at 2 / 16 / 32 / 48 / 64; C kernel 1.014 -> 0.981 at 16, 1.013 at 64)
+constexpr int kGroupStartAD = 16, kGroupStartC = 16;
 #endif
-constexpr int kRegenMin = PSDR_REGEN_MIN;
+constexpr int kRegenMinEdge = 1;                   // MODE 1: compile-time, the field is not read
 
 // position of the r-th (0-based) set bit of m; r < popcount(m)
-PSDR_DEV int nth_set_bit(unsigned long long m, int r) {
-    unsigned w = (unsigned) m;
-    int pos = 0;
-    const int c0 = __popc(w);
-    if (r >= c0) { r -= c0; w = (unsigned) (m >> 32); pos = 32; }
-#pragma unroll
-    for (int half = 16; half >= 1; half >>= 1) {
-        const int cl = __popc(w & ((1u << half) - 1u));
-        if (r >= cl) { r -= cl; w >>= half; pos += half; }
-    }
-    return pos;
+PSDR_DEV int nth_set_bit(unsigned long long m, int r) { return gs_nth_set_bit(m, r); }
+
+// takes the next kFetchBatch positions of the launch's queue for this wave (one atomic, lane 0), or finds the queue exhausted
+template <typename Params>
+PSDR_DEV void fetch_batch(const Params &P, int lane_id, long long &q_next, long long &q_end, bool &exhausted) {
+    unsigned long long base = 0;
+    if (lane_id == 0) base = atomicAdd(P.counter, (unsigned long long) kFetchBatch);
+    base = __shfl(base, 0);
+    gs_fetched(base, P.n_local, kFetchBatch, q_next, q_end, exhausted);
+}
+
+// is queue position `it` a sample of a live pixel?  (take_live_items below)
+template <typename Params>
+PSDR_DEV bool live_position(const SceneTables &T, const SensorDev &cam, const Params &P, long long it) {
+    const long long chunk = (it >> 8) * P.shard_count + P.shard_rank;
+    const long long lane = P.begin + (chunk << 8) + (it & 255);
+    if (lane >= P.end) return false;
+    const unsigned k = T.spp > 1 ? (unsigned) lane / (unsigned) T.spp : (unsigned) lane;      // (fewer than 2^31 lanes: the callers check P.end)
+    const int pix = P.pix_ids ? P.pix_ids[k] : (int) k;
+    return (unsigned) pix >= (unsigned) (T.width * T.height) || ((cam.live[pix >> 5] >> (pix & 31)) & 1u) != 0u;      // (a pixel id outside the frame - batch rendering - is left to the path code)
 }
 
 // LIVE PIXELS ONLY (round 4).  64 % of the README frame is background: a sample there is seeded, its camera ray traced, and nothing comes of it.  Pixels no ray
@@ -115,24 +138,38 @@ PSDR_DEV long long take_live_items(const SceneTables &T, const SensorDev &cam, c
         const unsigned long long want = __ballot(wants && item >= q_end);
         const long long w0 = q_next + n_taken;
         if (want == 0ull || w0 >= q_end) break;
-        const int wlen = q_end - w0 < 64 ? (int) (q_end - w0) : 64;
-        bool live = false;
-        if (lane_id < wlen) {
-            const long long it = w0 + lane_id;
-            const long long chunk = (it >> 8) * P.shard_count + P.shard_rank;
-            const long long lane = P.begin + (chunk << 8) + (it & 255);
-            if (lane < P.end) {
-                const unsigned k = T.spp > 1 ? (unsigned) lane / (unsigned) T.spp : (unsigned) lane;      // (fewer than 2^31 lanes: the callers check P.end)
-                const int pix = P.pix_ids ? P.pix_ids[k] : (int) k;
-                live = (unsigned) pix >= (unsigned) (T.width * T.height) || ((cam.live[pix >> 5] >> (pix & 31)) & 1u) != 0u;      // (a pixel id outside the frame - batch rendering - is left to the path code)
-            }
-        }
-        const unsigned long long lv = __ballot(live);
+        const int wlen = gs_window_len(w0, q_end);
+        const unsigned long long lv = __ballot(lane_id < wlen && live_position(T, cam, P, w0 + lane_id));
         const int n_live = __popcll(lv), n_want = __popcll(want);
-        if (wants && item >= q_end) { const int r = __popcll(want & lt_mask); if (r < n_live) item = w0 + nth_set_bit(lv, r); }
+        if (wants && item >= q_end) { const int p = gs_lane_pick(lv, want, lt_mask); if (p >= 0) item = w0 + p; }
         // the window is used up to its last taken position (all of it when every live position found a lane)
-        n_taken += n_live <= n_want ? wlen : nth_set_bit(lv, n_want - 1) + 1;
+        n_taken += gs_window_used(lv, n_want, wlen);
         if (n_live >= n_want) break;
+    }
+    return item;
+}
+
+// The same hand-out on the wave's queue itself (run_paths).  fill = false: as above, at most three windows of the batch in hand.  fill = true, a GROUPED start: it
+// goes on - window after window, and past the end of the wave's batch with a new fetch in between - until every lane that wants a work item has one or the launch's
+// queue is exhausted.  Either way the positions are handed out in the same order (a window's live positions to the idle lanes in lane order, the queue's head moved to
+// the last taken one), so which lane gets which item depends on the queue and the idle mask alone.  Every round uses up at least one position of a finite queue or
+// ends the loop.  -> this lane's item (-1: none); q_next, q_end, exhausted are the wave's queue, updated
+template <typename Params>
+PSDR_DEV long long take_live_items_fill(const SceneTables &T, const SensorDev &cam, const Params &P, bool wants, bool fill, long long &q_next, long long &q_end,
+                                        bool &exhausted, int lane_id, unsigned long long lt_mask) {
+    long long item = -1;
+#pragma nounroll
+    for (int win = 0; fill || win < 3; ++win) {
+        const unsigned long long want = __ballot(wants && item < 0);
+        if (want == 0ull) break;
+        if (q_next >= q_end) {
+            if (fill && !exhausted) fetch_batch(P, lane_id, q_next, q_end, exhausted);
+            if (q_next >= q_end) break;
+        }
+        const int wlen = gs_window_len(q_next, q_end);
+        const unsigned long long lv = __ballot(lane_id < wlen && live_position(T, cam, P, q_next + lane_id));
+        if (wants && item < 0) { const int p = gs_lane_pick(lv, want, lt_mask); if (p >= 0) item = q_next + p; }
+        q_next += gs_window_used(lv, __popcll(want), wlen);
     }
     return item;
 }
@@ -177,6 +214,10 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
     // camera rays already share one trace2 pass, and resolving both from the table while regenerating cost more than the iteration it saved (LABNOTES).
     constexpr bool kCamTab = in_lds(LDS) && !COUNT && MODE == 0;
     const bool use_tab = kCamTab && cam.cam_tab != nullptr && P.max_depth > 0 && sw::lanes_out(P) == nullptr && sw::field(S) < 0 && !sw::ortho(cam);
+    // GROUPED STARTS (above): the start threshold of this wave.  Above 1 on the table route with the live-pixel hand-out only; a wave that meets a pixel id outside the
+    // frame - that lane's camera ray is traced - goes on lane by lane
+    int G = kRegenMinEdge;
+    if constexpr (MODE == 0) { if (use_tab && cam.live != nullptr && P.end < (1ll << 31)) G = P.group_start < 1 ? 1 : (P.group_start > 64 ? 64 : P.group_start); }
 
 #if PSDR_DIAG == 6
     // phase timers (wave cycles, every lane adds the same delta): c_rays = fetch + regeneration, c_nodes = drawing the vertex's
@@ -185,6 +226,13 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
 #define PSDR_PHASE(field) do { if (COUNT) { const unsigned long long t_now = __builtin_readcyclecounter(); S.field += (unsigned) (t_now - t_ph); t_ph = t_now; } } while (0)
 #else
 #define PSDR_PHASE(field) do { } while (0)
+#endif
+#if PSDR_DIAG == 13
+    // census of the interior term's schedule (uncounted kernels; api.hip prints the sums per launch): c_rays = start blocks issued (per wave), c_nodes = samples started,
+    // c_tris = loop bodies issued (per wave), c_hits = busy lanes over those bodies
+#define PSDR_CENSUS(stmt) do { if (MODE == 0 && !COUNT) { stmt; } } while (0)
+#else
+#define PSDR_CENSUS(stmt) do { } while (0)
 #endif
     for (;;) {
         // MODE 1: the camera ray of an edge sample's SECOND path rides in the first path's first trace (whose next-event slot is idle: no vertex yet); its hit waits in
@@ -203,15 +251,23 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
         // regenerate only when enough lanes are idle: seeding a lane (two 64-bit TEA hashes + pcg32 seed, ~600
         // instructions) runs under the mask of the fetching lanes, so doing it every iteration for a handful of
         // lanes costs as much as doing it for a quarter of the wave
-        if (need != 0ull && q_next < q_end && (__popcll(need) >= kRegenMin || __ballot(busy) == 0ull)) {
+        // (the primary-edge term keeps its compile-time form: its kernels are the code they were before the interior term's threshold)
+        bool start_now;
+        if constexpr (MODE == 0) start_now = gs_start_now(__popcll(need), __popcll(__ballot(busy)), G, q_next < q_end);
+        else start_now = need != 0ull && q_next < q_end && (__popcll(need) >= kRegenMinEdge || __ballot(busy) == 0ull);
+        if (start_now) {
             const int n_need = __popcll(need);
+            PSDR_CENSUS(if (lane_id == 0) S.c_rays++);
             long long item = q_end;                       // the work item this lane starts (q_end: none)
             int n_taken;                                  // queue positions consumed
             bool tab_on = false;                          // this lane's camera ray is resolved from the table: tab_m lists its candidate slots
             unsigned long long tab_m = 0ull;
             if (MODE == 0 && !COUNT && cam.live != nullptr && sw::lanes_out(P) == nullptr && P.end < (1ll << 31)) {      // (the counted builds and the per-lane output see every sample)
-                // LIVE PIXELS ONLY (round 4): take_live_items above
-                item = take_live_items(T, cam, P, !busy, q_next, q_end, lane_id, lt_mask, n_taken);
+                // LIVE PIXELS ONLY (round 4): take_live_items above, on the wave's queue itself (which it moves: n_taken = 0); a grouped start fills every idle lane.
+                // A start may end in a later batch than it began in: the launch's queue only grows, so a position taken from an earlier batch lies below q_end too
+                item = take_live_items_fill(T, cam, P, !busy, G > 1, q_next, q_end, exhausted, lane_id, lt_mask);
+                n_taken = 0;
+                if (item < 0) item = q_end;
             } else {
                 item = q_next + __popcll(need & lt_mask);
                 n_taken = n_need < (int) (q_end - q_next) ? n_need : (int) (q_end - q_next);
@@ -221,6 +277,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                 const long long lane = P.begin + (chunk << 8) + (item & 255);
                 if (lane < P.end) {
                     busy = true; depth = -1; thr = V(R(1.f)); res = V(R(0.f));
+                    PSDR_CENSUS(S.c_nodes++);
                     if (MODE == 0) {
                         const long long k = T.spp > 1 ? lane / T.spp : lane;
                         const int pix = P.pix_ids ? P.pix_ids[k] : (int) k;
@@ -278,10 +335,12 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                         }
                     }
                 }
+                if (G > 1 && __ballot(busy && depth < 0) != 0ull) G = 1;      // (a started lane still at its camera ray: a pixel id outside the frame)
             }
         }
         PSDR_PHASE(c_rays);
         if (__ballot(busy) == 0ull) { if (exhausted && q_next >= q_end) break; continue; }
+        PSDR_CENSUS(if (lane_id == 0) S.c_tris++; if (busy) S.c_hits++);
 
         // ------------------------------------------------------------------ [A] next-event estimation (path.cpp:47-83)
         const bool at_vertex = busy && depth >= 0;
@@ -490,6 +549,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
         PSDR_PHASE(c_hits);
     }
 #undef PSDR_PHASE
+#undef PSDR_CENSUS
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

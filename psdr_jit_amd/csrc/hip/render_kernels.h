@@ -116,6 +116,9 @@ __global__ __launch_bounds__(kBlock, (AD ? (in_lds(LDS) ? PSDR_LDS_AD_WAVES : (L
         run_paths_any<AD, LDS, COUNT, MODE, VAR>(S, cam, P);
     }
     if (COUNT) flush_counters(S, ctr);
+#if PSDR_DIAG == 13
+    if (!COUNT && MODE == 0) flush_counters(S, ctr);      // (the census of paths.h)
+#endif
 }
 
 // reverse mode of the interior term (adjoint.h)
