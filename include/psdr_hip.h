@@ -257,11 +257,11 @@ typedef struct psdr_counters {
  *      created non-blocking (torch's pool streams) do not synchronise.
  *   2. The caller's duty: every device input of the call is ready ON THE STREAM THAT IS PASSED (written by work queued on it earlier, or complete before the call),
  *      and the outputs are read on that stream or after it has been waited for.
- *   3. Every psdr_hip_*_create (scene, guiding_build, precond, denoise, vdenoise, subdiv, msloss) returns with the handle usable on ANY stream and with the caller's host and
+ *   3. Every psdr_hip_*_create (scene, guiding_build, precond, denoise, vdenoise, subdiv, msloss, ssim) returns with the handle usable on ANY stream and with the caller's host and
  *      device arrays free again: it synchronises `stream` (the scene calls: the NULL stream they work on) before it returns.  They are cold paths.
  *   4. What the library serialises: calls on ONE SCENE from different streams (above).  psdr_hip_scene_update waits on the host for the scene's last call before it
  *      rewrites anything, works on the NULL stream and synchronises it before it returns: a render queued before it sees the old state, one issued after it the new.
- *   5. What it does not: a denoise / vdenoise / precond / msloss handle owns work frames, so calls on one such handle must follow each other on one stream or be ordered
+ *   5. What it does not: a denoise / vdenoise / precond / msloss handle owns work frames and so does an ssim handle, so calls on one such handle must follow each other on one stream or be ordered
  *      by the caller; subdiv handles are read-only after the create and may be applied from any number of streams.
  * "No call synchronises the device" (above) means hipDeviceSynchronize; the calls that wait for their own stream say so: the creates, psdr_hip_guiding_build,
  * psdr_hip_precond_solve (it reads its residuals), the *_counted renders, and a render that has to grow the scene's scratch (first call, or a larger one). */
@@ -715,6 +715,40 @@ int psdr_hip_msloss_eval(psdr_hip_msloss *m, const float *img, const float *targ
                          const float *level_weights, float *out, float *grad, void *stream);
 int psdr_hip_msloss_level(psdr_hip_msloss *m, int32_t level, float *out, void *stream);
 int psdr_hip_msloss_destroy(psdr_hip_msloss *m);
+
+/* THE SSIM LOSS, 1 - MEAN STRUCTURAL SIMILARITY, VALUE AND IMAGE GRADIENT IN ONE FUSED PASS (csrc/hip/ssim.hip; psdr_jit_amd/ssim.py).  A norm of pixel
+ * differences cannot tell structure from brightness; SSIM compares local means, variances and the covariance under a Gaussian window.  Device pointers in eval and map, plain
+ * launches on `stream` (three with a gradient, two without), no host synchronisation, no copy to the host, no atomics: the same input gives the same bits.  Added under ABI 16
+ * like the msloss entry points: nothing existing changed.
+ *
+ * The definition.  Frame W x H, pixel (x, y) at row y W + x.  img = x, target = y: float32 [W H, C], C in [1, 4].  mask = m: NULL (1 everywhere) or [W H], finite and
+ * non-negative.  Neither target nor mask gets a gradient.
+ *     window:   K odd in [3, 11], R = K / 2, taps g_0 .. g_{K-1}: a HOST array read by create.  The float32 taps ARE the definition (psdr.gaussian_window(K, sigma):
+ *               exp(-(k - R)^2 / (2 sigma^2)) normalised in double, rounded once); they travel to the kernels as arguments.
+ *     G v     = the vertical pass of the horizontal pass of v, each pass sum_k g_k v(. + k - R), in any summation order; pixels outside the frame count as 0 and the
+ *               window is not renormalised (F.conv2d(padding = R))
+ *     mu_x = G x, mu_y = G y, E_xx = G(x x), E_yy = G(y y), E_xy = G(x y);   s_xx = E_xx - mu_x mu_x, s_yy = E_yy - mu_y mu_y, s_xy = E_xy - mu_x mu_y
+ *     a1 = 2 (mu_x mu_y) + c1,  a2 = 2 s_xy + c2,  b1 = (mu_x mu_x + mu_y mu_y) + c1,  b2 = (s_xx + s_yy) + c2;   c1 = (k1 range)^2, c2 = (k2 range)^2 as float32
+ *     S = (a1 a2) / (b1 b2): one product each, one division; img == target gives S == 1 exactly
+ *     m_eff   = m (PSDR_SSIM_SAME), or m times the indicator of R <= x < W - R and R <= y < H - R (PSDR_SSIM_VALID: the mean over windows that lie wholly inside)
+ *     N = C sum_p m_eff(p);  mean = (sum_{p,c} m_eff(p) S(p, c)) / N;  out[0] = loss = 1 - mean, out[1] = mean;  N == 0: out = (0, 0) and the gradient is 0
+ *     P = m_eff [2 mu_y (a2 - a1) - 2 mu_x S (b2 - b1)] / (b1 b2),   Q = -m_eff S / b2,   T = m_eff 2 a1 / (b1 b2)
+ *     dloss / dimg = -(G P + 2 x G Q + y G T) / N with the same zero-padded G: the window is symmetric, so the gradient is a gather
+ * create(W, H, C, window, taps, c1, c2, padding) owns S, P, Q, T ([W H, C] each), the tiles' partial sums and the scale -1 / N.  It is refused with psdr_hip_last_error
+ * text BEFORE any device call unless: out and taps are not NULL; 1 <= W, H <= 16384 and W H <= 2^24; C in [1, 4]; window odd in [3, 11]; every tap finite and their sum 1
+ * within 1e-5; c1, c2 finite and positive; padding one of the two; W, H >= window under PSDR_SSIM_VALID.
+ * eval writes out[0 .. 1] (device) and, if grad is not NULL, dloss / dimg [W H, C].  It is refused before any launch for a NULL handle, img, target or out and a grad that
+ * is img or target.  grad = NULL gives the same out bits.
+ * map copies the unmasked S of the handle's last eval, [W H, C], to `out` (device) on `stream`; refused for a NULL argument and a handle never evaluated.
+ * The sums: m_eff S and m_eff are added per 32 x 16 tile (a lane's own elements, the wave, the workgroup's four waves, always in the same order), then over the tiles by
+ * one workgroup in a fixed order. */
+#define PSDR_SSIM_SAME 0
+#define PSDR_SSIM_VALID 1
+typedef struct psdr_hip_ssim psdr_hip_ssim;
+int psdr_hip_ssim_create(int32_t W, int32_t H, int32_t C, int32_t window, const float *taps, float c1, float c2, int32_t padding, psdr_hip_ssim **out, void *stream);
+int psdr_hip_ssim_eval(psdr_hip_ssim *s, const float *img, const float *target, const float *mask, float *out, float *grad, void *stream);
+int psdr_hip_ssim_map(psdr_hip_ssim *s, float *out, void *stream);
+int psdr_hip_ssim_destroy(psdr_hip_ssim *s);
 
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);

@@ -1471,3 +1471,6 @@ from .vdenoise import VarianceDenoiser, luminance_variance  # noqa: E402,F401
 from .subdiv import Subdivision, subdivision_level  # noqa: E402,F401
 # the multi-scale (image pyramid) loss, value and gradient in one fused pass (msloss.py; kernels: csrc/hip/msloss.hip)
 from .msloss import MultiScaleLoss, pyramid_shapes  # noqa: E402,F401
+
+# the SSIM loss 1 - mean structural similarity, value and image gradient in one fused pass (ssim.py; kernels: csrc/hip/ssim.hip)
+from .ssim import SSIMLoss, gaussian_window  # noqa: E402,F401

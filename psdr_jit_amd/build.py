@@ -40,6 +40,7 @@ OPERATOR_UNITS = [
     ("vdenoise", "vdenoise.hip", "psdr_hip_vdenoise_*: the variance-guided a-trous denoiser, its recorded (frozen) operator and that operator's transpose", ("atrous.h",)),
     ("subdiv", "subdiv.hip", "psdr_hip_subdiv_*: one level of Loop / midpoint subdivision as a sparse operator (CSR from the host) and its transpose", ()),
     ("msloss", "msloss.hip", "psdr_hip_msloss_*: the multi-scale image loss over a residual pyramid, value and gradient in three launches", ()),
+    ("ssim", "ssim.hip", "psdr_hip_ssim_*: the SSIM loss 1 - mean structural similarity under a Gaussian window, value and image gradient in three launches", ()),
 ]
 OPERATOR_TUS = [(name, _H(src)[0], [], [os.path.join(ROOT, "include", "psdr_hip.h")] + _H(*headers) + BUILD_DEPS) for name, src, _what, headers in OPERATOR_UNITS]      # hip_units()'s tuples
 HIP_SRCS = [API_SRC, UNITS_SRC, SCENE_SRC] + [u[1] for u in OPERATOR_TUS]

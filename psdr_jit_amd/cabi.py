@@ -17,6 +17,7 @@ SYMBOLS = [
     "psdr_hip_vdenoise_create", "psdr_hip_vdenoise_apply", "psdr_hip_vdenoise_frozen", "psdr_hip_vdenoise_frozen_adj", "psdr_hip_vdenoise_record", "psdr_hip_vdenoise_destroy",
     "psdr_hip_subdiv_create", "psdr_hip_subdiv_apply", "psdr_hip_subdiv_apply_adj", "psdr_hip_subdiv_destroy",
     "psdr_hip_msloss_create", "psdr_hip_msloss_eval", "psdr_hip_msloss_level", "psdr_hip_msloss_destroy",
+    "psdr_hip_ssim_create", "psdr_hip_ssim_eval", "psdr_hip_ssim_map", "psdr_hip_ssim_destroy",
 ]
 
 
@@ -116,6 +117,10 @@ def lib():
         L.psdr_hip_msloss_eval.argtypes = [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
         L.psdr_hip_msloss_level.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.psdr_hip_msloss_destroy.argtypes = [C.c_void_p]
+        L.psdr_hip_ssim_create.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p]
+        L.psdr_hip_ssim_eval.argtypes = [C.c_void_p] * 7
+        L.psdr_hip_ssim_map.argtypes = [C.c_void_p] * 3
+        L.psdr_hip_ssim_destroy.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
