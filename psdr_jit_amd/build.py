@@ -29,7 +29,7 @@ _H = lambda *names: [os.path.join(CSRC, "hip", f) for f in names]
 # every quoted #include a unit's source reaches is in that unit's list (tests/test_build_deps.py walks the include graph)
 DEVICE_DEPS = _H("scene_dev.h", "dmath.h", "trav4.h")
 COMMON_DEPS = DEVICE_DEPS + _H("scene_obj.h") + [os.path.join(ROOT, "include", "psdr_hip.h"), os.path.join(CSRC, "common", "threads.h")]
-KERNEL_DEPS = DEVICE_DEPS + _H("render_kernels.h", "sampler.h", "shade.h", "edges.h", "paths.h", "group_start.h", "adj_layout.h", "adjoint.h", "adjoint_mat.h", "isect_ad.h", "microfacet.h") + [os.path.join(CSRC, "common", "envmath.h")] + BUILD_DEPS
+KERNEL_DEPS = DEVICE_DEPS + _H("render_kernels.h", "sampler.h", "shade.h", "edges.h", "paths.h", "group_start.h", "edge_switch.h", "adj_layout.h", "adjoint.h", "adjoint_mat.h", "isect_ad.h", "microfacet.h") + [os.path.join(CSRC, "common", "envmath.h")] + BUILD_DEPS
 API_DEPS = sorted(set(COMMON_DEPS + KERNEL_DEPS))      # the host unit launches the heavy kernels: it sees their header, they do not see api.hip
 SCENE_DEPS = COMMON_DEPS + _H("bvh.h", "filter.h", "cam_table.h", "blob_rows.h", "blob_layout.h") + [os.path.join(CSRC, "host", "hnum.h"), os.path.join(CSRC, "host", "edge_select.h")] + BUILD_DEPS
 # the stand-alone operators, one source file each: (unit, source, what it holds, the headers of csrc/hip it includes beside include/psdr_hip.h); compiled in this order

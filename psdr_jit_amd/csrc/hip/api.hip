@@ -295,7 +295,7 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
     }
     Counters *ctr = (Counters *) sc->counters.p;
     if (COUNT) HIPCHK(hipMemsetAsync(ctr, 0, sizeof(Counters), st));
-#if PSDR_DIAG == 13
+#if PSDR_DIAG == 13 || PSDR_DIAG == 14
     if (!COUNT) HIPCHK(hipMemsetAsync(ctr, 0, sizeof(Counters), st));
 #endif
     const SensorDev &cam = sc->sensors[a->sensor_id];
@@ -371,6 +371,14 @@ static int render_impl(const psdr_hip_scene *sc, const psdr_render_args *a, bool
 #define K_PRIMARY(C) LAUNCH_PATHS(C, false, COUNT, 1, lean, sc, P.n_local, s_prim, sc->blob.as<float4>(), T_prim, cam, P, ctr)
                 LAUNCH_CLS_FWD(cls, K_PRIMARY);
 #undef K_PRIMARY
+#if PSDR_DIAG == 14
+                if (!COUNT) {      // the census of the side switch (paths.h): one line per primary-edge launch (development builds; the call waits for the kernel)
+                    Counters h;
+                    HIPCHK(hipMemcpyAsync(&h, ctr, sizeof(h), hipMemcpyDeviceToHost, s_prim));
+                    HIPCHK(hipStreamSynchronize(s_prim));
+                    std::fprintf(stderr, "psdr census: edge samples %llu early %llu detour %llu bodies %llu depth %d\n", h.rays, h.nodes, h.hits, h.tris, P.max_depth);
+                }
+#endif
             }
         }
         if (want_sec) {

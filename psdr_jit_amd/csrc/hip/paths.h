@@ -16,6 +16,7 @@
 //         one edge sample = two consecutive paths (ray_n then ray_p) sharing the lane's RNG stream.
 #pragma once
 #include "edges.h"
+#include "edge_switch.h"
 #include "group_start.h"
 
 namespace psdr {
@@ -206,6 +207,19 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
     auto park_i = [&](int r, int v) { cold[r * kBlock] = __int_as_float(v); };
     static_assert(kColdRows >= 15, "scene_dev.h::kColdRows");
     static_assert(MODE == 0 || !AD, "the primary-edge paths are traced in C mode");
+    // MODE 1: the origin of the second path's camera ray ray_p = sample_primary_ray(p + EdgeEpsilon * n) - the sensor's position for a perspective camera, the same for
+    // every sample; for an orthographic one the near-plane point, by the same arithmetic as at the start of the work item (from the edge sample in the cold rows)
+    auto second_path_origin = [&]() -> Vec3f {
+        if (sw::ortho(cam)) {
+            const int edge_i = cold_i(kEdgeI);
+            const float edge_s = cold_f(kEdgeS), edge_nx = cold_f(kNx), edge_ny = cold_f(kNy);
+            const float4 r0 = S.ld(cam.pe_off + 3 * edge_i);
+            const float oms = 1.0f - edge_s;
+            const float pxv = fmaf(r0.x, oms, r0.z * edge_s), pyv = fmaf(r0.y, oms, r0.w * edge_s);
+            return sample_primary_ray<false, !sw::lean>(cam, pxv + kEdgeEpsilon * edge_nx, pyv + kEdgeEpsilon * edge_ny).o;
+        }
+        return primary_ray_origin(cam);
+    };
     // CAMERA RAYS FROM THE SENSOR'S TRIANGLE TABLE (interior term).  Which triangles a camera ray can hit is known per pixel (SensorDev::cam_tab): a lane that takes a
     // work item resolves its camera ray against those few triangles while it regenerates (trace_listed: the tracer's exact test and (t, id) order, without the filter
     // pass over every primitive) and enters the loop AT its first vertex, instead of spending one iteration of the whole wave on a trace2 of the camera ray: one
@@ -214,6 +228,19 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
     // camera rays already share one trace2 pass, and resolving both from the table while regenerating cost more than the iteration it saved (LABNOTES).
     constexpr bool kCamTab = in_lds(LDS) && !COUNT && MODE == 0;
     const bool use_tab = kCamTab && cam.cam_tab != nullptr && P.max_depth > 0 && sw::lanes_out(P) == nullptr && sw::field(S) < 0 && !sw::ortho(cam);
+    // THE EARLY SIDE SWITCH (primary-edge term, edge_switch.h).  An edge sample's first path has ended when its ray missed, was not traced, or found the path's last
+    // vertex - all known from the hit in hand, before its vertex is built -, and a last vertex is read for Le x thr x weight only: an exact zero off the emitters.  A lane
+    // whose first path ends like that switches sides AHEAD of the loop's make_its and hands it the parked hit of ray_p in the same iteration: the lane's slot in the one
+    // make_its builds the second path's first vertex instead of a vertex nobody reads, and the late switch's own make_its + first-hit value leave the kernel.  The lanes
+    // that do read the vertex (a last hit on an emitter; every camera hit at max_depth == 0) go through the vertex block as ever, park their radiance at the bottom and
+    // wait one iteration with `side == 2` - no rays posted -, then take the same route.  Rays, draws and per-sample arithmetic are the late switch's; the counted kernels
+    // keep the late switch (their iteration counts are what tools/phase_timers.py and the roofline read), so every library carries both schedules.
+    // (One difference, on no set of paths of measure greater than zero: a last hit off the emitters used to add 0 x thr x weight, a NaN where thr or weight is not finite -
+    //  the weight where pdf0 is zero or its square leaves the float range: cos == 0.0f exactly, or a grazing angle below some 1e-17 rad, at a valid hit; thr where a valid
+    //  BSDF sample's pdf is denormal - and that NaN sample was dropped at the accumulation; the early switch keeps the finite radiance gathered so far.  LABNOTES.)
+    // Class 1 only (the scene in LDS, Diffuse BSDFs).  On the class with materials (3) that NaN is no rare event: a rough dielectric's sample can come with a value over pdf
+    // that is not finite, the reference drops such samples, and frames of the randomised parity run were 2e-3 off with the early switch - class 3 keeps the late one.
+    constexpr bool kEarlySwitch = MODE == 1 && !COUNT && LDS == 1 && !AD;
     // GROUPED STARTS (above): the start threshold of this wave.  Above 1 on the table route with the live-pixel hand-out only; a wave that meets a pixel id outside the
     // frame - that lane's camera ray is traced - goes on lane by lane
     int G = kRegenMinEdge;
@@ -233,6 +260,13 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
 #define PSDR_CENSUS(stmt) do { if (MODE == 0 && !COUNT) { stmt; } } while (0)
 #else
 #define PSDR_CENSUS(stmt) do { } while (0)
+#endif
+#if PSDR_DIAG == 14
+    // census of the primary-edge term's side switch (uncounted kernels; api.hip prints the sums per launch): c_rays = edge samples started, c_nodes = first paths that
+    // switch early, c_tris = loop bodies issued (per wave), c_hits = first paths that take the detour (their last vertex is read)
+#define PSDR_CENSUS_EDGE(stmt) do { if (MODE == 1 && !COUNT) { stmt; } } while (0)
+#else
+#define PSDR_CENSUS_EDGE(stmt) do { } while (0)
 #endif
     for (;;) {
         // MODE 1: the camera ray of an edge sample's SECOND path rides in the first path's first trace (whose next-event slot is idle: no vertex yet); its hit waits in
@@ -317,6 +351,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                         // (the edge sample itself: read again by the reverse mode's scatter and by an orthographic sensor's second path, see the side switch below)
                         if (sw::adj_w(P) != nullptr || sw::ortho(cam)) { park_f(kEdgeS, s); park_f(kNx, nx); park_f(kNy, ny); park_i(kEdgeI, ei); }
                         if (!edge_valid) busy = false;       // Li(..., valid=false) contributes nothing
+                        PSDR_CENSUS_EDGE(if (edge_valid) S.c_rays++);
                     }
                 }
             }
@@ -341,6 +376,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
         PSDR_PHASE(c_rays);
         if (__ballot(busy) == 0ull) { if (exhausted && q_next >= q_end) break; continue; }
         PSDR_CENSUS(if (lane_id == 0) S.c_tris++; if (busy) S.c_hits++);
+        PSDR_CENSUS_EDGE(if (lane_id == 0) S.c_tris++);
 
         // ------------------------------------------------------------------ [A] next-event estimation (path.cpp:47-83)
         const bool at_vertex = busy && depth >= 0;
@@ -376,7 +412,9 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
         // an invalid BSDF sample (e.g. on the BSDF-less bounding cube of the environment map: wo = 0) ends the path whatever
         // its ray hits; a zero-direction ray would wander through every BVH node that contains its origin
         if (MODE == 1) { if (trace_p) ray1 = cam_p; }
-        trace2<LDS, COUNT>(S, detach(ray1.o), detach(ray1.d), do_nee || (MODE == 1 && trace_p), detach(ext.o), detach(ext.d), busy && bs.valid, h, hx);
+        bool trace_ext = busy && bs.valid;
+        if constexpr (kEarlySwitch) trace_ext = trace_ext && side != 2;      // (switched, waiting for the make_its below: nothing to trace)
+        trace2<LDS, COUNT>(S, detach(ray1.o), detach(ray1.d), do_nee || (MODE == 1 && trace_p), detach(ext.o), detach(ext.d), trace_ext, h, hx);
         PSDR_PHASE(c_tris);
         if (MODE == 1) { if (trace_p) { park_i(kHpSlot, h.slot); park_f(kHpU, h.u); park_f(kHpV, h.v); park_f(kHpT, h.t); } }
         {
@@ -396,6 +434,32 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                     const float pdf1 = bsdf_pdf<AD, LDS>(S, its, wo_local, true) * detach(G_val);
                     if (pdf1 != 0.f) res = res + thr * emitter_val * bsdf_val2 * R(sw::mis(P) == 0 ? 1.f : mis_weight(ps.pdf, pdf1));
                 }
+            }
+        }
+
+        if constexpr (kEarlySwitch) {
+            bool switch_now = busy && side == 2;
+            if (busy && side == 0) {
+                const bool hit = hx.slot >= 0;
+                bool hit_emitter = false;
+                if (es_last_hit(depth, P.max_depth, bs.valid, hit)) hit_emitter = mesh_emitter(S, __float_as_int(S.ld(T.shade_off + 6 * hx.slot + 1).w)) >= 0;
+                const EdgeSwitch es = es_path_end(depth, P.max_depth, bs.valid, hit, hit_emitter);
+                if (es.ends && !es.needs_itx) {
+                    // what the path-end block does for side 0; res is complete: the term this hit would add is an exact zero
+                    { const Vec3f Ln = detach(res); park_f(kLnX, Ln.x); park_f(kLnY, Ln.y); park_f(kLnZ, Ln.z); }
+                    const int d_end = es_end_depth(depth);
+                    if (d_end < P.max_depth) rng.skip_levels(sw::mis(P) == 0 ? 2 : (sw::mis(P) == 1 ? 3 : 5), P.max_depth - d_end);
+                    thr = V(R(1.f)); res = V(R(0.f)); depth = -1;
+                    switch_now = true;
+                    PSDR_CENSUS_EDGE(S.c_nodes++);
+                }
+            }
+            if (switch_now) {
+                // the second path starts AT its first vertex: ray_p's hit has waited in the cold rows since the first path's first trace (this very iteration's, when the
+                // first path ended on its camera ray); of the ray only the origin is wanted (see the late switch below)
+                side = 1;
+                ext.o = second_path_origin();
+                hx.slot = cold_i(kHpSlot); hx.u = cold_f(kHpU); hx.v = cold_f(kHpV); hx.t = cold_f(kHpT);
             }
         }
 
@@ -479,22 +543,14 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
                     { const Vec3f Ln = detach(res); park_f(kLnX, Ln.x); park_f(kLnY, Ln.y); park_f(kLnZ, Ln.z); }
                     // the reference's Li always draws 5 numbers per depth level; skip what this path left
                     if (depth < P.max_depth) rng.skip_levels(sw::mis(P) == 0 ? 2 : (sw::mis(P) == 1 ? 3 : 5), P.max_depth - depth);
-                    side = 1; depth = -1; thr = V(R(1.f)); res = V(R(0.f));
-                    if constexpr (!AD) {
+                    PSDR_CENSUS_EDGE(if (kEarlySwitch) S.c_hits++);
+                    side = kEarlySwitch ? 2 : 1; depth = -1; thr = V(R(1.f)); res = V(R(0.f));      // (2: the early switch's detour, the hit is handed over in the next iteration)
+                    if constexpr (!AD && !kEarlySwitch) {
                         // The second path's camera ray ray_p = sample_primary_ray(p + EdgeEpsilon * n) was traced in the first path's first trace.  Of the ray itself only
                         // the ORIGIN is still wanted - make_its below takes its direction from hit point - origin, and ext.d is set by the BSDF sample before the next
                         // trace reads it -: the sensor's position for a perspective camera, the same for every sample; for an orthographic one the near-plane point,
                         // by the same arithmetic as at the start of the work item
-                        if (sw::ortho(cam)) {
-                            const int edge_i = cold_i(kEdgeI);
-                            const float edge_s = cold_f(kEdgeS), edge_nx = cold_f(kNx), edge_ny = cold_f(kNy);
-                            const float4 r0 = S.ld(cam.pe_off + 3 * edge_i);
-                            const float oms = 1.0f - edge_s;
-                            const float pxv = fmaf(r0.x, oms, r0.z * edge_s), pyv = fmaf(r0.y, oms, r0.w * edge_s);
-                            ext.o = sample_primary_ray<false, !sw::lean>(cam, pxv + kEdgeEpsilon * edge_nx, pyv + kEdgeEpsilon * edge_ny).o;
-                        } else {
-                            ext.o = primary_ray_origin(cam);
-                        }
+                        ext.o = second_path_origin();
                         // ... and its hit was found in the first path's first trace: the second path starts AT its first vertex (path.cpp:38-43)
                         Hit hp; hp.slot = cold_i(kHpSlot); hp.u = cold_f(kHpU); hp.v = cold_f(kHpV); hp.t = cold_f(kHpT);
                         const Its<AD> itp = make_its<AD, LDS, true>(S, hp, ext, false);
@@ -550,6 +606,7 @@ PSDR_DEV void run_paths(SceneView<LDS> &S, const SensorDev &cam, const PathParam
     }
 #undef PSDR_PHASE
 #undef PSDR_CENSUS
+#undef PSDR_CENSUS_EDGE
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -118,6 +118,8 @@ __global__ __launch_bounds__(kBlock, (AD ? (in_lds(LDS) ? PSDR_LDS_AD_WAVES : (L
     if (COUNT) flush_counters(S, ctr);
 #if PSDR_DIAG == 13
     if (!COUNT && MODE == 0) flush_counters(S, ctr);      // (the census of paths.h)
+#elif PSDR_DIAG == 14
+    if (!COUNT && MODE == 1) flush_counters(S, ctr);      // (the census of the side switch, paths.h)
 #endif
 }
 
