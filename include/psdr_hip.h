@@ -257,12 +257,13 @@ typedef struct psdr_counters {
  *      created non-blocking (torch's pool streams) do not synchronise.
  *   2. The caller's duty: every device input of the call is ready ON THE STREAM THAT IS PASSED (written by work queued on it earlier, or complete before the call),
  *      and the outputs are read on that stream or after it has been waited for.
- *   3. Every psdr_hip_*_create (scene, guiding_build, precond, denoise, vdenoise, subdiv, msloss, ssim) returns with the handle usable on ANY stream and with the caller's host and
+ *   3. Every psdr_hip_*_create (scene, guiding_build, precond, denoise, vdenoise, subdiv, msloss, ssim, meshreg) returns with the handle usable on ANY stream and with the caller's host and
  *      device arrays free again: it synchronises `stream` (the scene calls: the NULL stream they work on) before it returns.  They are cold paths.
  *   4. What the library serialises: calls on ONE SCENE from different streams (above).  psdr_hip_scene_update waits on the host for the scene's last call before it
  *      rewrites anything, works on the NULL stream and synchronises it before it returns: a render queued before it sees the old state, one issued after it the new.
  *   5. What it does not: a denoise / vdenoise / precond / msloss handle owns work frames and so does an ssim handle, so calls on one such handle must follow each other on one stream or be ordered
- *      by the caller; subdiv handles are read-only after the create and may be applied from any number of streams.
+ *      by the caller; the same holds for a meshreg handle (it owns the contribution buffers and partial sums of its eval).  subdiv handles are read-only after the create and
+ *      may be applied from any number of streams.
  * "No call synchronises the device" (above) means hipDeviceSynchronize; the calls that wait for their own stream say so: the creates, psdr_hip_guiding_build,
  * psdr_hip_precond_solve (it reads its residuals), the *_counted renders, and a render that has to grow the scene's scratch (first call, or a larger one). */
 const char *psdr_hip_last_error(void);
@@ -749,6 +750,49 @@ int psdr_hip_ssim_create(int32_t W, int32_t H, int32_t C, int32_t window, const 
 int psdr_hip_ssim_eval(psdr_hip_ssim *s, const float *img, const float *target, const float *mask, float *out, float *grad, void *stream);
 int psdr_hip_ssim_map(psdr_hip_ssim *s, float *out, void *stream);
 int psdr_hip_ssim_destroy(psdr_hip_ssim *s);
+
+/* THE MESH REGULARISERS - UNIFORM LAPLACIAN, NORMAL CONSISTENCY, EDGE LENGTH - VALUE AND VERTEX GRADIENT IN ONE FUSED PASS (csrc/hip/meshreg.hip; psdr_jit_amd/meshreg.py;
+ * DESIGN.md section 7j).  The part of a shape-optimisation loss that depends on the mesh, not on the image: it holds the vertices in place where the image is silent.  Device
+ * pointers in eval, plain launches on `stream` (three with a gradient, two without), no host synchronisation, no copy to the host, no atomics: the same input gives the same
+ * bits.  Added under ABI 16 like the ssim entry points: nothing existing changed.
+ *
+ * The definition.  V = v: float32 [n, 3].  F: [f, 3] vertex ids, every face with three distinct ids in [0, n); no welding.  The topology is built on the host once per mesh
+ * (psdr_jit_amd/meshreg.py: mesh_topology) and travels to create:
+ *     E        the distinct undirected edges (a < b) of F in ascending (a, b) order, e of them.  N(i) = the other ends of the edges at i, deg_i = |N(i)| (the CSR of
+ *              psdr_jit_amd/precond.py: laplacian_csr)
+ *     hinges   the edges with exactly two incident faces, in edge order, h of them, each a row (a, b, c, d): c the vertex opposite the edge in its first incident face (the
+ *              lower face index), d the one in the second.  A boundary edge (one face) and a non-manifold edge (three or more) form no hinge; two copies of one face make
+ *              a hinge with c == d.
+ *     n1 = (b - a) x (c - a),  n2 = (d - a) x (b - a),  u = n / |n|: independent of the faces' winding
+ * The terms:
+ *     laplacian = (1 / n_L) sum_i |delta_i|^2,   delta_i = v_i - (1 / deg_i) sum_{j in N(i)} v_j;  delta_i = 0 for a vertex no face uses, n_L = the number of vertices with
+ *                 deg_i > 0, the value 0 when n_L = 0.   d / dv_k = (2 / n_L) (delta_k - sum_{j in N(k)} delta_j / deg_j): a gather over the same CSR
+ *     normal    = (1 / h) sum_hinges 1/2 |u1 - u2|^2:  1 - cos of the dihedral deviation without the cancellation of 1 - u1 . u2;  0 on a flat hinge, 2 on one folded back
+ *                 onto itself, smooth at both.  A hinge with |n1|^2 < 2^-100 or |n2|^2 < 2^-100 adds 0 to the value and no gradient; it still counts in h.
+ *                 With w = u1 - u2:  d / dn1 = (w - (u1 . w) u1) / |n1|,  d / dn2 = -(w - (u2 . w) u2) / |n2|  (the projections applied to w, which is small where the hinge
+ *                 is flat);  d / db = (c - a) x g1 + g2 x (d - a),  d / dc = g1 x (b - a),  d / dd = (b - a) x g2,  d / da = -(their sum)
+ *     edge      = (1 / e) sum_edges (|v_a - v_b| - L0)^2,  L0 = target_length >= 0.  At L0 == 0 the summand is |v_a - v_b|^2 and nothing is divided; at L0 > 0 an edge with
+ *                 |v_a - v_b|^2 < 2^-100 adds L0^2 and no gradient.
+ *     loss      = w_lap laplacian + w_nor normal + w_edge edge, weights[3] = (w_lap, w_nor, w_edge).  A term whose weight is 0 is not evaluated: its reported value is 0, it
+ *                 does no work and the gradient is the other terms' bit for bit; a term with e = 0 or h = 0 is 0.  The terms are added in this order, those that are off left out.
+ * out[4] (device) = (loss, laplacian, normal, edge); grad (device, [n, 3], or NULL for a value-only call, which gives the same out bits) = d loss / d V.
+ *
+ * create(n, e, h, edges [e, 2], hinges [h, 4], row_begin [n + 1], col, ev_begin [n + 1], ev_elem, ev_role [2 e], hv_begin [n + 1], hv_elem, hv_role [4 h]): HOST arrays, read by
+ * create.  ev_* and hv_* are the inverted indices: per vertex the (element, role) pairs that name it, in ascending (element, role) order - role 0, 1 = a, b of an edge, role
+ * 0 .. 3 = a, b, c, d of a hinge - so that the gradient is a gather in a fixed order.  It is refused with psdr_hip_last_error text BEFORE any device call unless: out is not
+ * NULL; 1 <= n <= 2^26, 0 <= e, h <= 2^26; no array that has entries is NULL; every edge has 0 <= a < b < n; every hinge's ids lie in [0, n) with a < b and c, d off the
+ * edge; row_begin, ev_begin, hv_begin start at 0 and never decrease; every col lies in [0, n) and is not its row; ev_begin ends at 2 e and hv_begin at 4 h; every element
+ * lies in [0, e) or [0, h) and every role in [0, 2) or [0, 4); the vertex an entry names is the one that lists it; the entries of a vertex ascend.
+ * The handle owns delta and delta / deg ([n] float4 each), one float4 per edge, four per hinge and one partial sum per 256 elements of each kind.
+ * eval is refused before any launch for a NULL handle, v, weights or out, a grad that is v, and a weight or target_length that is negative or not finite.
+ * The sums: a workgroup of 256 elements of one kind adds its summands in a fixed order (the wave, then its four waves), one workgroup then adds the partial sums of each
+ * kind in a fixed order; a vertex adds its contributions in the stored order and scales each term's sum once (2 w_lap / n_L, w_nor / h, w_edge / e, rounded from double). */
+typedef struct psdr_hip_meshreg psdr_hip_meshreg;
+int psdr_hip_meshreg_create(int32_t n, int32_t e, int32_t h, const int32_t *edges, const int32_t *hinges, const int32_t *row_begin, const int32_t *col,
+                            const int32_t *ev_begin, const int32_t *ev_elem, const int32_t *ev_role, const int32_t *hv_begin, const int32_t *hv_elem, const int32_t *hv_role,
+                            psdr_hip_meshreg **out, void *stream);
+int psdr_hip_meshreg_eval(psdr_hip_meshreg *m, const float *v, const float *weights, float target_length, float *out, float *grad, void *stream);
+int psdr_hip_meshreg_destroy(psdr_hip_meshreg *m);
 
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);

@@ -1474,3 +1474,5 @@ from .msloss import MultiScaleLoss, pyramid_shapes  # noqa: E402,F401
 
 # the SSIM loss 1 - mean structural similarity, value and image gradient in one fused pass (ssim.py; kernels: csrc/hip/ssim.hip)
 from .ssim import SSIMLoss, gaussian_window  # noqa: E402,F401
+# the mesh regularisers (uniform Laplacian, normal consistency, edge length), value and vertex gradient in one fused pass (meshreg.py; kernels: csrc/hip/meshreg.hip)
+from .meshreg import MeshRegularizer, mesh_topology  # noqa: E402,F401

@@ -18,6 +18,7 @@ SYMBOLS = [
     "psdr_hip_subdiv_create", "psdr_hip_subdiv_apply", "psdr_hip_subdiv_apply_adj", "psdr_hip_subdiv_destroy",
     "psdr_hip_msloss_create", "psdr_hip_msloss_eval", "psdr_hip_msloss_level", "psdr_hip_msloss_destroy",
     "psdr_hip_ssim_create", "psdr_hip_ssim_eval", "psdr_hip_ssim_map", "psdr_hip_ssim_destroy",
+    "psdr_hip_meshreg_create", "psdr_hip_meshreg_eval", "psdr_hip_meshreg_destroy",
 ]
 
 
@@ -121,6 +122,9 @@ def lib():
         L.psdr_hip_ssim_eval.argtypes = [C.c_void_p] * 7
         L.psdr_hip_ssim_map.argtypes = [C.c_void_p] * 3
         L.psdr_hip_ssim_destroy.argtypes = [C.c_void_p]
+        L.psdr_hip_meshreg_create.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 10 + [C.POINTER(C.c_void_p), C.c_void_p]
+        L.psdr_hip_meshreg_eval.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.psdr_hip_meshreg_destroy.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
