@@ -263,7 +263,8 @@ typedef struct psdr_counters {
  *      rewrites anything, works on the NULL stream and synchronises it before it returns: a render queued before it sees the old state, one issued after it the new.
  *   5. What it does not: a denoise / vdenoise / precond / msloss handle owns work frames and so does an ssim handle, so calls on one such handle must follow each other on one stream or be ordered
  *      by the caller; the same holds for a meshreg handle (it owns the contribution buffers and partial sums of its eval).  subdiv handles are read-only after the create and
- *      may be applied from any number of streams.
+ *      may be applied from any number of streams.  The chamfer entry points (psdr_hip_chamfer_nearest, psdr_hip_chamfer_eval) have no handle and no create: their work
+ *      arrays (keys, partial) are the caller's, one set per call in flight, and psdr_hip_chamfer_plan touches no device.
  * "No call synchronises the device" (above) means hipDeviceSynchronize; the calls that wait for their own stream say so: the creates, psdr_hip_guiding_build,
  * psdr_hip_precond_solve (it reads its residuals), the *_counted renders, and a render that has to grow the scene's scratch (first call, or a larger one). */
 const char *psdr_hip_last_error(void);
@@ -793,6 +794,46 @@ int psdr_hip_meshreg_create(int32_t n, int32_t e, int32_t h, const int32_t *edge
                             psdr_hip_meshreg **out, void *stream);
 int psdr_hip_meshreg_eval(psdr_hip_meshreg *m, const float *v, const float *weights, float target_length, float *out, float *grad, void *stream);
 int psdr_hip_meshreg_destroy(psdr_hip_meshreg *m);
+
+/* THE CHAMFER DISTANCE BETWEEN TWO POINT SETS - EXACT NEAREST NEIGHBOURS BY A BRUTE-FORCE SCAN, VALUE AND BOTH GRADIENTS (csrc/hip/chamfer.hip; psdr_jit_amd/chamfer.py; DESIGN.md
+ * section 7k).  The part of a shape-optimisation loop that measures the shape itself: how far a mesh's surface samples are from a scan, a point cloud or another mesh's samples.
+ * Stateless entry points: device pointers, work arrays from the caller, plain launches on `stream`, no host synchronisation, no copy to the host, no float atomics: the same
+ * input gives the same bits.  Added under ABI 16 like the meshreg entry points: nothing existing changed.
+ *
+ * The definition.  x: float32 [n, 3], y: float32 [m, 3], 1 <= n, m <= 2^26, all finite.
+ *     distance  d2(i, j) = (dx dx + dy dy) + dz dz with dx = x_i0 - y_j0, dy = x_i1 - y_j1, dz = x_i2 - y_j2: every operation one float32 rounding, nothing fused, in this
+ *               order.  The difference form on purpose: |x|^2 + |y|^2 - 2 x.y cancels exactly where a neighbour is near; this form does not, and a float32 restatement
+ *               reproduces it bit for bit.  d2 >= +0.
+ *     nearest   a(i) = the lowest j that minimises d2(i, j), dist2_xy[i] = d2(i, a(i));  b(j) = the lowest i that minimises d2(i, j), dist2_yx[j] = d2(b(j), j).  The
+ *               lexicographic minimum over (d2, j) is associative and commutative: the result does not depend on how the scan is split or merged.  With non-finite inputs
+ *               the values are unspecified, but every index lies in range.
+ *     loss      = w_xy (1 / n) sum_i rho(dist2_xy[i]) + w_yx (1 / m) sum_j rho(dist2_yx[j]), weights[2] = (w_xy, w_yx);  rho(s) = s (squared != 0) or sqrt(s) (squared == 0),
+ *               whose derivative at s = 0 is defined as 0.  A term whose weight is 0 is not evaluated: its reported value is 0 and the gradients are the other term's bit for
+ *               bit.  The terms are added in this order.
+ *     gradient  the indices are constants.  With k(s) = 2 w / count (squared) or (w / count) / sqrt(s), 0 at s = 0 (not squared), w / count and 2 w / count rounded from double:
+ *               d loss / d x_i = k_xy(dist2_xy[i]) (x_i - y_a(i))  +  sum over {j : b(j) = i}, in ascending j, of k_yx(dist2_yx[j]) (x_i - y_j)
+ *               and y_j receives the mirror image.  Each product is k times the rounded difference; the second sum starts at 0 and is added to the first contribution once.
+ *
+ * psdr_hip_chamfer_plan(n, m) -> (tile, queries_per_lane, slices, slice_len): how psdr_hip_chamfer_nearest splits its scan, a pure function, callable without a GPU.  A
+ * workgroup of 256 lanes holds 256 queries_per_lane queries; slice s holds the candidates [s slice_len, min(m, (s + 1) slice_len)), slice_len a multiple of tile, no slice
+ * empty; the grid is ceil(n / (256 queries_per_lane)) x slices.  queries_per_lane = 4 for n > 1024, else 1; slices = the fewest that bring the grid to 2048 workgroups, at
+ * most one per tile.  The result of the scan does not depend on the plan.
+ * psdr_hip_chamfer_nearest(x, n, y, m, keys, index, dist2): one direction; index int32 [n] = a, dist2 float32 [n]; keys: uint64 [n] work array of the caller (the per-query
+ * minimum of (float bits of d2) << 32 | j, merged over the slices by an integer atomic minimum).  For b and dist2_yx call it with the sets swapped.
+ * psdr_hip_chamfer_eval(x, n, y, m, index_xy, dist2_xy [n], index_yx, dist2_yx [m], x_begin [n + 1], x_list [m], y_begin [m + 1], y_list [n], weights, squared, partial, out,
+ * grad_x, grad_y): out[3] (device) = (loss, mean_i rho(dist2_xy), mean_j rho(dist2_yx)); grad_x [n, 3], grad_y [m, 3] (device; both NULL for a value-only call, which gives the
+ * same out bits).  x_begin / x_list: the inverted index of index_yx - x_list holds the j in ascending (index_yx[j], j) order (a stable sort of index_yx), x_begin[i] the
+ * position of point i's first entry, x_begin[n] = m; y_begin / y_list the same for index_xy.  They are the caller's duty; the kernel clamps what it reads from them into
+ * range.  partial: double work array of ceil(n / 256) + ceil(m / 256) entries (the sums of rho are
+ * added in double and each mean is rounded to float32 once).  The arrays of a direction whose weight is 0, and the inverted indices of a value-only call, are
+ * not read and may be NULL.  One launch per point set and one that adds the per-workgroup sums in a fixed order.
+ * All three are refused with psdr_hip_last_error text before any device call for n or m outside [1, 2^26], a NULL array that would be read or written, a weight that is
+ * negative or not finite, one gradient without the other, and a gradient that aliases an input or the other gradient. */
+int psdr_hip_chamfer_plan(int32_t n, int32_t m, int32_t *tile, int32_t *queries_per_lane, int32_t *slices, int32_t *slice_len);
+int psdr_hip_chamfer_nearest(const float *x, int32_t n, const float *y, int32_t m, uint64_t *keys, int32_t *index, float *dist2, void *stream);
+int psdr_hip_chamfer_eval(const float *x, int32_t n, const float *y, int32_t m, const int32_t *index_xy, const float *dist2_xy, const int32_t *index_yx, const float *dist2_yx,
+                          const int32_t *x_begin, const int32_t *x_list, const int32_t *y_begin, const int32_t *y_list, const float *weights, int32_t squared,
+                          double *partial, float *out, float *grad_x, float *grad_y, void *stream);
 
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);

@@ -1476,3 +1476,5 @@ from .msloss import MultiScaleLoss, pyramid_shapes  # noqa: E402,F401
 from .ssim import SSIMLoss, gaussian_window  # noqa: E402,F401
 # the mesh regularisers (uniform Laplacian, normal consistency, edge length), value and vertex gradient in one fused pass (meshreg.py; kernels: csrc/hip/meshreg.hip)
 from .meshreg import MeshRegularizer, mesh_topology  # noqa: E402,F401
+# the Chamfer distance between two point sets (exact nearest neighbours, value and both gradients) and points sampled from a mesh's surface (chamfer.py; kernels: csrc/hip/chamfer.hip)
+from .chamfer import ChamferDistance, SurfaceSampler, nearest_points, launch_plan, sample_surface, sampling_csr  # noqa: E402,F401

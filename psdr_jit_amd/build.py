@@ -45,6 +45,7 @@ OPERATOR_UNITS = [
 # the operators on meshes rather than frames: the same row format, compiled after OPERATOR_UNITS
 MESH_OPERATOR_UNITS = [
     ("meshreg", "meshreg.hip", "psdr_hip_meshreg_*: the mesh regularisers (uniform Laplacian, normal consistency, edge length), value and vertex gradient in three launches", ()),
+    ("chamfer", "chamfer.hip", "psdr_hip_chamfer_*: the Chamfer distance between two point sets, exact nearest neighbours by an LDS-tiled scan over query blocks x candidate slices, value and both gradients", ()),
 ]
 OPERATOR_TUS = [(name, _H(src)[0], [], [os.path.join(ROOT, "include", "psdr_hip.h")] + _H(*headers) + BUILD_DEPS) for name, src, _what, headers in OPERATOR_UNITS + MESH_OPERATOR_UNITS]      # hip_units()'s tuples
 HIP_SRCS = [API_SRC, UNITS_SRC, SCENE_SRC] + [u[1] for u in OPERATOR_TUS]

@@ -19,6 +19,7 @@ SYMBOLS = [
     "psdr_hip_msloss_create", "psdr_hip_msloss_eval", "psdr_hip_msloss_level", "psdr_hip_msloss_destroy",
     "psdr_hip_ssim_create", "psdr_hip_ssim_eval", "psdr_hip_ssim_map", "psdr_hip_ssim_destroy",
     "psdr_hip_meshreg_create", "psdr_hip_meshreg_eval", "psdr_hip_meshreg_destroy",
+    "psdr_hip_chamfer_plan", "psdr_hip_chamfer_nearest", "psdr_hip_chamfer_eval",
 ]
 
 
@@ -125,6 +126,9 @@ def lib():
         L.psdr_hip_meshreg_create.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 10 + [C.POINTER(C.c_void_p), C.c_void_p]
         L.psdr_hip_meshreg_eval.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         L.psdr_hip_meshreg_destroy.argtypes = [C.c_void_p]
+        L.psdr_hip_chamfer_plan.argtypes = [C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 4
+        L.psdr_hip_chamfer_nearest.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
+        L.psdr_hip_chamfer_eval.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8 + [C.POINTER(C.c_float), C.c_int32] + [C.c_void_p] * 5
         _lib = L
     return _lib
 

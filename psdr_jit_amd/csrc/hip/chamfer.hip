@@ -1,0 +1,294 @@
+// chamfer.hip — the Chamfer distance between two point sets: the exact nearest neighbour of every point in the other set by a brute-force scan, the loss and its gradient
+// with respect to both sets (Python surface: psdr_jit_amd/chamfer.py).
+//
+// The definition (include/psdr_hip.h states it in full).  x float32 [n, 3], y float32 [m, 3], 1 <= n, m <= 2^26.
+//   d2(i, j)    = (dx dx + dy dy) + dz dz,  dx = x_i0 - y_j0 ...: the difference form, every operation one float32 rounding, nothing fused
+//   a(i)        = the lowest j that minimises d2(i, j);  dist2_xy[i] = d2(i, a(i));  b(j), dist2_yx[j]: the same with the roles swapped
+//   loss        = w_xy (1 / n) sum_i rho(dist2_xy[i]) + w_yx (1 / m) sum_j rho(dist2_yx[j]);  rho(s) = s (squared) or sqrt(s), whose derivative at 0 is defined as 0
+//   d / dx_i    = k_xy(dist2_xy[i]) (x_i - y_a(i)) + sum over {j : b(j) = i}, ascending j, of k_yx(dist2_yx[j]) (x_i - y_j);  k(s) = 2 w / count (squared) or
+//                 (w / count) / sqrt(s), 0 at s = 0;  y_j receives the mirror image.  The indices are constants.
+//
+// The scan (k_scan<Q>).  A lane holds Q queries in registers; the candidates of the workgroup's slice go through LDS a tile at a time as x / y / z planes, and every lane
+// reads the same float4 of a plane: a broadcast, four candidates per read, each serving the lane's Q queries.  A lane walks its candidates in ascending j and replaces its
+// best on a strict `<`, which is the tie rule inside a slice; the best leaves the lane as the 64-bit key (float bits of d2) << 32 | j - d2 >= +0, so keys order as
+// unsigned integers - and the slices are merged by one integer minimum per query (atomicMin on the key array: an integer minimum is associative and commutative, the
+// result does not depend on the order).  With one slice the key is stored.  The grid is query blocks x candidate slices (psdr_hip_chamfer_plan): 10 000 queries alone
+// are 10 workgroups on 256 CUs.  A partial last tile is padded with +infinity coordinates: d2 = +inf never passes `<`.  A d2 that is NaN never passes it either, so with
+// non-finite inputs the index stays the slice's first candidate: in range.
+// The evaluation (k_eval, one launch per point set): a lane per point - its own term from (index, dist2), then the points of the other set that chose it through the
+// inverted index (per point the j in ascending order, built by the caller with a stable sort), one store of the gradient, no atomics; the workgroup adds rho(dist2) in a
+// fixed order into its partial sum (in double, so that the mean carries one rounding).  k_finish: one workgroup adds the partial sums of each direction in a fixed order.
+// No host synchronisation; the same input gives the same bits.  No contraction in this unit (the build's -ffp-contract=off, and the distance is written with __fmul_rn / __fadd_rn).
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "../../../include/psdr_hip.h"
+
+namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
+
+namespace {
+
+constexpr int kThreads = 256;           // 4 waves
+constexpr int kSumThreads = 1024;       // k_finish: one workgroup, 16 waves
+constexpr int kTile = 1024;             // candidates per LDS tile: three planes of 4 KiB
+constexpr int kWideQueries = 4;         // queries per lane of the wide scan
+constexpr int kNarrowMax = 1024;        // n <= kNarrowMax: one query per lane (the wide scan would leave three of four registers idle)
+constexpr int kTargetGroups = 2048;     // workgroups the grid aims at: 8 per CU, the most that 256 CUs hold of 256-thread workgroups
+constexpr int kMaxCount = 1 << 26;
+
+struct Plan { int tile, qpl, slices, slice_len; };
+
+// the split, a pure function of (n, m); psdr_jit_amd/chamfer.py: launch_plan states it a second time
+inline Plan plan_of(int n, int m) {
+    Plan p;
+    p.tile = kTile;
+    p.qpl = n > kNarrowMax ? kWideQueries : 1;
+    const int per_group = kThreads * p.qpl;
+    const int qblocks = (n + per_group - 1) / per_group;
+    const int tiles = (m + kTile - 1) / kTile;
+    int want = (kTargetGroups + qblocks - 1) / qblocks;
+    if (want > tiles) want = tiles;
+    const int tiles_per_slice = (tiles + want - 1) / want;
+    p.slice_len = tiles_per_slice * kTile;
+    p.slices = (m + p.slice_len - 1) / p.slice_len;           // no empty slice: slice s is [s slice_len, min(m, (s + 1) slice_len))
+    return p;
+}
+
+template <int Q> __global__ void __launch_bounds__(kThreads) k_scan(const float *__restrict__ x, int n, const float *__restrict__ y, int m, int slice_len, int slices,
+                                                                    unsigned long long *__restrict__ keys) {
+    __shared__ float4 s_c[3][kTile / 4];
+    float *s_x = reinterpret_cast<float *>(s_c[0]), *s_y = reinterpret_cast<float *>(s_c[1]), *s_z = reinterpret_cast<float *>(s_c[2]);
+    const int j0 = blockIdx.y * slice_len;
+    const int j1 = min(m, j0 + slice_len);
+    float qx[Q], qy[Q], qz[Q], best[Q];
+    int bj[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const int i = (blockIdx.x * Q + q) * kThreads + threadIdx.x;
+        const bool live = i < n;
+        qx[q] = live ? x[3LL * i] : 0.f;
+        qy[q] = live ? x[3LL * i + 1] : 0.f;
+        qz[q] = live ? x[3LL * i + 2] : 0.f;
+        best[q] = INFINITY;
+        bj[q] = j0;
+    }
+    for (int base = j0; base < j1; base += kTile) {
+        __syncthreads();                                       // (the previous tile has been read)
+        for (int t = threadIdx.x; t < kTile; t += kThreads) {
+            const int j = base + t;
+            const bool live = j < j1;
+            s_x[t] = live ? y[3LL * j] : INFINITY;
+            s_y[t] = live ? y[3LL * j + 1] : INFINITY;
+            s_z[t] = live ? y[3LL * j + 2] : INFINITY;
+        }
+        __syncthreads();
+        const int groups = (min(kTile, j1 - base) + 3) >> 2;
+        for (int g = 0; g < groups; ++g) {
+            const float4 cx = s_c[0][g], cy = s_c[1][g], cz = s_c[2][g];
+            const float ax[4] = {cx.x, cx.y, cx.z, cx.w}, ay[4] = {cy.x, cy.y, cy.z, cy.w}, az[4] = {cz.x, cz.y, cz.z, cz.w};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = base + 4 * g + u;
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    const float dx = __fsub_rn(qx[q], ax[u]), dy = __fsub_rn(qy[q], ay[u]), dz = __fsub_rn(qz[q], az[u]);
+                    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+                    if (d2 < best[q]) { best[q] = d2; bj[q] = j; }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const int i = (blockIdx.x * Q + q) * kThreads + threadIdx.x;
+        if (i < n) {
+            const unsigned long long key = ((unsigned long long) __float_as_uint(best[q]) << 32) | (unsigned int) bj[q];
+            if (slices == 1) keys[i] = key;
+            else atomicMin(keys + i, key);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) k_unpack(const unsigned long long *__restrict__ keys, int n, int m, int *__restrict__ idx, float *__restrict__ dist2) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long key = keys[i];
+    idx[i] = (int) min((unsigned int) (key & 0xffffffffu), (unsigned int) (m - 1));
+    dist2[i] = __uint_as_float((unsigned int) (key >> 32));
+}
+
+// the sum over the workgroup in a fixed order, valid in thread 0: a wave by shuffles, the waves one after the other.  In double: the sum of 2^26 float32 terms then carries
+// one rounding, the final one, whatever the count
+template <int THREADS> __device__ double block_sum(double v, double *s_red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    __syncthreads();                                       // (s_red of the previous sum has been read)
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0)
+        for (int k = 0; k < THREADS / 64; ++k) t += s_red[k];
+    return t;
+}
+
+// one point set p [n, 3] against the other set o [m, 3]
+struct Side {
+    const float *p, *o;
+    int n, m;
+    const int *idx;                     // [n] the point's nearest in o, or NULL: its own direction is off
+    const float *dist2;                 // [n]
+    const int *inv_begin, *inv_list;    // [n + 1], [m]: the points of o that chose this one, ascending, or NULL: the other direction is off
+    const float *o_dist2;               // [m] their squared distances
+    float k_own, k_inv;                 // squared: 2 w / count; else w / count (divided by sqrt(s) per point)
+    float *grad;                        // [n, 3] or NULL
+    double *partial;                    // one sum per workgroup (only when idx)
+};
+
+__device__ __forceinline__ float coefficient(float k, float s, int squared) { return squared ? k : (s > 0.f ? k / sqrtf(s) : 0.f); }
+
+__global__ void __launch_bounds__(kThreads) k_eval(Side S, int squared) {
+    __shared__ double s_red[kThreads / 64];
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    float val = 0.f;
+    if (i < S.n) {
+        const float px = S.p[3LL * i], py = S.p[3LL * i + 1], pz = S.p[3LL * i + 2];
+        float gx = 0.f, gy = 0.f, gz = 0.f;
+        bool have = false;
+        if (S.idx) {
+            const float s = S.dist2[i];
+            val = squared ? s : sqrtf(s);
+            if (S.grad) {
+                const int a = min(max(S.idx[i], 0), S.m - 1);
+                const float k = coefficient(S.k_own, s, squared);
+                gx = k * (px - S.o[3LL * a]);
+                gy = k * (py - S.o[3LL * a + 1]);
+                gz = k * (pz - S.o[3LL * a + 2]);
+                have = true;
+            }
+        }
+        if (S.inv_begin && S.grad) {
+            const int b0 = min(max(S.inv_begin[i], 0), S.m), b1 = min(max(S.inv_begin[i + 1], b0), S.m);
+            float sx = 0.f, sy = 0.f, sz = 0.f;
+#pragma unroll 4
+            for (int t = b0; t < b1; ++t) {
+                const int j = min(max(S.inv_list[t], 0), S.m - 1);
+                const float k = coefficient(S.k_inv, S.o_dist2[j], squared);
+                sx += k * (px - S.o[3LL * j]);
+                sy += k * (py - S.o[3LL * j + 1]);
+                sz += k * (pz - S.o[3LL * j + 2]);
+            }
+            gx = have ? gx + sx : sx;
+            gy = have ? gy + sy : sy;
+            gz = have ? gz + sz : sz;
+        }
+        if (S.grad) {
+            float *g = S.grad + 3LL * i;
+            g[0] = gx;
+            g[1] = gy;
+            g[2] = gz;
+        }
+    }
+    if (S.idx) {                                            // (uniform over the launch)
+        const double t = block_sum<kThreads>((double) val, s_red);
+        if (threadIdx.x == 0) S.partial[blockIdx.x] = t;
+    }
+}
+
+// a lane adds every 1024th partial sum of a direction in ascending order, then the workgroup's fixed order
+__device__ double run_sum(const double *p, int count, double *s_red) {
+    double a = 0.0;
+    for (int t = threadIdx.x; t < count; t += kSumThreads) a += p[t];
+    return block_sum<kSumThreads>(a, s_red);
+}
+
+__global__ void __launch_bounds__(kSumThreads) k_finish(const double *__restrict__ partial, int blocks_x, int blocks_y, int n, int m, float w_xy, float w_yx, float *__restrict__ out) {
+    __shared__ double s_red[kSumThreads / 64];
+    const double sx = run_sum(partial, blocks_x, s_red);
+    const double sy = run_sum(partial + blocks_x, blocks_y, s_red);
+    if (threadIdx.x == 0) {
+        const float tx = blocks_x ? (float) (sx / (double) n) : 0.f, ty = blocks_y ? (float) (sy / (double) m) : 0.f;
+        float loss = 0.f;
+        if (blocks_x) loss = w_xy * tx;
+        if (blocks_y) { const float t = w_yx * ty; loss = blocks_x ? loss + t : t; }
+        out[0] = loss;
+        out[1] = tx;
+        out[2] = ty;
+    }
+}
+
+inline int blocks_of(int count) { return (count + kThreads - 1) / kThreads; }
+
+inline std::string range_text(const char *name, long long v) { return std::string(name) + " = " + std::to_string(v) + ", must lie in [1, 2^26]"; }
+
+} // namespace
+
+extern "C" {
+
+int psdr_hip_chamfer_plan(int32_t n, int32_t m, int32_t *tile, int32_t *queries_per_lane, int32_t *slices, int32_t *slice_len) {
+    const std::string who = "psdr_hip_chamfer_plan: ";
+    if (n < 1 || n > kMaxCount) return psdr::api_fail(who + range_text("n", n));
+    if (m < 1 || m > kMaxCount) return psdr::api_fail(who + range_text("m", m));
+    if (!tile || !queries_per_lane || !slices || !slice_len) return psdr::api_fail(who + "NULL argument");
+    const Plan p = plan_of(n, m);
+    *tile = p.tile;
+    *queries_per_lane = p.qpl;
+    *slices = p.slices;
+    *slice_len = p.slice_len;
+    return 0;
+}
+
+int psdr_hip_chamfer_nearest(const float *x, int32_t n, const float *y, int32_t m, uint64_t *keys, int32_t *index, float *dist2, void *stream) {
+    const std::string who = "psdr_hip_chamfer_nearest: ";
+    if (n < 1 || n > kMaxCount) return psdr::api_fail(who + range_text("n", n));
+    if (m < 1 || m > kMaxCount) return psdr::api_fail(who + range_text("m", m));
+    if (!x || !y || !keys || !index || !dist2) return psdr::api_fail(who + "NULL argument");
+    const Plan p = plan_of(n, m);
+    hipStream_t st = (hipStream_t) stream;
+    unsigned long long *k = reinterpret_cast<unsigned long long *>(keys);
+    if (p.slices > 1) {
+        const hipError_t e = hipMemsetAsync(k, 0xff, (size_t) n * sizeof(unsigned long long), st);          // above every key: the float half of a key is at most +infinity's bits
+        if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
+    }
+    const int per_group = kThreads * p.qpl;
+    const dim3 grid((unsigned) ((n + per_group - 1) / per_group), (unsigned) p.slices);
+    if (p.qpl == 1) k_scan<1><<<grid, kThreads, 0, st>>>(x, n, y, m, p.slice_len, p.slices, k);
+    else k_scan<kWideQueries><<<grid, kThreads, 0, st>>>(x, n, y, m, p.slice_len, p.slices, k);
+    k_unpack<<<blocks_of(n), kThreads, 0, st>>>(k, n, m, index, dist2);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
+    return 0;
+}
+
+int psdr_hip_chamfer_eval(const float *x, int32_t n, const float *y, int32_t m, const int32_t *index_xy, const float *dist2_xy, const int32_t *index_yx, const float *dist2_yx,
+                          const int32_t *x_begin, const int32_t *x_list, const int32_t *y_begin, const int32_t *y_list, const float *weights, int32_t squared,
+                          double *partial, float *out, float *grad_x, float *grad_y, void *stream) {
+    const std::string who = "psdr_hip_chamfer_eval: ";
+    if (n < 1 || n > kMaxCount) return psdr::api_fail(who + range_text("n", n));
+    if (m < 1 || m > kMaxCount) return psdr::api_fail(who + range_text("m", m));
+    if (!x || !y || !weights || !partial || !out) return psdr::api_fail(who + "NULL argument");
+    for (int k = 0; k < 2; ++k)
+        if (!std::isfinite(weights[k]) || weights[k] < 0.f) return psdr::api_fail(who + "weights[" + std::to_string(k) + "] = " + std::to_string(weights[k]) + ", must be finite and not negative");
+    if (!grad_x != !grad_y) return psdr::api_fail(who + "grad_x and grad_y must both be given or both be NULL");
+    if (grad_x && (grad_x == x || grad_x == y || grad_y == x || grad_y == y || grad_x == grad_y)) return psdr::api_fail(who + "grad_x and grad_y must be arrays of their own");
+    const bool on_xy = weights[0] > 0.f, on_yx = weights[1] > 0.f;
+    if (on_xy && (!index_xy || !dist2_xy)) return psdr::api_fail(who + "weights[0] > 0 needs index_xy and dist2_xy");
+    if (on_yx && (!index_yx || !dist2_yx)) return psdr::api_fail(who + "weights[1] > 0 needs index_yx and dist2_yx");
+    if (grad_x && on_xy && (!y_begin || !y_list)) return psdr::api_fail(who + "the gradient of the x -> y term needs y_begin and y_list, the inverted index of index_xy");
+    if (grad_x && on_yx && (!x_begin || !x_list)) return psdr::api_fail(who + "the gradient of the y -> x term needs x_begin and x_list, the inverted index of index_yx");
+    const double unit = squared ? 2.0 : 1.0;
+    const float k_xy = (float) (unit * (double) weights[0] / (double) n), k_yx = (float) (unit * (double) weights[1] / (double) m);
+    const int bx = on_xy ? blocks_of(n) : 0, by = on_yx ? blocks_of(m) : 0;
+    hipStream_t st = (hipStream_t) stream;
+    Side X{x, y, n, m, on_xy ? index_xy : nullptr, dist2_xy, on_yx ? x_begin : nullptr, x_list, dist2_yx, k_xy, k_yx, grad_x, partial};
+    Side Y{y, x, m, n, on_yx ? index_yx : nullptr, dist2_yx, on_xy ? y_begin : nullptr, y_list, dist2_xy, k_yx, k_xy, grad_y, partial + bx};
+    if (on_xy || grad_x) k_eval<<<blocks_of(n), kThreads, 0, st>>>(X, squared ? 1 : 0);
+    if (on_yx || grad_y) k_eval<<<blocks_of(m), kThreads, 0, st>>>(Y, squared ? 1 : 0);
+    k_finish<<<1, kSumThreads, 0, st>>>(partial, bx, by, n, m, weights[0], weights[1], out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
+    return 0;
+}
+
+} // extern "C"
