@@ -264,7 +264,8 @@ typedef struct psdr_counters {
  *   5. What it does not: a denoise / vdenoise / precond / msloss handle owns work frames and so does an ssim handle, so calls on one such handle must follow each other on one stream or be ordered
  *      by the caller; the same holds for a meshreg handle (it owns the contribution buffers and partial sums of its eval).  subdiv handles are read-only after the create and
  *      may be applied from any number of streams.  The chamfer entry points (psdr_hip_chamfer_nearest, psdr_hip_chamfer_eval) have no handle and no create: their work
- *      arrays (keys, partial) are the caller's, one set per call in flight, and psdr_hip_chamfer_plan touches no device.
+ *      arrays (keys, partial) are the caller's, one set per call in flight, and psdr_hip_chamfer_plan touches no device.  The same holds for the point-to-mesh entry points
+ *      (psdr_hip_pointmesh_nearest, psdr_hip_pointmesh_eval: records, keys, corners and partial are the caller's; psdr_hip_pointmesh_plan touches no device).
  * "No call synchronises the device" (above) means hipDeviceSynchronize; the calls that wait for their own stream say so: the creates, psdr_hip_guiding_build,
  * psdr_hip_precond_solve (it reads its residuals), the *_counted renders, and a render that has to grow the scene's scratch (first call, or a larger one). */
 const char *psdr_hip_last_error(void);
@@ -834,6 +835,71 @@ int psdr_hip_chamfer_nearest(const float *x, int32_t n, const float *y, int32_t 
 int psdr_hip_chamfer_eval(const float *x, int32_t n, const float *y, int32_t m, const int32_t *index_xy, const float *dist2_xy, const int32_t *index_yx, const float *dist2_yx,
                           const int32_t *x_begin, const int32_t *x_list, const int32_t *y_begin, const int32_t *y_list, const float *weights, int32_t squared,
                           double *partial, float *out, float *grad_x, float *grad_y, void *stream);
+
+/* THE POINT-TO-MESH DISTANCE - FOR EVERY POINT THE NEAREST FACE, FOR EVERY FACE THE NEAREST POINT, VALUE AND BOTH GRADIENTS (csrc/hip/pointmesh.hip; psdr_jit_amd/pointmesh.py;
+ * DESIGN.md section 7l).  What a user fitting a mesh to a scan needs: the distance from the scan's points to the closed triangles themselves, not to a frozen sample of them
+ * (pytorch3d's point_mesh_face_distance).  Stateless entry points like the chamfer ones: device pointers, work arrays from the caller, plain launches on `stream`, no host
+ * synchronisation, no float atomics: the same input gives the same bits.  Added under ABI 16: nothing existing changed.
+ *
+ * The definition.  p: float32 [N, 3] points; v: float32 [n, 3] vertices; faces: int32 [F, 3], ids in [0, n), no id repeated in a face; 1 <= N, F, n <= 2^26, all values finite.
+ *   The pair function cp(p; a, b, c): the closest point of the closed triangle (a, b, c) to p as barycentrics (1 - s - t, s, t), by the region cascade of Ericson, Real-Time
+ *   Collision Detection, section 5.1.5.  With ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c (componentwise) and x.y = (x0 y0 + x1 y1) + x2 y2:
+ *       d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp, d5 = ab.cp, d6 = ac.cp,  vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4
+ *   the first test that holds decides:
+ *       1. d1 <= 0 && d2 <= 0                              vertex a   s = 0, t = 0
+ *       2. d3 >= 0 && d4 <= d3                             vertex b   s = 1, t = 0
+ *       3. vc <= 0 && d1 >= 0 && d3 <= 0                   edge ab    s = d1 / (d1 - d3), t = 0
+ *       4. d6 >= 0 && d5 <= d6                             vertex c   s = 0, t = 1
+ *       5. vb <= 0 && d2 >= 0 && d6 <= 0                   edge ac    s = 0, t = d2 / (d2 - d6)
+ *       6. va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0         edge bc    t = (d4 - d3) / ((d4 - d3) + (d5 - d6)), s = 1 - t
+ *       7. otherwise                                       interior   s = vb / ((va + vb) + vc), t = vc / ((va + vb) + vc)
+ *   A quotient whose denominator is 0 is 0: a zero-length edge and a zero-area face give a finite point of the triangle, never a NaN.  Then
+ *       e = ap - (s ab + t ac)  (componentwise: two products, their sum, one difference),   dist2(p, f) = (e0 e0 + e1 e1) + e2 e2 >= +0
+ *   the difference form of the chamfer section: nothing is expanded, nothing cancels where the point is near the face.  Every operation written here is one float32 operation
+ *   with one rounding, in this order, nothing contracted; a comparison with a NaN is false.  The barycentrics reported are ((1 - s) - t, s, t).
+ *   nearest   D_p[i] = min_f dist2(p_i, f), a(i) = the lowest f among the minima of this float32 dist2;  D_f[f] = min_i dist2(p_i, f), b(f) = the lowest i likewise.  The
+ *             lexicographic minimum over (dist2, index) does not depend on how a scan is split or merged.  On a closed mesh a point nearest a shared edge or vertex is equally
+ *             near several faces: a(i) is defined by THIS float32 dist2 and need not be the face another precision picks; the closest point itself is unique.  With non-finite
+ *             inputs the values are unspecified, but every index lies in range.
+ *   loss      = w_pf (1 / N) sum_i rho(D_p[i]) + w_fp (1 / F) sum_f rho(D_f[f]), weights[2] = (w_pf, w_fp);  rho(s) = s (squared != 0) or sqrt(s) (squared == 0), whose
+ *             derivative at s = 0 is defined as 0.  A term whose weight is 0 is not evaluated: its reported value is exactly 0 and the gradients are the other term's bit for
+ *             bit.  The terms are added in this order.
+ *   gradient  the indices and the barycentrics are constants.  For the squared distance this is not a convention but the exact derivative: dist2 is the minimum over the
+ *             triangle's points of |p - q|^2, and by the envelope theorem the derivative of a minimum with respect to a parameter is the partial derivative at the minimiser.
+ *             For a chosen pair (i, f) with r = p_i - q, q = sum_c bary_c v_faces[f][c] - evaluated as the pair function's e, which is that difference without the
+ *             cancellation - p_i receives +k r and v_faces[f][c] receives -k bary_c r, each product k r first, then times bary_c;  k(s) = 2 w / count (squared) or
+ *             (w / count) / sqrt(s), 0 at s = 0 (not squared), w / count and 2 w / count rounded from double, s the pair's dist2.  The orders of addition:
+ *               p_i       its own pair (i, a(i)), then the sum, started at 0 and added once, over the faces with b(f) = i in ascending f
+ *               face f    a [3, 3] corner record: its own pair (b(f), f), then the sum, started at 0 and added once, over the points with a(i) = f in ascending i
+ *               vertex    the corner records of the corners that name it, in ascending (face, corner) order (vc_begin / vc_corner below), added from 0
+ *
+ * psdr_hip_pointmesh_plan(n_queries, n_candidates) -> (tile, queries_per_lane, slices, slice_len): how either scan is split, a pure function, callable without a GPU.  A
+ * workgroup of 256 lanes holds 256 queries_per_lane queries; slice s holds the candidates [s slice_len, min(count, (s + 1) slice_len)), slice_len a multiple of tile, no slice
+ * empty; the grid is ceil(n_queries / (256 queries_per_lane)) x slices.  tile = 256; queries_per_lane = 2 for n_queries > 1024, else 1; slices = the fewest that bring the grid
+ * to 2048 workgroups, at most one per tile.  The result of a scan does not depend on the plan.
+ * psdr_hip_pointmesh_nearest(p, N, v, n, faces, F, direction, records, keys, index, bary, dist2): one scan.  direction 0: the points are the queries - index int32 [N] = a, bary
+ * float32 [N, 3], dist2 float32 [N] = D_p; direction 1: the faces are - index [F] = b, bary [F, 3], dist2 [F] = D_f.  keys: uint64 work array with one entry per query (the minimum
+ * of (float bits of dist2) << 32 | index, merged over the slices by an integer atomic minimum, after a clear to all ones on `stream`).  records: float32 [F, 16] work array,
+ * direction 0 only (NULL otherwise): per face (a, ab, ac, b, c, 0), written once per call by a small kernel and staged through LDS by the scan; nothing else is precomputed.
+ * The scan carries dist2 only; the barycentrics are those of the winning pair, evaluated once more per query by the same pair function.  Vertex ids read from `faces` are
+ * clamped into [0, n).
+ * psdr_hip_pointmesh_eval(p, N, v, n, faces, F, face_of_point, bary_p, dist2_p, point_of_face, bary_f, dist2_f, p_begin [N + 1], p_list [F], f_begin [F + 1], f_list [N],
+ * vc_begin [n + 1], vc_corner [3 F], weights, squared, partial, corners, out, grad_p, grad_v): out[3] (device) = (loss, mean_i rho(D_p), mean_f rho(D_f)); grad_p [N, 3], grad_v
+ * [n, 3] (device; both NULL for a value-only call, which gives the same out bits).  p_begin / p_list: the inverted index of point_of_face - p_list holds the f in ascending
+ * (point_of_face[f], f) order (a stable sort), p_begin[i] the position of point i's first entry; f_begin / f_list the same for face_of_point.  vc_begin / vc_corner: per vertex
+ * the corners 3 f + c that name it, ascending - the mesh's topology, from the host once per mesh.  All three are the caller's duty; the kernels clamp everything they read
+ * from an index into range.  partial: double work array of ceil(N / 256) + ceil(F / 256) entries (the sums of rho are added in double in a fixed order, each mean is rounded to
+ * float32 once); corners: float32 [F, 9] work array, the corner records.  The arrays of a direction whose weight is 0, and the inverted indices, vc_* and corners of a
+ * value-only call, are not read and may be NULL.  One launch each for the points, the faces and the vertices, and one that adds the per-workgroup sums.
+ * All three are refused with psdr_hip_last_error text before any device call for a count outside [1, 2^26], a direction other than 0 or 1, a NULL array that would be read or
+ * written, a weight that is negative or not finite, one gradient without the other, and a gradient that aliases an input or the other gradient. */
+int psdr_hip_pointmesh_plan(int32_t n_queries, int32_t n_candidates, int32_t *tile, int32_t *queries_per_lane, int32_t *slices, int32_t *slice_len);
+int psdr_hip_pointmesh_nearest(const float *p, int32_t n_points, const float *v, int32_t n_vertices, const int32_t *faces, int32_t n_faces, int32_t direction,
+                               float *records, uint64_t *keys, int32_t *index, float *bary, float *dist2, void *stream);
+int psdr_hip_pointmesh_eval(const float *p, int32_t n_points, const float *v, int32_t n_vertices, const int32_t *faces, int32_t n_faces,
+                            const int32_t *face_of_point, const float *bary_p, const float *dist2_p, const int32_t *point_of_face, const float *bary_f, const float *dist2_f,
+                            const int32_t *p_begin, const int32_t *p_list, const int32_t *f_begin, const int32_t *f_list, const int32_t *vc_begin, const int32_t *vc_corner,
+                            const float *weights, int32_t squared, double *partial, float *corners, float *out, float *grad_p, float *grad_v, void *stream);
 
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);

@@ -1478,3 +1478,5 @@ from .ssim import SSIMLoss, gaussian_window  # noqa: E402,F401
 from .meshreg import MeshRegularizer, mesh_topology  # noqa: E402,F401
 # the Chamfer distance between two point sets (exact nearest neighbours, value and both gradients) and points sampled from a mesh's surface (chamfer.py; kernels: csrc/hip/chamfer.hip)
 from .chamfer import ChamferDistance, SurfaceSampler, nearest_points, launch_plan, sample_surface, sampling_csr  # noqa: E402,F401
+# the point-to-mesh distance: for every point the nearest face, for every face the nearest point, value and both gradients (pointmesh.py; kernels: csrc/hip/pointmesh.hip)
+from .pointmesh import PointMeshDistance, closest_points_on_mesh, launch_plan_pm  # noqa: E402,F401
