@@ -265,7 +265,8 @@ typedef struct psdr_counters {
  *      by the caller; the same holds for a meshreg handle (it owns the contribution buffers and partial sums of its eval).  subdiv handles are read-only after the create and
  *      may be applied from any number of streams.  The chamfer entry points (psdr_hip_chamfer_nearest, psdr_hip_chamfer_eval) have no handle and no create: their work
  *      arrays (keys, partial) are the caller's, one set per call in flight, and psdr_hip_chamfer_plan touches no device.  The same holds for the point-to-mesh entry points
- *      (psdr_hip_pointmesh_nearest, psdr_hip_pointmesh_eval: records, keys, corners and partial are the caller's; psdr_hip_pointmesh_plan touches no device).
+ *      (psdr_hip_pointmesh_nearest, psdr_hip_pointmesh_eval: records, keys, corners and partial are the caller's; psdr_hip_pointmesh_plan touches no device) and for the
+ *      signed-distance entry points (psdr_hip_sdf_winding, psdr_hip_sdf_grad: records, partial and corners are the caller's).
  * "No call synchronises the device" (above) means hipDeviceSynchronize; the calls that wait for their own stream say so: the creates, psdr_hip_guiding_build,
  * psdr_hip_precond_solve (it reads its residuals), the *_counted renders, and a render that has to grow the scene's scratch (first call, or a larger one). */
 const char *psdr_hip_last_error(void);
@@ -900,6 +901,54 @@ int psdr_hip_pointmesh_eval(const float *p, int32_t n_points, const float *v, in
                             const int32_t *face_of_point, const float *bary_p, const float *dist2_p, const int32_t *point_of_face, const float *bary_f, const float *dist2_f,
                             const int32_t *p_begin, const int32_t *p_list, const int32_t *f_begin, const int32_t *f_list, const int32_t *vc_begin, const int32_t *vc_corner,
                             const float *weights, int32_t squared, double *partial, float *corners, float *out, float *grad_p, float *grad_v, void *stream);
+
+/* THE SIGNED DISTANCE - FOR EVERY POINT THE GENERALIZED WINDING NUMBER OF A MESH, THE DISTANCE SIGNED BY IT, AND THE VECTOR-JACOBIAN PRODUCT OF THAT DISTANCE (csrc/hip/sdf.hip;
+ * psdr_jit_amd/sdf.py).  What a penetration penalty, a containment or free-space constraint and supervision against signed distance samples need: which
+ * side of the surface a point lies on.  The sign is that of the generalized winding number (Jacobson, Kavan, Sorkine-Hornung 2013): the sum of the signed solid angles of all
+ * faces, 1 inside and 0 outside a closed mesh, degrading smoothly at holes where a normal-based sign is wrong.  Stateless entry points like the point-to-mesh ones: device
+ * pointers, work arrays from the caller, plain launches on `stream`, no host synchronisation, no float atomics: the same input gives the same bits.  Added under ABI 16: nothing
+ * existing changed.
+ *
+ * The definition.  p, v, faces, N, n, F as in the point-to-mesh section.  For a point p and a face with the corners A, B, C in the file's vertex order, with
+ * x.y = (x0 y0 + x1 y1) + x2 y2 and x X y = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0):
+ *       a = A - p, b = B - p, c = C - p (componentwise),   la = sqrt(a.a), lb = sqrt(b.b), lc = sqrt(c.c)
+ *       Nm = a . (b X c),   Dn = ((la lb) lc + (a.b) lc) + ((b.c) la + (c.a) lb)
+ *       theta(p, f) = 0 if Nm == 0, else atan2(Nm, Dn)
+ *   theta is half the signed solid angle of the face seen from p (Van Oosterom & Strackee 1983), in (-pi, pi].  The Nm == 0 branch is the principal value: a point in the
+ *   face's plane, a point on a vertex and a face of zero area contribute 0, and no pair of finite inputs produces a NaN.  Every operation written here is one float32 operation
+ *   with one rounding, in this order, nothing contracted, the square roots correctly rounded; atan2 is the device library's float32 atan2f.
+ *   winding   w[i] = (1 / (2 pi)) sum_f theta(p_i, f).  The order of summation: the faces are split into the slices of psdr_hip_pointmesh_plan(N, F) - there is no second plan -
+ *             a lane adds the thetas of a slice in ascending f into a double, started at 0, and rounds the slice's sum to float32 (partial[slice][i]); the slices are added in
+ *             ascending order from 0 in double, the sum is multiplied by the double nearest 1 / (2 pi) and rounded to float32 once.  So the last bits of w depend on the plan -
+ *             the one place where this operator differs from the point-to-mesh distance, whose results do not - and the plan is a pure function of (N, F): the same input gives
+ *             the same bits.
+ *   sign      inside[i] = (orientation w[i] > 1 / 2), orientation = +1 where the faces wind counter-clockwise seen from outside, -1 for the other winding.
+ *   distance  s[i] = -sqrt(D_p[i]) if inside[i], else +sqrt(D_p[i]) (one correctly rounded square root);  D_p, a(i) and the barycentrics are exactly those of
+ *             psdr_hip_pointmesh_nearest, direction 0, which the caller runs as it is.
+ *   gradient  of s only; indices, barycentrics and the sign are constants.  With r_i the point-to-mesh pair function's e of the pair (i, a(i)) - p_i - q_i without the
+ *             cancellation, q_i = bary_i . v[faces[a(i)]] - ds_i / dp_i = r_i / s_i and ds_i / dv[faces[a(i)][c]] = -bary_ic r_i / s_i, both 0 where s_i == 0 (D_p[i] = 0), as
+ *             rho' is in the point-to-mesh section.  For an incoming g [N]: k_i = g_i / s_i (one division; 0 where s_i == 0), p_i receives k_i r_i, corner c of a(i) receives
+ *             -((k_i r_i) bary_ic).  The orders of addition: a face's [3, 3] corner record is the sum, started at 0, over the points with a(i) = f in ascending i; a vertex adds
+ *             the corner records of the corners that name it in ascending (face, corner) order (vc_begin / vc_corner), from 0.
+ *             w and inside carry no gradient.  For a closed mesh the winding number is piecewise constant in the point and in the vertices: its analytic vertex gradient cancels
+ *             to 1e-17 in float64.  It is the sign, not a differentiable quantity; the differentiable operator is the signed distance.
+ *
+ * psdr_hip_sdf_winding(p, N, v, n, faces, F, records, partial, dist2_or_null, orientation, w, sdf_or_null): w float32 [N]; with dist2 float32 [N] (D_p) also sdf float32 [N] = s,
+ * both given or both NULL.  records: float32 [F, 12] work array, per face (A, B, C, 0, 0, 0), vertex ids clamped into [0, n), written once per call by a small kernel and staged
+ * through LDS by the scan, which keeps the plan's queries per lane in registers; its grid is query blocks x slices.  partial: float32 [slices, N] work array, slices from
+ * psdr_hip_pointmesh_plan(N, F); every entry is written by one lane, nothing is cleared.  One launch each for the records, the scan and the merge.  Nothing of size N x F exists.
+ * psdr_hip_sdf_grad(p, N, v, n, faces, F, face, bary, sdf, g, f_begin [F + 1], f_list [N], vc_begin [n + 1], vc_corner [3 F], corners, grad_p, grad_v): the vector-Jacobian
+ * product of s for the incoming g float32 [N]: grad_p [N, 3], grad_v [n, 3].  face int32 [N], bary float32 [N, 3]: a and the barycentrics from psdr_hip_pointmesh_nearest; sdf: s
+ * from psdr_hip_sdf_winding.  f_begin / f_list: the inverted index of face (a stable sort); vc_begin / vc_corner: the mesh's vertex-to-corner index, as in
+ * psdr_hip_pointmesh_eval; corners: float32 [F, 9] work array.  One launch each for the points, the faces and the vertices; the kernels clamp everything they read from an index
+ * into range.
+ * Both are refused with psdr_hip_last_error text before any device call for a count outside [1, 2^26], an orientation other than +1 or -1, a NULL array that would be read or
+ * written, dist2 without sdf or sdf without dist2, and a gradient that aliases an input or the other gradient. */
+int psdr_hip_sdf_winding(const float *p, int32_t n_points, const float *v, int32_t n_vertices, const int32_t *faces, int32_t n_faces, float *records, float *partial,
+                         const float *dist2, int32_t orientation, float *w, float *sdf, void *stream);
+int psdr_hip_sdf_grad(const float *p, int32_t n_points, const float *v, int32_t n_vertices, const int32_t *faces, int32_t n_faces, const int32_t *face, const float *bary,
+                      const float *sdf, const float *g, const int32_t *f_begin, const int32_t *f_list, const int32_t *vc_begin, const int32_t *vc_corner, float *corners,
+                      float *grad_p, float *grad_v, void *stream);
 
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);

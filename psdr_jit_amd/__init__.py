@@ -1480,3 +1480,5 @@ from .meshreg import MeshRegularizer, mesh_topology  # noqa: E402,F401
 from .chamfer import ChamferDistance, SurfaceSampler, nearest_points, launch_plan, sample_surface, sampling_csr  # noqa: E402,F401
 # the point-to-mesh distance: for every point the nearest face, for every face the nearest point, value and both gradients (pointmesh.py; kernels: csrc/hip/pointmesh.hip)
 from .pointmesh import PointMeshDistance, closest_points_on_mesh, launch_plan_pm  # noqa: E402,F401
+# the signed distance to a mesh: the generalized winding number for the sign, the signed distance and its gradients (sdf.py; kernels: csrc/hip/sdf.hip)
+from .sdf import SignedDistance, SignedDistanceResult, signed_distance, winding_number  # noqa: E402,F401

@@ -21,6 +21,7 @@ SYMBOLS = [
     "psdr_hip_meshreg_create", "psdr_hip_meshreg_eval", "psdr_hip_meshreg_destroy",
     "psdr_hip_chamfer_plan", "psdr_hip_chamfer_nearest", "psdr_hip_chamfer_eval",
     "psdr_hip_pointmesh_plan", "psdr_hip_pointmesh_nearest", "psdr_hip_pointmesh_eval",
+    "psdr_hip_sdf_winding", "psdr_hip_sdf_grad",
 ]
 
 
@@ -133,6 +134,8 @@ def lib():
         L.psdr_hip_pointmesh_plan.argtypes = [C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 4
         L.psdr_hip_pointmesh_nearest.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
         L.psdr_hip_pointmesh_eval.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 12 + [C.POINTER(C.c_float), C.c_int32] + [C.c_void_p] * 6
+        L.psdr_hip_sdf_winding.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3
+        L.psdr_hip_sdf_grad.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 12
         _lib = L
     return _lib
 
