@@ -266,7 +266,9 @@ typedef struct psdr_counters {
  *      may be applied from any number of streams.  The chamfer entry points (psdr_hip_chamfer_nearest, psdr_hip_chamfer_eval) have no handle and no create: their work
  *      arrays (keys, partial) are the caller's, one set per call in flight, and psdr_hip_chamfer_plan touches no device.  The same holds for the point-to-mesh entry points
  *      (psdr_hip_pointmesh_nearest, psdr_hip_pointmesh_eval: records, keys, corners and partial are the caller's; psdr_hip_pointmesh_plan touches no device) and for the
- *      signed-distance entry points (psdr_hip_sdf_winding, psdr_hip_sdf_grad: records, partial and corners are the caller's).
+ *      signed-distance entry points (psdr_hip_sdf_winding, psdr_hip_sdf_grad: records, partial and corners are the caller's), and for the isosurface entry points
+ *      (psdr_hip_mtet_count, psdr_hip_mtet_emit, psdr_hip_mtet_vertices, psdr_hip_mtet_vertices_adj: mask, base, the cell arrays, scratch and totals are the caller's and
+ *      none of them synchronises - the caller reads totals after waiting for `stream` itself; psdr_hip_mtet_plan touches no device).
  * "No call synchronises the device" (above) means hipDeviceSynchronize; the calls that wait for their own stream say so: the creates, psdr_hip_guiding_build,
  * psdr_hip_precond_solve (it reads its residuals), the *_counted renders, and a render that has to grow the scene's scratch (first call, or a larger one). */
 const char *psdr_hip_last_error(void);
@@ -949,6 +951,60 @@ int psdr_hip_sdf_winding(const float *p, int32_t n_points, const float *v, int32
 int psdr_hip_sdf_grad(const float *p, int32_t n_points, const float *v, int32_t n_vertices, const int32_t *faces, int32_t n_faces, const int32_t *face, const float *bary,
                       const float *sdf, const float *g, const int32_t *f_begin, const int32_t *f_list, const int32_t *vc_begin, const int32_t *vc_corner, float *corners,
                       float *grad_p, float *grad_v, void *stream);
+
+/* THE ISOSURFACE - MARCHING TETRAHEDRA: FROM A SIGNED DISTANCE ON A LATTICE TO A TRIANGLE MESH, THE POSITIONS OF ITS VERTICES AND THEIR VECTOR-JACOBIAN PRODUCT (csrc/hip/mtet.hip;
+ * psdr_jit_amd/mtet.py).  The way back from the signed-distance section: that one makes a lattice of signed distances from any mesh, this one makes a
+ * mesh from any lattice, so that an optimisation can change the topology (DMTet, Shen et al. 2021: optimise the values, extract at every step).  Stateless entry points: device
+ * pointers, work arrays from the caller, plain launches on `stream`, no host synchronisation, no float atomics: the same input gives the same bits.  Added under ABI 16: nothing
+ * existing changed.
+ *
+ * The definition.
+ *   lattice     shape = (nx, ny, nz) vertices, every extent at least 2; vertex id u = x + nx (y + ny z); Nv = nx ny nz <= 2^24, so that every count and every 3 F offset fits an
+ *               int32; cell id cx + (nx - 1) (cy + (ny - 1) cz).  sdf float32 [Nv], pos float32 [Nv, 3]; pos may be deformed (DMTet moves the lattice).
+ *   tetrahedra  Kuhn's split, six per cell.  For the axis permutations (a, b, c) in the order xyz, xzy, yxz, yzx, zxy, zyx tet k has the corners q0 = the cell's low corner,
+ *               q1 = q0 + e_a, q2 = q1 + e_b, q3 = q2 + e_c; tet id 6 cell + k.  The split is translation invariant: the face diagonals of neighbouring cells agree.
+ *   edge slots  every edge of every tet is one of seven classes anchored at its low end, with the offsets d_0..6 = (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1); slot
+ *               7 u + c is the edge from u to u + d_c and exists where that end lies in the lattice.
+ *   inside      inside(u) = sdf[u] < 0: a zero is outside and so is a NaN.  A slot crosses where its two ends differ.  The mesh's vertices are the crossing slots in ascending
+ *               slot order; edges int32 [V, 2] holds (a, b), a the anchor.
+ *   position    t = s_a / (s_a - s_b), always from the anchor (the two values have opposite signs or one is zero: nothing cancels), p = p_a + t (p_b - p_a) per component, every
+ *               operation one float32 rounding.  s_b = 0 gives t = 1, p = p_b up to the rounding of that formula; several slots may then coincide and faces of zero area
+ *               result: defined, not an error.  With an infinite or NaN end the topology is as above and the position is unspecified.
+ *   faces       a tet with 0 or 4 inside corners gives none.  One inside corner i - or, the mirror case, one outside corner i - gives the triangle of the slots e_ij, e_ik, e_il
+ *               to the other three corners j < k < l in tet-local order.  Two inside corners i < j with the outside corners k < l give the quad e_ik, e_il, e_jl, e_jk, split along
+ *               e_ik - e_jl into (e_ik, e_il, e_jl) and (e_ik, e_jl, e_jk).  Each triangle is then wound counter-clockwise seen from the outside (sdf >= 0) corners on a regular
+ *               lattice of positive spacing - the signed distance's orientation = +1 - by exchanging its last two slots where needed.  The winding is a function of (k, mask)
+ *               alone, a table, never a test on pos: a deformed lattice keeps the topological orientation.  Faces come in ascending tet id, the two of a quad in the order above.
+ *   gradient    with the topology held constant.  For the slot (a, b), d = p_b - p_a, den = s_a - s_b, and an incoming g (the slot's row of g [V, 3]):
+ *               w = ((g0 d0 + g1 d1) + g2 d2) / (den den);  s_a receives (-s_b) w, s_b receives s_a w, p_a receives (1 - t) g, p_b receives t g (dp/ds_a = -s_b d / den^2, dp/ds_b =
+ *               s_a d / den^2, dp/dp_a = 1 - t, dp/dp_b = t).  A lattice vertex adds, from 0, its own seven slots in ascending class and then the seven slots it is the far end of
+ *               (anchors u - d_c) in ascending class: fourteen fixed look-ups, no sort, no inverted index, no float atomics.
+ *
+ * The index of slot 7 u + c among the mesh's vertices is base[u] + popcount(mask[u] & ((1 << c) - 1)): mask uint8 [Nv] holds the seven crossing bits of a lattice vertex and
+ * base int32 [Nv] the exclusive scan of their popcounts.  These five bytes per lattice vertex are the whole topology state a later call needs (a slot table would take 28).
+ * The scans are reduce / scan of the workgroup sums / scatter in plain launches over tiles of 256 entries - no workgroup waits for another - so Nv <= 256^3 needs at most two
+ * passes over workgroup sums.  psdr_hip_mtet_plan(nx, ny, nz) -> (tile = 256, vertex_blocks = ceil(Nv / tile), cell_blocks = ceil(cells / tile), vertex_passes, cell_passes:
+ * 1 where the blocks fit one tile, else 2, scratch_ints): a pure function, callable without a GPU.
+ * psdr_hip_mtet_count(sdf, nx, ny, nz, mask, base, cell_faces, cell_base, scratch, totals): mask and base as above; cell_faces uint8 [cells] the faces of a cell's six tets
+ * (0 .. 12), cell_base int32 [cells] their exclusive scan (one lane emits a cell's tets in ascending k, so one offset per cell serves and nothing of size 6 cells exists);
+ * scratch int32 [scratch_ints]; totals int32 [2] (device) = (V, F).  Nothing is cleared, every entry is written by one lane.
+ * psdr_hip_mtet_emit(sdf, nx, ny, nz, mask, base, cell_base, num_vertices, num_faces, edges, edge_rows, faces, face_rows): edges int32 [V, 2], faces int32 [F, 3], two launches.
+ * num_vertices and num_faces are the totals the caller read, edge_rows and face_rows the rows of the arrays it gives; sdf must be the one the count saw.  The kernels write no
+ * row beyond those given.  psdr_hip_mtet_vertices(sdf, pos, nx, ny, nz, edges, num_vertices, v): v float32 [V, 3], one launch; ids read from edges are clamped into [0, Nv).
+ * psdr_hip_mtet_vertices_adj(sdf, pos, nx, ny, nz, mask, base, num_vertices, g, grad_sdf, grad_pos): the vector-Jacobian product for g float32 [V, 3]: grad_sdf [Nv], grad_pos
+ * [Nv, 3], one launch, every entry written (0 where no slot crosses).
+ * All are refused with psdr_hip_last_error text before any device call for a NULL array, an extent below 2, more than 2^24 lattice vertices, num_vertices outside [1, 7 Nv] or
+ * num_faces outside [1, 12 cells] (a lattice without a crossing has nothing to emit: the caller skips the call), totals that disagree with the rows given to the emit, and
+ * outputs that alias an input or each other. */
+int psdr_hip_mtet_plan(int32_t nx, int32_t ny, int32_t nz, int32_t *tile, int32_t *vertex_blocks, int32_t *cell_blocks, int32_t *vertex_passes, int32_t *cell_passes,
+                       int32_t *scratch_ints);
+int psdr_hip_mtet_count(const float *sdf, int32_t nx, int32_t ny, int32_t nz, uint8_t *mask, int32_t *base, uint8_t *cell_faces, int32_t *cell_base, int32_t *scratch,
+                        int32_t *totals, void *stream);
+int psdr_hip_mtet_emit(const float *sdf, int32_t nx, int32_t ny, int32_t nz, const uint8_t *mask, const int32_t *base, const int32_t *cell_base, int32_t num_vertices,
+                       int32_t num_faces, int32_t *edges, int32_t edge_rows, int32_t *faces, int32_t face_rows, void *stream);
+int psdr_hip_mtet_vertices(const float *sdf, const float *pos, int32_t nx, int32_t ny, int32_t nz, const int32_t *edges, int32_t num_vertices, float *v, void *stream);
+int psdr_hip_mtet_vertices_adj(const float *sdf, const float *pos, int32_t nx, int32_t ny, int32_t nz, const uint8_t *mask, const int32_t *base, int32_t num_vertices,
+                               const float *g, float *grad_sdf, float *grad_pos, void *stream);
 
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);

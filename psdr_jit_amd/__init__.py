@@ -1482,3 +1482,5 @@ from .chamfer import ChamferDistance, SurfaceSampler, nearest_points, launch_pla
 from .pointmesh import PointMeshDistance, closest_points_on_mesh, launch_plan_pm  # noqa: E402,F401
 # the signed distance to a mesh: the generalized winding number for the sign, the signed distance and its gradients (sdf.py; kernels: csrc/hip/sdf.hip)
 from .sdf import SignedDistance, SignedDistanceResult, signed_distance, winding_number  # noqa: E402,F401
+# the way back: marching tetrahedra, from a signed distance on a lattice to a mesh, differentiable in the values and the positions (mtet.py; kernels: csrc/hip/mtet.hip)
+from .mtet import MarchingTetrahedra, MtetTopology, lattice_points, launch_plan_mt  # noqa: E402,F401

@@ -22,6 +22,7 @@ SYMBOLS = [
     "psdr_hip_chamfer_plan", "psdr_hip_chamfer_nearest", "psdr_hip_chamfer_eval",
     "psdr_hip_pointmesh_plan", "psdr_hip_pointmesh_nearest", "psdr_hip_pointmesh_eval",
     "psdr_hip_sdf_winding", "psdr_hip_sdf_grad",
+    "psdr_hip_mtet_plan", "psdr_hip_mtet_count", "psdr_hip_mtet_emit", "psdr_hip_mtet_vertices", "psdr_hip_mtet_vertices_adj",
 ]
 
 
@@ -136,6 +137,11 @@ def lib():
         L.psdr_hip_pointmesh_eval.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 12 + [C.POINTER(C.c_float), C.c_int32] + [C.c_void_p] * 6
         L.psdr_hip_sdf_winding.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3
         L.psdr_hip_sdf_grad.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 12
+        L.psdr_hip_mtet_plan.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 6
+        L.psdr_hip_mtet_count.argtypes = [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 7
+        L.psdr_hip_mtet_emit.argtypes = [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.psdr_hip_mtet_vertices.argtypes = [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.psdr_hip_mtet_vertices_adj.argtypes = [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_void_p] * 2 + [C.c_int32] + [C.c_void_p] * 4
         _lib = L
     return _lib
 
