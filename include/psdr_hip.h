@@ -268,7 +268,8 @@ typedef struct psdr_counters {
  *      (psdr_hip_pointmesh_nearest, psdr_hip_pointmesh_eval: records, keys, corners and partial are the caller's; psdr_hip_pointmesh_plan touches no device) and for the
  *      signed-distance entry points (psdr_hip_sdf_winding, psdr_hip_sdf_grad: records, partial and corners are the caller's), and for the isosurface entry points
  *      (psdr_hip_mtet_count, psdr_hip_mtet_emit, psdr_hip_mtet_vertices, psdr_hip_mtet_vertices_adj: mask, base, the cell arrays, scratch and totals are the caller's and
- *      none of them synchronises - the caller reads totals after waiting for `stream` itself; psdr_hip_mtet_plan touches no device).
+ *      none of them synchronises - the caller reads totals after waiting for `stream` itself; psdr_hip_mtet_plan touches no device), and for the lattice regularisers
+ *      (psdr_hip_latreg_eval: scratch, out, crossings and grad are the caller's; psdr_hip_latreg_plan touches no device).
  * "No call synchronises the device" (above) means hipDeviceSynchronize; the calls that wait for their own stream say so: the creates, psdr_hip_guiding_build,
  * psdr_hip_precond_solve (it reads its residuals), the *_counted renders, and a render that has to grow the scene's scratch (first call, or a larger one). */
 const char *psdr_hip_last_error(void);
@@ -1005,6 +1006,47 @@ int psdr_hip_mtet_emit(const float *sdf, int32_t nx, int32_t ny, int32_t nz, con
 int psdr_hip_mtet_vertices(const float *sdf, const float *pos, int32_t nx, int32_t ny, int32_t nz, const int32_t *edges, int32_t num_vertices, float *v, void *stream);
 int psdr_hip_mtet_vertices_adj(const float *sdf, const float *pos, int32_t nx, int32_t ny, int32_t nz, const uint8_t *mask, const int32_t *base, int32_t num_vertices,
                                const float *g, float *grad_sdf, float *grad_pos, void *stream);
+
+/* THE LATTICE REGULARISERS - EIKONAL, LAPLACIAN, SIGN-CHANGE CROSS-ENTROPY OF A SIGNED DISTANCE ON A REGULAR LATTICE - VALUE AND GRADIENT IN ONE FUSED STENCIL (csrc/hip/latreg.hip;
+ * psdr_jit_amd/latreg.py).  The term of a DMTet / nvdiffrec-style loop that depends on the lattice alone: marching tetrahedra hands a gradient to the two
+ * ends of a crossing edge only, and nothing else keeps the rest of the field a distance, smooth and free of sign changes that no pixel sees.  What the mesh regularisers are to
+ * a fixed topology.  Stateless entry points: device pointers, work arrays from the caller, plain launches on `stream`, no host synchronisation, no atomics, every output entry
+ * written by one lane in a fixed order: the same input gives the same bits.  Added under ABI 16: nothing existing changed.
+ *
+ * The definition.
+ *   lattice     THE ISOSURFACE's: shape = (nx, ny, nz) vertices, every extent at least 2, vertex id u = x + nx (y + ny z), Nv = nx ny nz <= 2^24, inside(u) = sdf[u] < 0 (a zero
+ *               is outside), Nc = (nx - 1) (ny - 1) (nz - 1) cells.  The lattice is regular with the spacing h = (hx, hy, hz) > 0 (float64, host); a deformed lattice is out of
+ *               scope.  The divisions by the spacing are multiplications by the float32 roundings of 1 / (4 h_a) and 1 / h_a^2, formed in float64 on the host.
+ *   eikonal     = (1 / Nc) sum_cells e_c, e_c = (n - 1)^2, n = sqrt((g_x^2 + g_y^2) + g_z^2), g_x = ((((s100 - s000) + (s110 - s010)) + (s101 - s001)) + (s111 - s011)) / (4 hx)
+ *               the mean of the cell's four x-edge differences (s_xyz: the corner at offset (x, y, z) from the cell's low corner), g_y and g_z likewise with the differences
+ *               in the order of their low ends 000, 100, 001, 101 for y and 000, 100, 010, 110 for z (x: 000, 010, 001, 011).  A cell with n = 0 adds 1 and no gradient: defined,
+ *               not NaN.  d e_c / d s_corner = sum_a (+-) q_a, q_a = (2 (n - 1) (g_a / n)) / (4 h_a), + where the corner is the high end of axis a.
+ *   laplacian   = (1 / Nv) sum_u r_u^2, r_u = sum_a ((s_{u - e_a} - s_u) + (s_{u + e_a} - s_u)) / h_a^2 over the axes a, in the order x, y, z, along which u has both
+ *               neighbours (the two-difference form: it does not cancel as s_- - 2 s + s_+ does).  An axis of extent 2 contributes nowhere and a vertex on a boundary face
+ *               omits the axis normal to it, so a linear field gives exactly 0.  d / d s_u = (2 / Nv) sum_a (-2 r_u [u interior along a] + r_{u - e_a} [u - e_a interior along
+ *               a] + r_{u + e_a} [u + e_a interior along a]) / h_a^2.
+ *   sign        nvdiffrec's sdf_reg_loss over the lattice edges of the seven classes d in {0, 1}^3 \ {0} - THE ISOSURFACE's slots, the edges of Kuhn's tetrahedra.  For every edge
+ *               (a, b) with inside(a) != inside(b) add bce(k s_a, y_b) + bce(k s_b, y_a), y_j = 0 if inside(j) else 1, bce(x, y) = max(x, 0) - x y + log1p(exp(-|x|)), k =
+ *               sign_scale; sign = (1 / V) sum, V the number of crossing edges, held constant in the gradient; V = 0 gives 0 and a zero gradient.  Each of the two summands is
+ *               softplus(k |s|) of its own end (softplus(t) = t + log1p(exp(-t))), so the sum is the per-vertex form (1 / V) sum_u m_u softplus(k |s_u|), m_u the crossing edges
+ *               among u's fourteen - the form the kernels evaluate - with d / d s_u = (+-) (k / V) m_u / (1 + exp(-k |s_u|)), - where u is inside.
+ *   loss        = w_eik eikonal + w_lap laplacian + w_sign sign, weights = (w_eik, w_lap, w_sign); a term of weight 0 is not evaluated and reports 0 (crossings too reports 0
+ *               where w_sign = 0).  The gradient adds the evaluated terms in that order.
+ * sdf is expected to be finite; nothing checks it (a check would synchronise).  Every address is computed from lattice coordinates, never from data: a NaN gives NaNs, not an
+ * access out of range.
+ *
+ * psdr_hip_latreg_plan(nx, ny, nz) -> (tile_x, tile_y, tile_z: the vertices of a workgroup's tile, workgroups = the product of ceil(n_a / tile_a), scratch_floats = 4
+ * workgroups): a pure function, callable without a GPU.
+ * psdr_hip_latreg_eval(sdf, nx, ny, nz, spacing, weights, sign_scale, scratch, out, crossings, grad): sdf float32 [Nv]; spacing float64 [3] and weights float32 [3] on the host;
+ * scratch float32 [scratch_floats] the workgroups' partial sums; out float32 [4] = (loss, eikonal, laplacian, sign); crossings int32 [1] = V, which stays on the device: the
+ * gradient pass reads it there; grad float32 [Nv] = d loss / d sdf, or NULL for a value-only call.  Three launches (two without grad): the workgroups' partial sums in a fixed
+ * order, one finishing workgroup that adds them in float64, the gradient.  Every work array is the caller's, one set per call in flight; nothing is cleared, every entry is
+ * written.  Refused with psdr_hip_last_error text before any device call: a NULL required array, an extent below 2, more than 2^24 lattice vertices, a spacing that is not finite
+ * and positive (or whose 1 / (4 h) or 1 / h^2 is no positive float32), a weight or sign_scale that is negative or not finite, and scratch, out, crossings or grad that alias sdf
+ * or each other. */
+int psdr_hip_latreg_plan(int32_t nx, int32_t ny, int32_t nz, int32_t *tile_x, int32_t *tile_y, int32_t *tile_z, int32_t *workgroups, int32_t *scratch_floats);
+int psdr_hip_latreg_eval(const float *sdf, int32_t nx, int32_t ny, int32_t nz, const double *spacing, const float *weights, float sign_scale, float *scratch, float *out,
+                         int32_t *crossings, float *grad, void *stream);
 
 /* sampler building blocks (host side, bit-exact with the kernels): known-answer tests */
 uint64_t psdr_hip_tea64(uint64_t v0, uint64_t v1);

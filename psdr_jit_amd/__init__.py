@@ -1484,3 +1484,5 @@ from .pointmesh import PointMeshDistance, closest_points_on_mesh, launch_plan_pm
 from .sdf import SignedDistance, SignedDistanceResult, signed_distance, winding_number  # noqa: E402,F401
 # the way back: marching tetrahedra, from a signed distance on a lattice to a mesh, differentiable in the values and the positions (mtet.py; kernels: csrc/hip/mtet.hip)
 from .mtet import MarchingTetrahedra, MtetTopology, lattice_points, launch_plan_mt  # noqa: E402,F401
+# what keeps such a lattice a distance between the crossings: the Eikonal, Laplacian and sign-change regularisers of a lattice in one fused stencil (latreg.py; kernels: csrc/hip/latreg.hip)
+from .latreg import LatticeRegularizer, LatregPlan, lattice_spacing, launch_plan_lr  # noqa: E402,F401

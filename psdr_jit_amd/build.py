@@ -62,7 +62,12 @@ MESH_FIELD_UNITS = [
 MESH_EXTRACTION_UNITS = [
     ("mtet", "mtet.hip", "psdr_hip_mtet_*: isosurface extraction by marching tetrahedra, the crossing masks and face counts of a lattice with their scans, the emit of edges and faces, the vertex positions and their vector-Jacobian product", ()),
 ]
-OPERATOR_TUS = [(name, _H(src)[0], [], [os.path.join(ROOT, "include", "psdr_hip.h")] + _H(*headers) + BUILD_DEPS) for name, src, _what, headers in OPERATOR_UNITS + MESH_OPERATOR_UNITS + MESH_FIELD_UNITS + MESH_EXTRACTION_UNITS + MESH_DISTANCE_UNITS]      # hip_units()'s tuples
+# the operators on the lattice itself: the same row format, compiled between MESH_EXTRACTION_UNITS and MESH_DISTANCE_UNITS (a list of its own: tests/test_mtet_cpu.py pins
+# MESH_EXTRACTION_UNITS to its one row)
+LATTICE_OPERATOR_UNITS = [
+    ("latreg", "latreg.hip", "psdr_hip_latreg_*: the regularisers of a signed distance on a lattice (Eikonal, Laplacian, sign-change cross-entropy), value and gradient by one haloed LDS tile per workgroup in three launches", ()),
+]
+OPERATOR_TUS = [(name, _H(src)[0], [], [os.path.join(ROOT, "include", "psdr_hip.h")] + _H(*headers) + BUILD_DEPS) for name, src, _what, headers in OPERATOR_UNITS + MESH_OPERATOR_UNITS + MESH_FIELD_UNITS + MESH_EXTRACTION_UNITS + LATTICE_OPERATOR_UNITS + MESH_DISTANCE_UNITS]      # hip_units()'s tuples
 HIP_SRCS = [API_SRC, UNITS_SRC, SCENE_SRC] + [u[1] for u in OPERATOR_TUS]
 HIP_DEPS = sorted(set(API_DEPS + SCENE_DEPS + [d for u in OPERATOR_TUS for d in u[3]]))
 HOST_SRCS = [os.path.join(CSRC, "host", f) for f in ("scene_host.cpp", "bindings.cpp", "exr_piz.cpp")]
@@ -180,7 +185,7 @@ def _lint_units(hipcc, flags, units, objdir):
 def hip_units(flags=()):
     """the translation units of the library as (name, source, defines, dependencies): object api_<name>.o is compiled again when its source, one of
     its dependencies or a flag changed - the host unit `main` from api.hip, the kernel units `tu<k>` from render_units.hip (NOT from api.hip: an
-    edit of the host code leaves them alone), `scene` from scene_build.hip, and the rows of OPERATOR_UNITS, MESH_OPERATOR_UNITS, MESH_FIELD_UNITS, MESH_EXTRACTION_UNITS and MESH_DISTANCE_UNITS"""
+    edit of the host code leaves them alone), `scene` from scene_build.hip, and the rows of OPERATOR_UNITS, MESH_OPERATOR_UNITS, MESH_FIELD_UNITS, MESH_EXTRACTION_UNITS, LATTICE_OPERATOR_UNITS and MESH_DISTANCE_UNITS"""
     # development builds (-DPSDR_CLS_MASK=m: the host code launches the kernels of those scene classes only) skip the other classes' units
     mask = 15
     for f in flags:

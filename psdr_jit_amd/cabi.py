@@ -23,6 +23,7 @@ SYMBOLS = [
     "psdr_hip_pointmesh_plan", "psdr_hip_pointmesh_nearest", "psdr_hip_pointmesh_eval",
     "psdr_hip_sdf_winding", "psdr_hip_sdf_grad",
     "psdr_hip_mtet_plan", "psdr_hip_mtet_count", "psdr_hip_mtet_emit", "psdr_hip_mtet_vertices", "psdr_hip_mtet_vertices_adj",
+    "psdr_hip_latreg_plan", "psdr_hip_latreg_eval",
 ]
 
 
@@ -142,6 +143,8 @@ def lib():
         L.psdr_hip_mtet_emit.argtypes = [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.psdr_hip_mtet_vertices.argtypes = [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.psdr_hip_mtet_vertices_adj.argtypes = [C.c_void_p] * 2 + [C.c_int32] * 3 + [C.c_void_p] * 2 + [C.c_int32] + [C.c_void_p] * 4
+        L.psdr_hip_latreg_plan.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 5
+        L.psdr_hip_latreg_eval.argtypes = [C.c_void_p] + [C.c_int32] * 3 + [C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_float] + [C.c_void_p] * 5
         _lib = L
     return _lib
 
