@@ -32,42 +32,24 @@ COMMON_DEPS = DEVICE_DEPS + _H("scene_obj.h") + [os.path.join(ROOT, "include", "
 KERNEL_DEPS = DEVICE_DEPS + _H("render_kernels.h", "sampler.h", "shade.h", "edges.h", "paths.h", "group_start.h", "edge_switch.h", "adj_layout.h", "adjoint.h", "adjoint_mat.h", "isect_ad.h", "microfacet.h") + [os.path.join(CSRC, "common", "envmath.h")] + BUILD_DEPS
 API_DEPS = sorted(set(COMMON_DEPS + KERNEL_DEPS))      # the host unit launches the heavy kernels: it sees their header, they do not see api.hip
 SCENE_DEPS = COMMON_DEPS + _H("bvh.h", "filter.h", "cam_table.h", "blob_rows.h", "blob_layout.h") + [os.path.join(CSRC, "host", "hnum.h"), os.path.join(CSRC, "host", "edge_select.h")] + BUILD_DEPS
-# the stand-alone operators, one source file each: (unit, source, what it holds, the headers of csrc/hip it includes beside include/psdr_hip.h); compiled in this order
+# the stand-alone operators, one source file each: (unit, source, what it holds, the headers of csrc/hip it includes beside include/psdr_hip.h); compiled in this order.
+# A new operator is one more row; DESIGN.md section 7p says which shared header owns what
 OPERATOR_UNITS = [
-    ("precond", "precond.hip", "psdr_hip_precond_*: the Laplacian vertex preconditioner, its matrix-vector product and CG solver", ()),
-    ("adaptive", "adaptive.hip", "psdr_hip_adaptive_*: sample counts from a weight map (scan), the pixel list, the segment fold and its transpose", ()),
-    ("denoise", "denoise.hip", "psdr_hip_denoise_*: the edge-avoiding a-trous denoiser and its transpose, one LDS-tiled gather per level", ("atrous.h",)),
-    ("vdenoise", "vdenoise.hip", "psdr_hip_vdenoise_*: the variance-guided a-trous denoiser, its recorded (frozen) operator and that operator's transpose", ("atrous.h",)),
-    ("subdiv", "subdiv.hip", "psdr_hip_subdiv_*: one level of Loop / midpoint subdivision as a sparse operator (CSR from the host) and its transpose", ()),
-    ("msloss", "msloss.hip", "psdr_hip_msloss_*: the multi-scale image loss over a residual pyramid, value and gradient in three launches", ()),
-    ("ssim", "ssim.hip", "psdr_hip_ssim_*: the SSIM loss 1 - mean structural similarity under a Gaussian window, value and image gradient in three launches", ()),
+    ("precond", "precond.hip", "psdr_hip_precond_*: the Laplacian vertex preconditioner, its matrix-vector product and CG solver", ("op_common.h",)),
+    ("adaptive", "adaptive.hip", "psdr_hip_adaptive_*: sample counts from a weight map (scan), the pixel list, the segment fold and its transpose", ("op_common.h",)),
+    ("denoise", "denoise.hip", "psdr_hip_denoise_*: the edge-avoiding a-trous denoiser and its transpose, one LDS-tiled gather per level", ("atrous.h", "op_common.h")),
+    ("vdenoise", "vdenoise.hip", "psdr_hip_vdenoise_*: the variance-guided a-trous denoiser, its recorded (frozen) operator and that operator's transpose", ("atrous.h", "op_common.h")),
+    ("subdiv", "subdiv.hip", "psdr_hip_subdiv_*: one level of Loop / midpoint subdivision as a sparse operator (CSR from the host) and its transpose", ("op_common.h",)),
+    ("msloss", "msloss.hip", "psdr_hip_msloss_*: the multi-scale image loss over a residual pyramid, value and gradient in three launches", ("op_common.h",)),
+    ("ssim", "ssim.hip", "psdr_hip_ssim_*: the SSIM loss 1 - mean structural similarity under a Gaussian window, value and image gradient in three launches", ("op_common.h",)),
+    ("meshreg", "meshreg.hip", "psdr_hip_meshreg_*: the mesh regularisers (uniform Laplacian, normal consistency, edge length), value and vertex gradient in three launches", ("op_common.h",)),
+    ("chamfer", "chamfer.hip", "psdr_hip_chamfer_*: the Chamfer distance between two point sets, exact nearest neighbours by an LDS-tiled scan over query blocks x candidate slices, value and both gradients", ("nn_scan.h", "op_common.h")),
+    ("sdf", "sdf.hip", "psdr_hip_sdf_*: the signed distance to a mesh, the generalized winding number by an LDS-tiled scan over query blocks x face slices for the sign, and the vector-Jacobian product of the signed distance", ("mesh_pair.h", "nn_scan.h", "op_common.h")),
+    ("mtet", "mtet.hip", "psdr_hip_mtet_*: isosurface extraction by marching tetrahedra, the crossing masks and face counts of a lattice with their scans, the emit of edges and faces, the vertex positions and their vector-Jacobian product", ("op_common.h",)),
+    ("latreg", "latreg.hip", "psdr_hip_latreg_*: the regularisers of a signed distance on a lattice (Eikonal, Laplacian, sign-change cross-entropy), value and gradient by one haloed LDS tile per workgroup in three launches", ("op_common.h",)),
+    ("pointmesh", "pointmesh.hip", "psdr_hip_pointmesh_*: the point-to-mesh distance, for every point the nearest face and for every face the nearest point by two LDS-tiled scans over one pair function, value and both gradients", ("mesh_pair.h", "nn_scan.h", "op_common.h")),
 ]
-# the operators on meshes rather than frames: the same row format, compiled after OPERATOR_UNITS
-MESH_OPERATOR_UNITS = [
-    ("meshreg", "meshreg.hip", "psdr_hip_meshreg_*: the mesh regularisers (uniform Laplacian, normal consistency, edge length), value and vertex gradient in three launches", ()),
-    ("chamfer", "chamfer.hip", "psdr_hip_chamfer_*: the Chamfer distance between two point sets, exact nearest neighbours by an LDS-tiled scan over query blocks x candidate slices, value and both gradients", ()),
-]
-# the distances between point sets and the faces of a mesh: the same row format, compiled after MESH_OPERATOR_UNITS (a list of its own: tests/test_chamfer_cpu.py pins
-# MESH_OPERATOR_UNITS to its two rows)
-MESH_DISTANCE_UNITS = [
-    ("pointmesh", "pointmesh.hip", "psdr_hip_pointmesh_*: the point-to-mesh distance, for every point the nearest face and for every face the nearest point by two LDS-tiled scans over one pair function, value and both gradients", ()),
-]
-# the fields a mesh defines in space: the same row format, compiled between MESH_OPERATOR_UNITS and MESH_DISTANCE_UNITS (tests/test_pointmesh_cpu.py pins `pointmesh` as the last
-# unit and MESH_DISTANCE_UNITS to its one row)
-MESH_FIELD_UNITS = [
-    ("sdf", "sdf.hip", "psdr_hip_sdf_*: the signed distance to a mesh, the generalized winding number by an LDS-tiled scan over query blocks x face slices for the sign, and the vector-Jacobian product of the signed distance", ()),
-]
-# the way back from a field to a mesh: the same row format, compiled between MESH_FIELD_UNITS and MESH_DISTANCE_UNITS (a list of its own: tests/test_sdf_cpu.py pins
-# MESH_FIELD_UNITS to its one row)
-MESH_EXTRACTION_UNITS = [
-    ("mtet", "mtet.hip", "psdr_hip_mtet_*: isosurface extraction by marching tetrahedra, the crossing masks and face counts of a lattice with their scans, the emit of edges and faces, the vertex positions and their vector-Jacobian product", ()),
-]
-# the operators on the lattice itself: the same row format, compiled between MESH_EXTRACTION_UNITS and MESH_DISTANCE_UNITS (a list of its own: tests/test_mtet_cpu.py pins
-# MESH_EXTRACTION_UNITS to its one row)
-LATTICE_OPERATOR_UNITS = [
-    ("latreg", "latreg.hip", "psdr_hip_latreg_*: the regularisers of a signed distance on a lattice (Eikonal, Laplacian, sign-change cross-entropy), value and gradient by one haloed LDS tile per workgroup in three launches", ()),
-]
-OPERATOR_TUS = [(name, _H(src)[0], [], [os.path.join(ROOT, "include", "psdr_hip.h")] + _H(*headers) + BUILD_DEPS) for name, src, _what, headers in OPERATOR_UNITS + MESH_OPERATOR_UNITS + MESH_FIELD_UNITS + MESH_EXTRACTION_UNITS + LATTICE_OPERATOR_UNITS + MESH_DISTANCE_UNITS]      # hip_units()'s tuples
+OPERATOR_TUS = [(name, _H(src)[0], [], [os.path.join(ROOT, "include", "psdr_hip.h")] + _H(*headers) + BUILD_DEPS) for name, src, _what, headers in OPERATOR_UNITS]      # hip_units()'s tuples
 HIP_SRCS = [API_SRC, UNITS_SRC, SCENE_SRC] + [u[1] for u in OPERATOR_TUS]
 HIP_DEPS = sorted(set(API_DEPS + SCENE_DEPS + [d for u in OPERATOR_TUS for d in u[3]]))
 HOST_SRCS = [os.path.join(CSRC, "host", f) for f in ("scene_host.cpp", "bindings.cpp", "exr_piz.cpp")]
@@ -185,7 +167,7 @@ def _lint_units(hipcc, flags, units, objdir):
 def hip_units(flags=()):
     """the translation units of the library as (name, source, defines, dependencies): object api_<name>.o is compiled again when its source, one of
     its dependencies or a flag changed - the host unit `main` from api.hip, the kernel units `tu<k>` from render_units.hip (NOT from api.hip: an
-    edit of the host code leaves them alone), `scene` from scene_build.hip, and the rows of OPERATOR_UNITS, MESH_OPERATOR_UNITS, MESH_FIELD_UNITS, MESH_EXTRACTION_UNITS, LATTICE_OPERATOR_UNITS and MESH_DISTANCE_UNITS"""
+    edit of the host code leaves them alone), `scene` from scene_build.hip, and the rows of OPERATOR_UNITS"""
     # development builds (-DPSDR_CLS_MASK=m: the host code launches the kernels of those scene classes only) skip the other classes' units
     mask = 15
     for f in flags:

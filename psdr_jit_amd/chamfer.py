@@ -20,27 +20,23 @@ Written in torch ops, cdist(x, y).min() materialises an N x M matrix and uses th
 backward scatters with float atomics.  Here the scan keeps the queries in registers and streams the candidates through LDS, nothing of size N x M exists, there are no
 float atomics and no host synchronisation, and the same inputs give the same bits.
 
-launch_plan(n, m) is the scan's split into query blocks x candidate slices, stated a second time in C (psdr_hip_chamfer_plan); the result does not depend on it.
+launch_plan(n, m) is the scan's split into query blocks x candidate slices, which psdr_hip_chamfer_plan states in C; the result does not depend on it.
 SurfaceSampler draws its points on the host (numpy, once per resample) and applies them on the GPU as a sparse matrix through the subdivision operator's kernels.  One GPU
 only: under an initialised torch.distributed group of more than one rank the calls raise."""
 import collections as _collections
 import ctypes as _C
 import math as _math
 
+import functools as _functools
+
 import numpy as _np
 
-MAX_COUNT = 1 << 26
-THREADS = 256                # lanes of a workgroup
+from ._opcommon import MAX_COUNT, NARROW_MAX, TARGET_GROUPS, SCAN_THREADS as THREADS, _ceil_div, _checked_points, _faces_checked, _inverted, _single_gpu, slice_plan  # noqa: F401
+
 TILE = 1024                  # candidates per LDS tile
 WIDE_QUERIES = 4             # queries per lane for n > NARROW_MAX, else 1
-NARROW_MAX = 1024
-TARGET_GROUPS = 2048         # workgroups the grid aims at
 
 LaunchPlan = _collections.namedtuple("LaunchPlan", ["tile", "queries_per_lane", "slices", "slice_len"])
-
-
-def _ceil_div(a, b):
-    return -(-a // b)
 
 
 def launch_plan(n, m):
@@ -48,14 +44,7 @@ def launch_plan(n, m):
 
     A workgroup holds 256 queries_per_lane queries; slice s holds the candidates [s slice_len, min(m, (s + 1) slice_len)); the grid is query blocks x slices."""
     n, m = int(n), int(m)
-    if not (1 <= n <= MAX_COUNT and 1 <= m <= MAX_COUNT):
-        raise ValueError("launch_plan: n = %d, m = %d, both must lie in [1, 2^26]" % (n, m))
-    qpl = WIDE_QUERIES if n > NARROW_MAX else 1
-    qblocks = _ceil_div(n, THREADS * qpl)
-    tiles = _ceil_div(m, TILE)
-    want = min(_ceil_div(TARGET_GROUPS, qblocks), tiles)
-    slice_len = _ceil_div(tiles, want) * TILE
-    return LaunchPlan(TILE, qpl, _ceil_div(m, slice_len), slice_len)
+    return LaunchPlan(*slice_plan(n, m, TILE, WIDE_QUERIES, "launch_plan: n = %d, m = %d, both must lie in [1, 2^26]" % (n, m)))
 
 
 def _checked_weights(weights):
@@ -66,19 +55,6 @@ def _checked_weights(weights):
     if len(w) != 2 or not all(_math.isfinite(x) and x >= 0.0 for x in w):
         raise ValueError("ChamferDistance: weights must be two finite numbers >= 0 (x -> y, y -> x), got %r" % (weights,))
     return w
-
-
-def _checked_points(p, what, name):
-    import torch
-    if not isinstance(p, torch.Tensor):
-        p = torch.as_tensor(_np.asarray(p))
-    if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] < 1:
-        raise ValueError("%s: %s must be [N, 3] with N >= 1, got shape %s" % (what, name, tuple(p.shape)))
-    if not p.is_floating_point():
-        raise ValueError("%s: %s must be a floating-point tensor, got %s" % (what, name, p.dtype))
-    if p.shape[0] > MAX_COUNT:
-        raise ValueError("%s: %s has %d points, at most 2^26" % (what, name, p.shape[0]))
-    return p
 
 
 def _nearest(x, y, device):
@@ -93,21 +69,11 @@ def _nearest(x, y, device):
     return index, dist2
 
 
-def _inverted(index, count):
-    """index int32 [K] with values in [0, count) -> (begin int32 [count + 1], list int32 [K]): per value the positions that hold it, ascending (a stable sort); no
-    host synchronisation"""
-    import torch
-    ordered, order = torch.sort(index, stable=True)
-    begin = torch.searchsorted(ordered, torch.arange(count + 1, device=index.device, dtype=torch.int32), out_int32=True)
-    return begin, order.to(torch.int32)
-
-
 def nearest_points(x, y):
     """For every x_i the lowest index j of its nearest y_j and the squared distance: (index int32 [N], dist2 float32 [N]) on the render device, detached, computed on
     torch's current stream without a host synchronisation.  x [N, 3], y [M, 3] on any device and of any float dtype; the distance is the module docstring's d2, bit for
     bit."""
     x, y = _checked_points(x, "nearest_points", "x"), _checked_points(y, "nearest_points", "y")
-    from .denoise import _single_gpu
     _single_gpu("nearest_points")
     import torch
     from . import _device
@@ -116,7 +82,8 @@ def nearest_points(x, y):
         return _nearest(x.detach().to(device, torch.float32).contiguous(), y.detach().to(device, torch.float32).contiguous(), device)
 
 
-def _make_fn():
+@_functools.lru_cache(maxsize=None)
+def _fns():
     import torch
 
     class _ChamferFn(torch.autograd.Function):
@@ -149,16 +116,6 @@ def _make_fn():
     return _ChamferFn, _SampleFn
 
 
-_FNS = None
-
-
-def _fns():
-    global _FNS
-    if _FNS is None:
-        _FNS = _make_fn()
-    return _FNS
-
-
 class ChamferDistance:
     """loss = w_xy mean_i rho(dist2_xy[i]) + w_yx mean_j rho(dist2_yx[j]) between two point sets (the module's docstring has the definition).
 
@@ -180,7 +137,6 @@ class ChamferDistance:
         """-> (out [3]: the loss and the two direction means, dloss / dx [N, 3] or None, dloss / dy [M, 3] or None), on the current stream"""
         w = _checked_weights(self.weights)
         x, y = _checked_points(x, "ChamferDistance", "x"), _checked_points(y, "ChamferDistance", "y")
-        from .denoise import _single_gpu
         _single_gpu("ChamferDistance")
         import torch
         from . import cabi, _device, _stream_ptr
@@ -199,7 +155,7 @@ class ChamferDistance:
                 if want_grad:
                     xb, xl = _inverted(iyx, n)
             out = torch.empty(3, device=device, dtype=torch.float32)
-            partial = torch.empty(-(-n // THREADS) - (-m // THREADS), device=device, dtype=torch.float64)
+            partial = torch.empty(_ceil_div(n, THREADS) + _ceil_div(m, THREADS), device=device, dtype=torch.float64)
             gx, gy = (torch.empty_like(x), torch.empty_like(y)) if want_grad else (None, None)
             cabi.check(cabi.lib().psdr_hip_chamfer_eval(x.data_ptr(), n, y.data_ptr(), m, ptr(ixy), ptr(dxy), ptr(iyx), ptr(dyx), ptr(xb), ptr(xl), ptr(yb), ptr(yl),
                                                         (_C.c_float * 2)(*w), 1 if self.squared else 0, partial.data_ptr(), out.data_ptr(), ptr(gx), ptr(gy), _stream_ptr()))
@@ -283,7 +239,6 @@ class SurfaceSampler:
             faces = _np.asarray(mesh_or_faces)
             if num_vertices is None:
                 raise ValueError("SurfaceSampler: num_vertices is required with a face array")
-        from .meshreg import _faces_checked
         self.num_vertices = int(num_vertices)
         self.mesh_faces = _faces_checked(faces, self.num_vertices, "SurfaceSampler")
         if self.mesh_faces.shape[0] == 0:
@@ -337,7 +292,6 @@ class SurfaceSampler:
             x = torch.as_tensor(_np.asarray(x))
         if tuple(x.shape) != (rows, 3) or not x.is_floating_point():
             raise ValueError("SurfaceSampler: %s must be a floating-point [%d, 3] tensor, got %s %s" % (name, rows, x.dtype, tuple(x.shape)))
-        from .denoise import _single_gpu
         _single_gpu("SurfaceSampler")
         return x
 

@@ -107,10 +107,10 @@ template <class Launch> void ping_pong(int L, bool forward, const float *in, flo
 } // namespace psdr
 
 #if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
 #include <type_traits>
 
-namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
+#include "op_common.h"
+
 #define ATROUS_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return psdr::api_fail(std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
 namespace psdr {

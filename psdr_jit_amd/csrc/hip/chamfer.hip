@@ -19,14 +19,12 @@
 // inverted index (per point the j in ascending order, built by the caller with a stable sort), one store of the gradient, no atomics; the workgroup adds rho(dist2) in a
 // fixed order into its partial sum (in double, so that the mean carries one rounding).  k_finish: one workgroup adds the partial sums of each direction in a fixed order.
 // No host synchronisation; the same input gives the same bits.  No contraction in this unit (the build's -ffp-contract=off, and the distance is written with __fmul_rn / __fadd_rn).
-#include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
 #include <string>
 
 #include "../../../include/psdr_hip.h"
-
-namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
+#include "nn_scan.h"
 
 namespace {
 
@@ -34,27 +32,7 @@ constexpr int kThreads = 256;           // 4 waves
 constexpr int kSumThreads = 1024;       // k_finish: one workgroup, 16 waves
 constexpr int kTile = 1024;             // candidates per LDS tile: three planes of 4 KiB
 constexpr int kWideQueries = 4;         // queries per lane of the wide scan
-constexpr int kNarrowMax = 1024;        // n <= kNarrowMax: one query per lane (the wide scan would leave three of four registers idle)
-constexpr int kTargetGroups = 2048;     // workgroups the grid aims at: 8 per CU, the most that 256 CUs hold of 256-thread workgroups
-constexpr int kMaxCount = 1 << 26;
-
-struct Plan { int tile, qpl, slices, slice_len; };
-
-// the split, a pure function of (n, m); psdr_jit_amd/chamfer.py: launch_plan states it a second time
-inline Plan plan_of(int n, int m) {
-    Plan p;
-    p.tile = kTile;
-    p.qpl = n > kNarrowMax ? kWideQueries : 1;
-    const int per_group = kThreads * p.qpl;
-    const int qblocks = (n + per_group - 1) / per_group;
-    const int tiles = (m + kTile - 1) / kTile;
-    int want = (kTargetGroups + qblocks - 1) / qblocks;
-    if (want > tiles) want = tiles;
-    const int tiles_per_slice = (tiles + want - 1) / want;
-    p.slice_len = tiles_per_slice * kTile;
-    p.slices = (m + p.slice_len - 1) / p.slice_len;           // no empty slice: slice s is [s slice_len, min(m, (s + 1) slice_len))
-    return p;
-}
+static_assert(kThreads == scan::kThreads, "plan_of splits for the scan's workgroup");
 
 template <int Q> __global__ void __launch_bounds__(kThreads) k_scan(const float *__restrict__ x, int n, const float *__restrict__ y, int m, int slice_len, int slices,
                                                                     unsigned long long *__restrict__ keys) {
@@ -103,11 +81,7 @@ template <int Q> __global__ void __launch_bounds__(kThreads) k_scan(const float 
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
         const int i = (blockIdx.x * Q + q) * kThreads + threadIdx.x;
-        if (i < n) {
-            const unsigned long long key = ((unsigned long long) __float_as_uint(best[q]) << 32) | (unsigned int) bj[q];
-            if (slices == 1) keys[i] = key;
-            else atomicMin(keys + i, key);
-        }
+        if (i < n) merge_key(keys, i, pack_key(best[q], bj[q]), slices);
     }
 }
 
@@ -115,22 +89,8 @@ __global__ void __launch_bounds__(kThreads) k_unpack(const unsigned long long *_
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
     const unsigned long long key = keys[i];
-    idx[i] = (int) min((unsigned int) (key & 0xffffffffu), (unsigned int) (m - 1));
-    dist2[i] = __uint_as_float((unsigned int) (key >> 32));
-}
-
-// the sum over the workgroup in a fixed order, valid in thread 0: a wave by shuffles, the waves one after the other.  In double: the sum of 2^26 float32 terms then carries
-// one rounding, the final one, whatever the count
-template <int THREADS> __device__ double block_sum(double v, double *s_red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();                                       // (s_red of the previous sum has been read)
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int k = 0; k < THREADS / 64; ++k) t += s_red[k];
-    return t;
+    idx[i] = key_index(key, m);
+    dist2[i] = key_dist2(key);
 }
 
 // one point set p [n, 3] against the other set o [m, 3]
@@ -145,8 +105,6 @@ struct Side {
     float *grad;                        // [n, 3] or NULL
     double *partial;                    // one sum per workgroup (only when idx)
 };
-
-__device__ __forceinline__ float coefficient(float k, float s, int squared) { return squared ? k : (s > 0.f ? k / sqrtf(s) : 0.f); }
 
 __global__ void __launch_bounds__(kThreads) k_eval(Side S, int squared) {
     __shared__ double s_red[kThreads / 64];
@@ -196,31 +154,10 @@ __global__ void __launch_bounds__(kThreads) k_eval(Side S, int squared) {
     }
 }
 
-// a lane adds every 1024th partial sum of a direction in ascending order, then the workgroup's fixed order
-__device__ double run_sum(const double *p, int count, double *s_red) {
-    double a = 0.0;
-    for (int t = threadIdx.x; t < count; t += kSumThreads) a += p[t];
-    return block_sum<kSumThreads>(a, s_red);
-}
-
 __global__ void __launch_bounds__(kSumThreads) k_finish(const double *__restrict__ partial, int blocks_x, int blocks_y, int n, int m, float w_xy, float w_yx, float *__restrict__ out) {
     __shared__ double s_red[kSumThreads / 64];
-    const double sx = run_sum(partial, blocks_x, s_red);
-    const double sy = run_sum(partial + blocks_x, blocks_y, s_red);
-    if (threadIdx.x == 0) {
-        const float tx = blocks_x ? (float) (sx / (double) n) : 0.f, ty = blocks_y ? (float) (sy / (double) m) : 0.f;
-        float loss = 0.f;
-        if (blocks_x) loss = w_xy * tx;
-        if (blocks_y) { const float t = w_yx * ty; loss = blocks_x ? loss + t : t; }
-        out[0] = loss;
-        out[1] = tx;
-        out[2] = ty;
-    }
+    finish_two<kSumThreads>(partial, blocks_x, blocks_y, n, m, w_xy, w_yx, out, s_red);
 }
-
-inline int blocks_of(int count) { return (count + kThreads - 1) / kThreads; }
-
-inline std::string range_text(const char *name, long long v) { return std::string(name) + " = " + std::to_string(v) + ", must lie in [1, 2^26]"; }
 
 } // namespace
 
@@ -228,10 +165,10 @@ extern "C" {
 
 int psdr_hip_chamfer_plan(int32_t n, int32_t m, int32_t *tile, int32_t *queries_per_lane, int32_t *slices, int32_t *slice_len) {
     const std::string who = "psdr_hip_chamfer_plan: ";
-    if (n < 1 || n > kMaxCount) return psdr::api_fail(who + range_text("n", n));
-    if (m < 1 || m > kMaxCount) return psdr::api_fail(who + range_text("m", m));
+    if (!in_range(n)) return psdr::api_fail(who + range_text("n", n));
+    if (!in_range(m)) return psdr::api_fail(who + range_text("m", m));
     if (!tile || !queries_per_lane || !slices || !slice_len) return psdr::api_fail(who + "NULL argument");
-    const Plan p = plan_of(n, m);
+    const Plan p = plan_of<kTile, kWideQueries>(n, m);
     *tile = p.tile;
     *queries_per_lane = p.qpl;
     *slices = p.slices;
@@ -241,32 +178,27 @@ int psdr_hip_chamfer_plan(int32_t n, int32_t m, int32_t *tile, int32_t *queries_
 
 int psdr_hip_chamfer_nearest(const float *x, int32_t n, const float *y, int32_t m, uint64_t *keys, int32_t *index, float *dist2, void *stream) {
     const std::string who = "psdr_hip_chamfer_nearest: ";
-    if (n < 1 || n > kMaxCount) return psdr::api_fail(who + range_text("n", n));
-    if (m < 1 || m > kMaxCount) return psdr::api_fail(who + range_text("m", m));
+    if (!in_range(n)) return psdr::api_fail(who + range_text("n", n));
+    if (!in_range(m)) return psdr::api_fail(who + range_text("m", m));
     if (!x || !y || !keys || !index || !dist2) return psdr::api_fail(who + "NULL argument");
-    const Plan p = plan_of(n, m);
+    const Plan p = plan_of<kTile, kWideQueries>(n, m);
     hipStream_t st = (hipStream_t) stream;
     unsigned long long *k = reinterpret_cast<unsigned long long *>(keys);
-    if (p.slices > 1) {
-        const hipError_t e = hipMemsetAsync(k, 0xff, (size_t) n * sizeof(unsigned long long), st);          // above every key: the float half of a key is at most +infinity's bits
-        if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
-    }
-    const int per_group = kThreads * p.qpl;
-    const dim3 grid((unsigned) ((n + per_group - 1) / per_group), (unsigned) p.slices);
+    const hipError_t e = clear_keys(k, n, p, st);
+    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
+    const dim3 grid = scan_grid(n, p);
     if (p.qpl == 1) k_scan<1><<<grid, kThreads, 0, st>>>(x, n, y, m, p.slice_len, p.slices, k);
     else k_scan<kWideQueries><<<grid, kThreads, 0, st>>>(x, n, y, m, p.slice_len, p.slices, k);
-    k_unpack<<<blocks_of(n), kThreads, 0, st>>>(k, n, m, index, dist2);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
-    return 0;
+    k_unpack<<<blocks_of<kThreads>(n), kThreads, 0, st>>>(k, n, m, index, dist2);
+    return launch_status(who);
 }
 
 int psdr_hip_chamfer_eval(const float *x, int32_t n, const float *y, int32_t m, const int32_t *index_xy, const float *dist2_xy, const int32_t *index_yx, const float *dist2_yx,
                           const int32_t *x_begin, const int32_t *x_list, const int32_t *y_begin, const int32_t *y_list, const float *weights, int32_t squared,
                           double *partial, float *out, float *grad_x, float *grad_y, void *stream) {
     const std::string who = "psdr_hip_chamfer_eval: ";
-    if (n < 1 || n > kMaxCount) return psdr::api_fail(who + range_text("n", n));
-    if (m < 1 || m > kMaxCount) return psdr::api_fail(who + range_text("m", m));
+    if (!in_range(n)) return psdr::api_fail(who + range_text("n", n));
+    if (!in_range(m)) return psdr::api_fail(who + range_text("m", m));
     if (!x || !y || !weights || !partial || !out) return psdr::api_fail(who + "NULL argument");
     for (int k = 0; k < 2; ++k)
         if (!std::isfinite(weights[k]) || weights[k] < 0.f) return psdr::api_fail(who + "weights[" + std::to_string(k) + "] = " + std::to_string(weights[k]) + ", must be finite and not negative");
@@ -279,16 +211,14 @@ int psdr_hip_chamfer_eval(const float *x, int32_t n, const float *y, int32_t m, 
     if (grad_x && on_yx && (!x_begin || !x_list)) return psdr::api_fail(who + "the gradient of the y -> x term needs x_begin and x_list, the inverted index of index_yx");
     const double unit = squared ? 2.0 : 1.0;
     const float k_xy = (float) (unit * (double) weights[0] / (double) n), k_yx = (float) (unit * (double) weights[1] / (double) m);
-    const int bx = on_xy ? blocks_of(n) : 0, by = on_yx ? blocks_of(m) : 0;
+    const int bx = on_xy ? blocks_of<kThreads>(n) : 0, by = on_yx ? blocks_of<kThreads>(m) : 0;
     hipStream_t st = (hipStream_t) stream;
     Side X{x, y, n, m, on_xy ? index_xy : nullptr, dist2_xy, on_yx ? x_begin : nullptr, x_list, dist2_yx, k_xy, k_yx, grad_x, partial};
     Side Y{y, x, m, n, on_yx ? index_yx : nullptr, dist2_yx, on_xy ? y_begin : nullptr, y_list, dist2_xy, k_yx, k_xy, grad_y, partial + bx};
-    if (on_xy || grad_x) k_eval<<<blocks_of(n), kThreads, 0, st>>>(X, squared ? 1 : 0);
-    if (on_yx || grad_y) k_eval<<<blocks_of(m), kThreads, 0, st>>>(Y, squared ? 1 : 0);
+    if (on_xy || grad_x) k_eval<<<blocks_of<kThreads>(n), kThreads, 0, st>>>(X, squared ? 1 : 0);
+    if (on_yx || grad_y) k_eval<<<blocks_of<kThreads>(m), kThreads, 0, st>>>(Y, squared ? 1 : 0);
     k_finish<<<1, kSumThreads, 0, st>>>(partial, bx, by, n, m, weights[0], weights[1], out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
-    return 0;
+    return launch_status(who);
 }
 
 } // extern "C"

@@ -29,8 +29,7 @@
 #include <string>
 
 #include "../../../include/psdr_hip.h"
-
-namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
+#include "op_common.h"
 
 namespace {
 
@@ -121,19 +120,6 @@ template <int H> __device__ __forceinline__ int crossings_of(const float *__rest
         if (x - dx >= 0 && y - dy >= 0 && z - dz >= 0 && inside_of(sS[T::at(lx - dx, ly - dy, lz - dz)]) != in0) ++m;
     }
     return m;
-}
-
-// the sum over the workgroup in a fixed order, valid in thread 0: a wave by shuffles, the waves one after the other
-template <int THREADS, typename T> __device__ T block_sum(T v, T *s_red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();                                       // (s_red of the previous sum has been read)
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T t = 0;
-    if (threadIdx.x == 0)
-        for (int k = 0; k < THREADS / 64; ++k) t += s_red[k];
-    return t;
 }
 
 // partial: [4][blocks] - the workgroups' sums of the Eikonal, Laplacian and sign summands, and (as int32) of m_u
@@ -382,9 +368,7 @@ int psdr_hip_latreg_eval(const float *sdf, int32_t nx, int32_t ny, int32_t nz, c
     k_value<<<L.blocks, kThreads, 0, st>>>(sdf, L, c, scratch);
     k_finish<<<1, kSumThreads, 0, st>>>(L, c, scratch, out, crossings);
     if (grad) k_grad<<<L.blocks, kThreads, 0, st>>>(sdf, L, c, crossings, grad);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
-    return 0;
+    return launch_status(who);
 }
 
 } // extern "C"

@@ -26,8 +26,7 @@
 #include <vector>
 
 #include "../../../include/psdr_hip.h"
-
-namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
+#include "op_common.h"
 
 namespace {
 
@@ -70,19 +69,6 @@ __device__ __forceinline__ float dop(float a, float b, float c, float d) {
 }
 __device__ __forceinline__ V3 cross(V3 a, V3 b) { return V3{dop(a.y, b.z, a.z, b.y), dop(a.z, b.x, a.x, b.z), dop(a.x, b.y, a.y, b.x)}; }
 __device__ __forceinline__ float4 f4(V3 a) { return make_float4(a.x, a.y, a.z, 0.f); }
-
-// the sum over the workgroup in a fixed order, valid in thread 0: a wave by shuffles, the waves one after the other
-template <int THREADS> __device__ float block_sum(float v, float *s_red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();                                       // (s_red of the previous sum has been read)
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-    if (threadIdx.x == 0)
-        for (int k = 0; k < THREADS / 64; ++k) t += s_red[k];
-    return t;
-}
 
 __device__ __forceinline__ float vertex_elem(const Mesh &M, const float *__restrict__ v, int i) {
     const int b0 = M.row_begin[i], b1 = M.row_begin[i + 1];
@@ -241,8 +227,6 @@ __global__ void __launch_bounds__(kSumThreads) k_finish(Mesh M, Call c, float *_
     }
 }
 
-inline int blocks_of(int count) { return (count + kThreads - 1) / kThreads; }
-
 // the host-side check of one per-vertex list of (element, role) pairs against the element table it inverts: "" or what is wrong with it
 std::string check_index(const char *name, int32_t n, int32_t count, int32_t roles, const int32_t *table, const int32_t *begin, const int32_t *elem, const int32_t *role) {
     const std::string s(name);
@@ -338,7 +322,7 @@ int psdr_hip_meshreg_create(int32_t n, int32_t e, int32_t h, const int32_t *edge
     for (size_t k = 0; k < z; ++k) ints[o_col + k] = col[k];
     for (size_t k = 0; k < e2; ++k) { ints[o_edges + k] = edges[k]; ints[o_evc + k] = 2 * ev_elem[k] + ev_role[k]; }
     for (size_t k = 0; k < h4; ++k) ints[o_hvc + k] = 4 * hv_elem[k] + hv_role[k];
-    const size_t n_vec = 2 * (size_t) n + (size_t) e + h4, n_part = (size_t) blocks_of(n) + blocks_of(e) + blocks_of(h);
+    const size_t n_vec = 2 * (size_t) n + (size_t) e + h4, n_part = (size_t) blocks_of<kThreads>(n) + blocks_of<kThreads>(e) + blocks_of<kThreads>(h);
     hipError_t err = hipMalloc((void **) &m->d_ints, ints.size() * sizeof(int32_t));
     if (err == hipSuccess) err = hipMalloc((void **) &m->d_vec, n_vec * sizeof(float4));
     if (err == hipSuccess) err = hipMalloc((void **) &m->d_partial, n_part * sizeof(float));
@@ -374,20 +358,18 @@ int psdr_hip_meshreg_eval(psdr_hip_meshreg *m, const float *v, const float *weig
     Call c{};
     c.w_lap = weights[0]; c.w_nor = weights[1]; c.w_edge = weights[2];
     c.L0 = target_length;
-    c.blocks_v = c.w_lap > 0.f && M.n_lap > 0 ? blocks_of(M.n) : 0;
-    c.blocks_h = c.w_nor > 0.f ? blocks_of(M.h) : 0;
-    c.blocks_e = c.w_edge > 0.f ? blocks_of(M.e) : 0;
+    c.blocks_v = c.w_lap > 0.f && M.n_lap > 0 ? blocks_of<kThreads>(M.n) : 0;
+    c.blocks_h = c.w_nor > 0.f ? blocks_of<kThreads>(M.h) : 0;
+    c.blocks_e = c.w_edge > 0.f ? blocks_of<kThreads>(M.e) : 0;
     c.s_lap = c.blocks_v ? (float) (2.0 * (double) c.w_lap / (double) M.n_lap) : 0.f;
     c.s_nor = c.blocks_h ? (float) ((double) c.w_nor / (double) M.h) : 0.f;
     c.s_edge = c.blocks_e ? (float) ((double) c.w_edge / (double) M.e) : 0.f;
     hipStream_t st = (hipStream_t) stream;
     const int blocks = c.blocks_v + c.blocks_e + c.blocks_h;
     if (blocks) k_elem<<<blocks, kThreads, 0, st>>>(M, c, v);
-    if (grad) k_gather<<<blocks_of(M.n), kThreads, 0, st>>>(M, c, grad);
+    if (grad) k_gather<<<blocks_of<kThreads>(M.n), kThreads, 0, st>>>(M, c, grad);
     k_finish<<<1, kSumThreads, 0, st>>>(M, c, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
-    return 0;
+    return launch_status(who);
 }
 
 } // extern "C"

@@ -21,8 +21,7 @@
 #include <string>
 
 #include "../../../include/psdr_hip.h"
-
-namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
+#include "op_common.h"
 
 namespace {
 
@@ -52,19 +51,6 @@ struct Pyr {
 
 template <int NORM> __device__ __forceinline__ float rho(float d) { return NORM == PSDR_MSLOSS_L1 ? fabsf(d) : d * d; }
 template <int NORM> __device__ __forceinline__ float drho(float d) { return NORM == PSDR_MSLOSS_L1 ? (float) (d > 0.f) - (float) (d < 0.f) : 2.f * d; }
-
-// the sum over the workgroup in a fixed order, valid in thread 0: a wave by shuffles, the waves one after the other
-template <int THREADS> __device__ float block_sum(float v, float *s_red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();                                       // (s_red of the previous sum has been read)
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-    if (threadIdx.x == 0)
-        for (int k = 0; k < THREADS / 64; ++k) t += s_red[k];
-    return t;
-}
 
 // WC: 0 no weight, 1 one channel, 2 C channels
 template <int C, int NORM, int WC> __global__ void __launch_bounds__(kThreads)
@@ -346,8 +332,7 @@ int psdr_hip_msloss_eval(psdr_hip_msloss *h, const float *img, const float *targ
     case 3: launch_c<3>(P, norm, wc, img, target, weight, out, grad, st); break;
     default: launch_c<4>(P, norm, wc, img, target, weight, out, grad, st); break;
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
+    if (launch_status(who)) return 1;
     h->evaluated = true;
     return 0;
 }

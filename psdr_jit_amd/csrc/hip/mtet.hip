@@ -19,8 +19,7 @@
 #include <string>
 
 #include "../../../include/psdr_hip.h"
-
-namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
+#include "op_common.h"
 
 namespace {
 
@@ -336,8 +335,6 @@ __global__ void __launch_bounds__(kThreads) k_vertices_adj(Adjoint A, Lattice L)
 
 // ---- host
 
-inline int blocks_of(int count) { return (count + kThreads - 1) / kThreads; }
-
 // refuses a bad lattice; fills L
 inline bool lattice(const std::string &who, int32_t nx, int32_t ny, int32_t nz, Lattice *L) {
     if (nx < 2 || ny < 2 || nz < 2) {
@@ -364,16 +361,14 @@ inline void scan_sums(int *sums, int *offsets, int blocks, int *sums1, int *offs
         k_scan_block<<<1, kThreads, 0, st>>>(sums, blocks, nullptr, offsets, total);
         return;
     }
-    const int blocks1 = blocks_of(blocks);          // <= 256: Nv <= 256^3
+    const int blocks1 = blocks_of<kThreads>(blocks);          // <= 256: Nv <= 256^3
     k_block_sums<<<blocks1, kThreads, 0, st>>>(sums, blocks, sums1);
     k_scan_block<<<1, kThreads, 0, st>>>(sums1, blocks1, nullptr, offsets1, total);
     k_scan_block<<<blocks1, kThreads, 0, st>>>(sums, blocks, offsets1, offsets, nullptr);
 }
 
 inline int launched(const std::string &who) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
-    return 0;
+    return launch_status(who);
 }
 
 } // namespace
@@ -387,11 +382,11 @@ int psdr_hip_mtet_plan(int32_t nx, int32_t ny, int32_t nz, int32_t *tile, int32_
     if (!lattice(who, nx, ny, nz, &L)) return 1;
     if (!tile || !vertex_blocks || !cell_blocks || !vertex_passes || !cell_passes || !scratch_ints) return psdr::api_fail(who + "NULL argument");
     *tile = kThreads;
-    *vertex_blocks = blocks_of(L.nv);
-    *cell_blocks = blocks_of(L.nc);
+    *vertex_blocks = blocks_of<kThreads>(L.nv);
+    *cell_blocks = blocks_of<kThreads>(L.nc);
     *vertex_passes = passes_of(*vertex_blocks);
     *cell_passes = passes_of(*cell_blocks);
-    *scratch_ints = 2 * (*vertex_blocks + blocks_of(*vertex_blocks));          // sums and offsets of both passes; the cells (fewer) use the same ints after the vertices
+    *scratch_ints = 2 * (*vertex_blocks + blocks_of<kThreads>(*vertex_blocks));          // sums and offsets of both passes; the cells (fewer) use the same ints after the vertices
     return 0;
 }
 
@@ -406,7 +401,7 @@ int psdr_hip_mtet_count(const float *sdf, int32_t nx, int32_t ny, int32_t nz, ui
         for (int j = i + 1; j < 7; ++j)
             if (outs[i] == outs[j]) return psdr::api_fail(who + "mask, base, cell_faces, cell_base, scratch and totals must be arrays of their own");
     hipStream_t st = (hipStream_t) stream;
-    const int bv = blocks_of(L.nv), bc = blocks_of(L.nc), bv1 = blocks_of(bv);
+    const int bv = blocks_of<kThreads>(L.nv), bc = blocks_of<kThreads>(L.nc), bv1 = blocks_of<kThreads>(bv);
     int *sums = scratch, *offsets = sums + bv, *sums1 = offsets + bv, *offsets1 = sums1 + bv1;
     k_vertex_mask<<<bv, kThreads, 0, st>>>(sdf, L, mask, sums);
     scan_sums(sums, offsets, bv, sums1, offsets1, totals, st);
@@ -431,8 +426,8 @@ int psdr_hip_mtet_emit(const float *sdf, int32_t nx, int32_t ny, int32_t nz, con
         (const void *) faces == mask || faces == base || faces == cell_base)
         return psdr::api_fail(who + "edges and faces must be arrays of their own");
     hipStream_t st = (hipStream_t) stream;
-    k_emit_edges<<<blocks_of(L.nv), kThreads, 0, st>>>(L, mask, base, num_vertices, edges);
-    k_emit_faces<<<blocks_of(L.nc), kThreads, 0, st>>>(sdf, L, mask, base, cell_base, num_faces, faces);
+    k_emit_edges<<<blocks_of<kThreads>(L.nv), kThreads, 0, st>>>(L, mask, base, num_vertices, edges);
+    k_emit_faces<<<blocks_of<kThreads>(L.nc), kThreads, 0, st>>>(sdf, L, mask, base, cell_base, num_faces, faces);
     return launched(who);
 }
 
@@ -443,7 +438,7 @@ int psdr_hip_mtet_vertices(const float *sdf, const float *pos, int32_t nx, int32
     if (num_vertices < 1 || (long long) num_vertices > 7LL * L.nv) return psdr::api_fail(who + "num_vertices = " + std::to_string(num_vertices) + ", must lie in [1, 7 Nv]");
     if (!sdf || !pos || !edges || !v) return psdr::api_fail(who + "NULL argument");
     if (v == sdf || v == pos || (const void *) v == edges) return psdr::api_fail(who + "v must be an array of its own");
-    k_vertices<<<blocks_of(num_vertices), kThreads, 0, (hipStream_t) stream>>>(sdf, pos, L.nv, edges, num_vertices, v);
+    k_vertices<<<blocks_of<kThreads>(num_vertices), kThreads, 0, (hipStream_t) stream>>>(sdf, pos, L.nv, edges, num_vertices, v);
     return launched(who);
 }
 
@@ -462,7 +457,7 @@ int psdr_hip_mtet_vertices_adj(const float *sdf, const float *pos, int32_t nx, i
     A.mask = mask; A.base = base;
     A.nv_mesh = num_vertices;
     A.gs = grad_sdf; A.gp = grad_pos;
-    k_vertices_adj<<<blocks_of(L.nv), kThreads, 0, (hipStream_t) stream>>>(A, L);
+    k_vertices_adj<<<blocks_of<kThreads>(L.nv), kThreads, 0, (hipStream_t) stream>>>(A, L);
     return launched(who);
 }
 

@@ -9,7 +9,7 @@
 // pair and one denominator, and divides twice - the quotients are those of the definition, bit for bit, because every region's s and t is one correctly rounded division (or a
 // constant, or 1 - t) of the selected operands.  A denominator of 0 gives the quotient 0.
 //
-// The scans (k_scan<Q, FACE_QUERIES>), the skeleton of chamfer.hip's k_scan.  A lane holds Q queries in registers; the candidates of the workgroup's slice go through LDS a
+// The scans (k_scan<Q, FACE_QUERIES>).  A lane holds Q queries in registers; the candidates of the workgroup's slice go through LDS a
 // tile at a time and every lane reads the same address: a broadcast.
 //   points as queries (FACE_QUERIES = false): the candidates are face records (a, ab, ac, b, c: 16 floats, written once per call by k_records), four float4 per face;
 //   faces as queries  (FACE_QUERIES = true):  a lane holds its faces' records in registers, the candidates are points as x / y / z planes, one float4 of a plane = four points.
@@ -22,57 +22,23 @@
 // corner record - its own pair, then the points that chose it, ascending), k_eval_vertices (a lane per vertex: the corner records that name it, in the topology's order), and
 // k_finish.  No float atomics, no host synchronisation; the same input gives the same bits.  No contraction in this unit (the build's -ffp-contract=off, and the pair function is
 // written with __fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn).
-#include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
 #include <string>
 
 #include "../../../include/psdr_hip.h"
-
-namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
+#include "mesh_pair.h"
+#include "nn_scan.h"
 
 namespace {
 
-constexpr int kThreads = 256;           // 4 waves
-constexpr int kSumThreads = 1024;       // k_finish: one workgroup, 16 waves
-constexpr int kTile = 256;              // candidates per LDS tile: 16 KiB of face records, or three planes of 1 KiB of points
-constexpr int kWideQueries = 2;         // queries per lane of the wide scan
-constexpr int kNarrowMax = 1024;        // n <= kNarrowMax: one query per lane
-constexpr int kTargetGroups = 2048;     // workgroups the grid aims at: 8 per CU (section 7k's constant)
-constexpr int kMaxCount = 1 << 26;
+constexpr int kThreads = 256;                   // 4 waves
+constexpr int kSumThreads = 1024;               // k_finish: one workgroup, 16 waves
+constexpr int kTile = pm::kTile;                // candidates per LDS tile: 16 KiB of face records, or three planes of 1 KiB of points
+constexpr int kWideQueries = pm::kWideQueries;  // queries per lane of the wide scan
+static_assert(kThreads == scan::kThreads, "plan_of splits for the scan's workgroup");
 
-struct Plan { int tile, qpl, slices, slice_len; };
-
-// the split, a pure function of (queries, candidates); psdr_jit_amd/pointmesh.py: launch_plan_pm states it a second time
-inline Plan plan_of(int n, int m) {
-    Plan p;
-    p.tile = kTile;
-    p.qpl = n > kNarrowMax ? kWideQueries : 1;
-    const int per_group = kThreads * p.qpl;
-    const int qblocks = (n + per_group - 1) / per_group;
-    const int tiles = (m + kTile - 1) / kTile;
-    int want = (kTargetGroups + qblocks - 1) / qblocks;
-    if (want > tiles) want = tiles;
-    const int tiles_per_slice = (tiles + want - 1) / want;
-    p.slice_len = tiles_per_slice * kTile;
-    p.slices = (m + p.slice_len - 1) / p.slice_len;           // no empty slice
-    return p;
-}
-
-struct Vec { float x, y, z; };
-struct Face { Vec a, ab, ac, b, c; };
-
-__device__ __forceinline__ Vec sub(Vec p, Vec q) { return {__fsub_rn(p.x, q.x), __fsub_rn(p.y, q.y), __fsub_rn(p.z, q.z)}; }
-__device__ __forceinline__ float dot(Vec p, Vec q) { return __fadd_rn(__fadd_rn(__fmul_rn(p.x, q.x), __fmul_rn(p.y, q.y)), __fmul_rn(p.z, q.z)); }
-__device__ __forceinline__ float cross2(float a, float b, float c, float d) { return __fsub_rn(__fmul_rn(a, b), __fmul_rn(c, d)); }          // a b - c d
 __device__ __forceinline__ float quotient(float num, float den) { return den == 0.f ? 0.f : __fdiv_rn(num, den); }
-
-// e = ap - (s ab + t ac): p - q without the cancellation
-__device__ __forceinline__ Vec residual(Vec ap, const Face &f, float s, float t) {
-    return {__fsub_rn(ap.x, __fadd_rn(__fmul_rn(s, f.ab.x), __fmul_rn(t, f.ac.x))),
-            __fsub_rn(ap.y, __fadd_rn(__fmul_rn(s, f.ab.y), __fmul_rn(t, f.ac.y))),
-            __fsub_rn(ap.z, __fadd_rn(__fmul_rn(s, f.ab.z), __fmul_rn(t, f.ac.z)))};
-}
 
 // THE PAIR FUNCTION: the closest point of the closed triangle f to p as (s, t), and dist2.  Selects only; later selects overrule earlier ones, so that the first test of the
 // definition's cascade that holds decides
@@ -102,21 +68,6 @@ __device__ __forceinline__ float closest(Vec p, const Face &f, float &s, float &
     if (r1) { s = 0.f; t = 0.f; }
     e = residual(ap, f, s, t);
     return dot(e, e);
-}
-
-__device__ __forceinline__ int clamped(int i, int count) { return min(max(i, 0), count - 1); }
-
-__device__ __forceinline__ Vec load3(const float *__restrict__ a, int i) { return {a[3LL * i], a[3LL * i + 1], a[3LL * i + 2]}; }
-
-// face f of the mesh: vertex ids clamped into [0, nv)
-__device__ __forceinline__ Face load_face(const float *__restrict__ v, int nv, const int *__restrict__ faces, int f) {
-    Face r;
-    r.a = load3(v, clamped(faces[3LL * f], nv));
-    r.b = load3(v, clamped(faces[3LL * f + 1], nv));
-    r.c = load3(v, clamped(faces[3LL * f + 2], nv));
-    r.ab = sub(r.b, r.a);
-    r.ac = sub(r.c, r.a);
-    return r;
 }
 
 __device__ __forceinline__ Face face_of(float4 q0, float4 q1, float4 q2, float4 q3) {
@@ -210,11 +161,7 @@ template <int Q, bool FACE_QUERIES> __global__ void __launch_bounds__(kThreads) 
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
         const int i = (blockIdx.x * Q + q) * kThreads + threadIdx.x;
-        if (i < n) {
-            const unsigned long long key = ((unsigned long long) __float_as_uint(best[q]) << 32) | (unsigned int) bj[q];
-            if (slices == 1) keys[i] = key;
-            else atomicMin(keys + i, key);
-        }
+        if (i < n) merge_key(keys, i, pack_key(best[q], bj[q]), slices);
     }
 }
 
@@ -225,7 +172,7 @@ __global__ void __launch_bounds__(kThreads) k_unpack(const unsigned long long *_
     const int n = face_queries ? nf : np, m = face_queries ? np : nf;
     if (i >= n) return;
     const unsigned long long key = keys[i];
-    const int j = (int) min((unsigned int) (key & 0xffffffffu), (unsigned int) (m - 1));
+    const int j = key_index(key, m);
     float s, t;
     Vec e;
     closest(load3(p, face_queries ? j : i), load_face(v, nv, faces, face_queries ? i : j), s, t, e);
@@ -233,23 +180,8 @@ __global__ void __launch_bounds__(kThreads) k_unpack(const unsigned long long *_
     bary[3LL * i] = __fsub_rn(__fsub_rn(1.f, s), t);
     bary[3LL * i + 1] = s;
     bary[3LL * i + 2] = t;
-    dist2[i] = __uint_as_float((unsigned int) (key >> 32));
+    dist2[i] = key_dist2(key);
 }
-
-// the sum over the workgroup in a fixed order, valid in thread 0 (chamfer.hip's): a wave by shuffles, the waves one after the other, in double
-template <int THREADS> __device__ double block_sum(double v, double *s_red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();                                       // (s_red of the previous sum has been read)
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int k = 0; k < THREADS / 64; ++k) t += s_red[k];
-    return t;
-}
-
-__device__ __forceinline__ float coefficient(float k, float s, int squared) { return squared ? k : (s > 0.f ? k / sqrtf(s) : 0.f); }
 
 struct Eval {
     const float *p, *v;
@@ -318,17 +250,6 @@ __global__ void __launch_bounds__(kThreads) k_eval_points(Eval E) {
     }
 }
 
-// c[3][3] += -(bary_c) kr
-__device__ __forceinline__ void add_corners(float *c, Vec kr, float b0, float b1, float b2) {
-    const float w[3] = {b0, b1, b2};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        c[3 * k] += -(kr.x * w[k]);
-        c[3 * k + 1] += -(kr.y * w[k]);
-        c[3 * k + 2] += -(kr.z * w[k]);
-    }
-}
-
 __global__ void __launch_bounds__(kThreads) k_eval_faces(Eval E) {
     __shared__ double s_red[kThreads / 64];
     const int f = blockIdx.x * kThreads + threadIdx.x;
@@ -341,7 +262,7 @@ __global__ void __launch_bounds__(kThreads) k_eval_faces(Eval E) {
             val = E.squared ? d2 : sqrtf(d2);
             if (E.corners) {
                 const float *b = E.bary_f + 3LL * f;
-                add_corners(own, pair_term(E, clamped(E.point_of_face[f], E.np), f, b[1], b[2], d2, E.k_fp), b[0], b[1], b[2]);
+                add_corners(own, pair_term(E, clamped(E.point_of_face[f], E.np), f, b[1], b[2], d2, E.k_fp), b);
                 have = true;
             }
         }
@@ -351,7 +272,7 @@ __global__ void __launch_bounds__(kThreads) k_eval_faces(Eval E) {
             for (int k = b0; k < b1; ++k) {
                 const int i = clamped(E.f_list[k], E.np);
                 const float *b = E.bary_p + 3LL * i;
-                add_corners(sum, pair_term(E, i, f, b[1], b[2], E.dist2_p[i], E.k_pf), b[0], b[1], b[2]);
+                add_corners(sum, pair_term(E, i, f, b[1], b[2], E.dist2_p[i], E.k_pf), b);
             }
 #pragma unroll
             for (int k = 0; k < 9; ++k) own[k] = have ? own[k] + sum[k] : sum[k];
@@ -368,50 +289,13 @@ __global__ void __launch_bounds__(kThreads) k_eval_faces(Eval E) {
 }
 
 __global__ void __launch_bounds__(kThreads) k_eval_vertices(Eval E) {
-    const int i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= E.nv) return;
-    const int total = 3 * E.nf;
-    const int b0 = min(max(E.vc_begin[i], 0), total), b1 = min(max(E.vc_begin[i + 1], b0), total);
-    float gx = 0.f, gy = 0.f, gz = 0.f;
-    for (int k = b0; k < b1; ++k) {
-        const float *c = E.corners + 3LL * clamped(E.vc_corner[k], total);
-        gx += c[0];
-        gy += c[1];
-        gz += c[2];
-    }
-    float *o = E.grad_v + 3LL * i;
-    o[0] = gx;
-    o[1] = gy;
-    o[2] = gz;
-}
-
-// a lane adds every 1024th partial sum of a direction in ascending order, then the workgroup's fixed order
-__device__ double run_sum(const double *p, int count, double *s_red) {
-    double a = 0.0;
-    for (int t = threadIdx.x; t < count; t += kSumThreads) a += p[t];
-    return block_sum<kSumThreads>(a, s_red);
+    gather_corners<kThreads>(E);
 }
 
 __global__ void __launch_bounds__(kSumThreads) k_finish(const double *__restrict__ partial, int blocks_p, int blocks_f, int np, int nf, float w_pf, float w_fp, float *__restrict__ out) {
     __shared__ double s_red[kSumThreads / 64];
-    const double sp = run_sum(partial, blocks_p, s_red);
-    const double sf = run_sum(partial + blocks_p, blocks_f, s_red);
-    if (threadIdx.x == 0) {
-        const float tp = blocks_p ? (float) (sp / (double) np) : 0.f, tf = blocks_f ? (float) (sf / (double) nf) : 0.f;
-        float loss = 0.f;
-        if (blocks_p) loss = w_pf * tp;
-        if (blocks_f) { const float t = w_fp * tf; loss = blocks_p ? loss + t : t; }
-        out[0] = loss;
-        out[1] = tp;
-        out[2] = tf;
-    }
+    finish_two<kSumThreads>(partial, blocks_p, blocks_f, np, nf, w_pf, w_fp, out, s_red);
 }
-
-inline int blocks_of(int count) { return (count + kThreads - 1) / kThreads; }
-
-inline bool in_range(long long v) { return v >= 1 && v <= kMaxCount; }
-
-inline std::string range_text(const char *name, long long v) { return std::string(name) + " = " + std::to_string(v) + ", must lie in [1, 2^26]"; }
 
 } // namespace
 
@@ -422,7 +306,7 @@ int psdr_hip_pointmesh_plan(int32_t n_queries, int32_t n_candidates, int32_t *ti
     if (!in_range(n_queries)) return psdr::api_fail(who + range_text("n_queries", n_queries));
     if (!in_range(n_candidates)) return psdr::api_fail(who + range_text("n_candidates", n_candidates));
     if (!tile || !queries_per_lane || !slices || !slice_len) return psdr::api_fail(who + "NULL argument");
-    const Plan p = plan_of(n_queries, n_candidates);
+    const Plan p = plan_of<kTile, kWideQueries>(n_queries, n_candidates);
     *tile = p.tile;
     *queries_per_lane = p.qpl;
     *slices = p.slices;
@@ -440,28 +324,23 @@ int psdr_hip_pointmesh_nearest(const float *p, int32_t n_points, const float *v,
     if (!p || !v || !faces || !keys || !index || !bary || !dist2) return psdr::api_fail(who + "NULL argument");
     if (direction == 0 && !records) return psdr::api_fail(who + "direction 0 needs the records work array, NULL given");
     const int n = direction ? n_faces : n_points, m = direction ? n_points : n_faces;
-    const Plan pl = plan_of(n, m);
+    const Plan pl = plan_of<kTile, kWideQueries>(n, m);
     hipStream_t st = (hipStream_t) stream;
     unsigned long long *k = reinterpret_cast<unsigned long long *>(keys);
-    if (pl.slices > 1) {
-        const hipError_t e = hipMemsetAsync(k, 0xff, (size_t) n * sizeof(unsigned long long), st);          // above every key: the float half of a key is at most +infinity's bits
-        if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
-    }
+    const hipError_t e = clear_keys(k, n, pl, st);
+    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
     float4 *rec = reinterpret_cast<float4 *>(records);
-    const int per_group = kThreads * pl.qpl;
-    const dim3 grid((unsigned) ((n + per_group - 1) / per_group), (unsigned) pl.slices);
+    const dim3 grid = scan_grid(n, pl);
     if (direction == 0) {
-        k_records<<<blocks_of(n_faces), kThreads, 0, st>>>(v, n_vertices, faces, n_faces, rec);
+        k_records<<<blocks_of<kThreads>(n_faces), kThreads, 0, st>>>(v, n_vertices, faces, n_faces, rec);
         if (pl.qpl == 1) k_scan<1, false><<<grid, kThreads, 0, st>>>(p, v, n_vertices, faces, rec, n, m, pl.slice_len, pl.slices, k);
         else k_scan<kWideQueries, false><<<grid, kThreads, 0, st>>>(p, v, n_vertices, faces, rec, n, m, pl.slice_len, pl.slices, k);
     } else {
         if (pl.qpl == 1) k_scan<1, true><<<grid, kThreads, 0, st>>>(p, v, n_vertices, faces, rec, n, m, pl.slice_len, pl.slices, k);
         else k_scan<kWideQueries, true><<<grid, kThreads, 0, st>>>(p, v, n_vertices, faces, rec, n, m, pl.slice_len, pl.slices, k);
     }
-    k_unpack<<<blocks_of(n), kThreads, 0, st>>>(k, p, n_points, v, n_vertices, faces, n_faces, direction, index, bary, dist2);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
-    return 0;
+    k_unpack<<<blocks_of<kThreads>(n), kThreads, 0, st>>>(k, p, n_points, v, n_vertices, faces, n_faces, direction, index, bary, dist2);
+    return launch_status(who);
 }
 
 int psdr_hip_pointmesh_eval(const float *p, int32_t n_points, const float *v, int32_t n_vertices, const int32_t *faces, int32_t n_faces,
@@ -484,7 +363,7 @@ int psdr_hip_pointmesh_eval(const float *p, int32_t n_points, const float *v, in
     if (grad_p && on_pf && (!f_begin || !f_list)) return psdr::api_fail(who + "the gradient of the point -> face term needs f_begin and f_list, the inverted index of face_of_point");
     if (grad_p && on_fp && (!p_begin || !p_list)) return psdr::api_fail(who + "the gradient of the face -> point term needs p_begin and p_list, the inverted index of point_of_face");
     const double unit = squared ? 2.0 : 1.0;
-    const int bp = on_pf ? blocks_of(n_points) : 0, bf = on_fp ? blocks_of(n_faces) : 0;
+    const int bp = on_pf ? blocks_of<kThreads>(n_points) : 0, bf = on_fp ? blocks_of<kThreads>(n_faces) : 0;
     Eval E;
     E.p = p; E.v = v; E.faces = faces;
     E.np = n_points; E.nv = n_vertices; E.nf = n_faces;
@@ -497,13 +376,11 @@ int psdr_hip_pointmesh_eval(const float *p, int32_t n_points, const float *v, in
     E.grad_p = grad_p; E.grad_v = grad_v; E.corners = grad_p ? corners : nullptr;
     E.partial_p = partial; E.partial_f = partial + bp;
     hipStream_t st = (hipStream_t) stream;
-    if (on_pf || grad_p) k_eval_points<<<blocks_of(n_points), kThreads, 0, st>>>(E);
-    if (on_fp || grad_p) k_eval_faces<<<blocks_of(n_faces), kThreads, 0, st>>>(E);
-    if (grad_p) k_eval_vertices<<<blocks_of(n_vertices), kThreads, 0, st>>>(E);
+    if (on_pf || grad_p) k_eval_points<<<blocks_of<kThreads>(n_points), kThreads, 0, st>>>(E);
+    if (on_fp || grad_p) k_eval_faces<<<blocks_of<kThreads>(n_faces), kThreads, 0, st>>>(E);
+    if (grad_p) k_eval_vertices<<<blocks_of<kThreads>(n_vertices), kThreads, 0, st>>>(E);
     k_finish<<<1, kSumThreads, 0, st>>>(partial, bp, bf, n_points, n_faces, weights[0], weights[1], out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
-    return 0;
+    return launch_status(who);
 }
 
 } // extern "C"

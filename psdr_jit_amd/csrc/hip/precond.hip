@@ -24,8 +24,7 @@
 #include <string>
 
 #include "../../../include/psdr_hip.h"
-
-namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
+#include "op_common.h"
 #define PCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return psdr::api_fail(std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
 namespace {

@@ -5,36 +5,30 @@
 // Oosterom & Strackee's formula, theta = atan2(Nm, Dn) with the principal value 0 where Nm == 0.  The magnitude is not computed here: the nearest face, its barycentrics and
 // dist2 are those of psdr_hip_pointmesh_nearest (pointmesh.hip), which the caller runs as it is.
 //
-// The scan (k_scan<Q>), the skeleton of pointmesh.hip's k_scan.  A lane holds Q points in registers; the faces of the workgroup's slice go through LDS a tile at a time as records
+// The scan (k_scan<Q>).  A lane holds Q points in registers; the faces of the workgroup's slice go through LDS a tile at a time as records
 // of three float4 (the three corners, written once per call by k_records) and every lane reads the same address: a broadcast.  A lane adds its candidates in ascending f into a
 // double and leaves the slice's sum as a float in partial[slice][i]: every entry is written by exactly one lane, nothing is cleared and nothing is atomic.  k_merge adds the
-// slices in ascending order in double, scales by 1 / (2 pi), rounds once, and - given dist2 - writes the signed distance.  The split is psdr_hip_pointmesh_plan's.
+// slices in ascending order in double, scales by 1 / (2 pi), rounds once, and - given dist2 - writes the signed distance.  The split is the point-to-mesh plan's (nn_scan.h).
 // The gradient: k_grad_points (a lane per point), k_grad_faces (a lane per face: the [3, 3] corner record over the points that chose the face, ascending, through the inverted
 // index), k_grad_vertices (a lane per vertex: the corner records that name it, in the topology's order).  No float atomics, no host synchronisation; the same input gives the
 // same bits.  No contraction in this unit (the build's -ffp-contract=off, and the pair function is written with __fmul_rn / __fadd_rn / __fsub_rn); sqrtf is the correctly
 // rounded square root, the compiler's default for HIP (__fsqrt_rn is not: the headers map it to the native one).
-#include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
 #include <string>
 
 #include "../../../include/psdr_hip.h"
-
-namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
+#include "mesh_pair.h"
+#include "nn_scan.h"
 
 namespace {
 
-constexpr int kThreads = 256;           // 4 waves
-constexpr int kTile = 256;              // faces per LDS tile: 12 KiB of records; must be the plan's tile
-constexpr int kWideQueries = 2;         // the plan's queries per lane are 1 or this
-constexpr int kMaxCount = 1 << 26;
+constexpr int kThreads = 256;                   // 4 waves
+constexpr int kTile = pm::kTile;                // faces per LDS tile: 12 KiB of records
+constexpr int kWideQueries = pm::kWideQueries;  // the plan's queries per lane are 1 or this
+static_assert(kThreads == scan::kThreads, "plan_of splits for the scan's workgroup");
 constexpr double kInvTwoPi = 0.15915494309189533576888376337251436;
 
-struct Vec { float x, y, z; };
-
-__device__ __forceinline__ Vec sub(Vec p, Vec q) { return {__fsub_rn(p.x, q.x), __fsub_rn(p.y, q.y), __fsub_rn(p.z, q.z)}; }
-__device__ __forceinline__ float dot(Vec p, Vec q) { return __fadd_rn(__fadd_rn(__fmul_rn(p.x, q.x), __fmul_rn(p.y, q.y)), __fmul_rn(p.z, q.z)); }
-__device__ __forceinline__ float cross2(float a, float b, float c, float d) { return __fsub_rn(__fmul_rn(a, b), __fmul_rn(c, d)); }          // a b - c d
 __device__ __forceinline__ float length(Vec p) { return sqrtf(dot(p, p)); }
 
 // THE PAIR FUNCTION: the half solid angle of the face (A, B, C) seen from p, in (-pi, pi]
@@ -47,10 +41,6 @@ __device__ __forceinline__ float theta(Vec p, Vec A, Vec B, Vec C) {
     const float t = atan2f(nm, dn);                            // (finite for nm == 0 too: a select, not a branch per pair)
     return nm == 0.f ? 0.f : t;
 }
-
-__device__ __forceinline__ int clamped(int i, int count) { return min(max(i, 0), count - 1); }
-
-__device__ __forceinline__ Vec load3(const float *__restrict__ a, int i) { return {a[3LL * i], a[3LL * i + 1], a[3LL * i + 2]}; }
 
 // the per-face records of the scan: [F] x three float4 (A, B, C, 0, 0, 0), vertex ids clamped into [0, nv)
 __global__ void __launch_bounds__(kThreads) k_records(const float *__restrict__ v, int nv, const int *__restrict__ faces, int nf, float4 *__restrict__ rec) {
@@ -117,17 +107,15 @@ struct Grad {
     const float *bary, *sdf, *g;        // [np, 3], [np], [np]
     const int *f_begin, *f_list;        // [nf + 1], [np]: the points that chose a face, ascending
     const int *vc_begin, *vc_corner;    // [nv + 1], [3 nf]: the corners 3 f + c that name a vertex, ascending
-    float *corners, *gp, *gv;           // [nf, 9], [np, 3], [nv, 3]
+    float *corners, *grad_p, *grad_v;   // [nf, 9], [np, 3], [nv, 3]
 };
 
 // (g_i / s_i) r of the pair (point i, face f): r is the point-to-mesh pair function's e = (p - a) - (s ab + t ac) with the stored barycentrics; 0 where s_i == 0
 __device__ __forceinline__ Vec pair_term(const Grad &G, int i, int f) {
-    const Vec a = load3(G.v, clamped(G.faces[3LL * f], G.nv)), b = load3(G.v, clamped(G.faces[3LL * f + 1], G.nv)), c = load3(G.v, clamped(G.faces[3LL * f + 2], G.nv));
-    const Vec ab = sub(b, a), ac = sub(c, a), ap = sub(load3(G.p, i), a);
+    const Face face = load_face(G.v, G.nv, G.faces, f);
+    const Vec ap = sub(load3(G.p, i), face.a);
     const float s = G.bary[3LL * i + 1], t = G.bary[3LL * i + 2];
-    const Vec e = {__fsub_rn(ap.x, __fadd_rn(__fmul_rn(s, ab.x), __fmul_rn(t, ac.x))),
-                   __fsub_rn(ap.y, __fadd_rn(__fmul_rn(s, ab.y), __fmul_rn(t, ac.y))),
-                   __fsub_rn(ap.z, __fadd_rn(__fmul_rn(s, ab.z), __fmul_rn(t, ac.z)))};
+    const Vec e = residual(ap, face, s, t);
     const float sd = G.sdf[i];
     const float k = sd == 0.f ? 0.f : __fdiv_rn(G.g[i], sd);
     return {__fmul_rn(k, e.x), __fmul_rn(k, e.y), __fmul_rn(k, e.z)};
@@ -137,7 +125,7 @@ __global__ void __launch_bounds__(kThreads) k_grad_points(Grad G) {
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= G.np) return;
     const Vec kr = pair_term(G, i, clamped(G.face[i], G.nf));
-    float *o = G.gp + 3LL * i;
+    float *o = G.grad_p + 3LL * i;
     o[0] = kr.x;
     o[1] = kr.y;
     o[2] = kr.z;
@@ -153,7 +141,7 @@ __global__ void __launch_bounds__(kThreads) k_grad_faces(Grad G) {
         const Vec kr = pair_term(G, i, f);
         const float *b = G.bary + 3LL * i;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
+        for (int c = 0; c < 3; ++c) {          // (mesh_pair.h: add_corners, in place)
             sum[3 * c] = __fadd_rn(sum[3 * c], -__fmul_rn(kr.x, b[c]));
             sum[3 * c + 1] = __fadd_rn(sum[3 * c + 1], -__fmul_rn(kr.y, b[c]));
             sum[3 * c + 2] = __fadd_rn(sum[3 * c + 2], -__fmul_rn(kr.z, b[c]));
@@ -164,28 +152,8 @@ __global__ void __launch_bounds__(kThreads) k_grad_faces(Grad G) {
 }
 
 __global__ void __launch_bounds__(kThreads) k_grad_vertices(Grad G) {
-    const int i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= G.nv) return;
-    const int total = 3 * G.nf;
-    const int b0 = min(max(G.vc_begin[i], 0), total), b1 = min(max(G.vc_begin[i + 1], b0), total);
-    float gx = 0.f, gy = 0.f, gz = 0.f;
-    for (int k = b0; k < b1; ++k) {
-        const float *c = G.corners + 3LL * clamped(G.vc_corner[k], total);
-        gx = __fadd_rn(gx, c[0]);
-        gy = __fadd_rn(gy, c[1]);
-        gz = __fadd_rn(gz, c[2]);
-    }
-    float *o = G.gv + 3LL * i;
-    o[0] = gx;
-    o[1] = gy;
-    o[2] = gz;
+    gather_corners<kThreads>(G);
 }
-
-inline int blocks_of(int count) { return (count + kThreads - 1) / kThreads; }
-
-inline bool in_range(long long v) { return v >= 1 && v <= kMaxCount; }
-
-inline std::string range_text(const char *name, long long v) { return std::string(name) + " = " + std::to_string(v) + ", must lie in [1, 2^26]"; }
 
 } // namespace
 
@@ -200,20 +168,15 @@ int psdr_hip_sdf_winding(const float *p, int32_t n_points, const float *v, int32
     if (orientation != 1 && orientation != -1) return psdr::api_fail(who + "orientation = " + std::to_string(orientation) + ", must be +1 (counter-clockwise seen from outside) or -1");
     if (!p || !v || !faces || !records || !partial || !w) return psdr::api_fail(who + "NULL argument");
     if (!dist2 != !sdf) return psdr::api_fail(who + "dist2 and sdf must both be given or both be NULL");
-    int32_t tile, qpl, slices, slice_len;
-    if (psdr_hip_pointmesh_plan(n_points, n_faces, &tile, &qpl, &slices, &slice_len)) return 1;
-    if (tile != kTile || (qpl != 1 && qpl != kWideQueries)) return psdr::api_fail(who + "the plan's tile or queries per lane are not the ones this unit was compiled for");
+    const Plan pl = plan_of<kTile, kWideQueries>(n_points, n_faces);
     hipStream_t st = (hipStream_t) stream;
     float4 *rec = reinterpret_cast<float4 *>(records);
-    const int per_group = kThreads * qpl;
-    const dim3 grid((unsigned) ((n_points + per_group - 1) / per_group), (unsigned) slices);
-    k_records<<<blocks_of(n_faces), kThreads, 0, st>>>(v, n_vertices, faces, n_faces, rec);
-    if (qpl == 1) k_scan<1><<<grid, kThreads, 0, st>>>(p, rec, n_points, n_faces, slice_len, partial);
-    else k_scan<kWideQueries><<<grid, kThreads, 0, st>>>(p, rec, n_points, n_faces, slice_len, partial);
-    k_merge<<<blocks_of(n_points), kThreads, 0, st>>>(partial, n_points, slices, dist2, (float) orientation, w, sdf);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
-    return 0;
+    const dim3 grid = scan_grid(n_points, pl);
+    k_records<<<blocks_of<kThreads>(n_faces), kThreads, 0, st>>>(v, n_vertices, faces, n_faces, rec);
+    if (pl.qpl == 1) k_scan<1><<<grid, kThreads, 0, st>>>(p, rec, n_points, n_faces, pl.slice_len, partial);
+    else k_scan<kWideQueries><<<grid, kThreads, 0, st>>>(p, rec, n_points, n_faces, pl.slice_len, partial);
+    k_merge<<<blocks_of<kThreads>(n_points), kThreads, 0, st>>>(partial, n_points, pl.slices, dist2, (float) orientation, w, sdf);
+    return launch_status(who);
 }
 
 int psdr_hip_sdf_grad(const float *p, int32_t n_points, const float *v, int32_t n_vertices, const int32_t *faces, int32_t n_faces, const int32_t *face, const float *bary,
@@ -230,14 +193,12 @@ int psdr_hip_sdf_grad(const float *p, int32_t n_points, const float *v, int32_t 
     G.np = n_points; G.nv = n_vertices; G.nf = n_faces;
     G.face = face; G.bary = bary; G.sdf = sdf; G.g = g;
     G.f_begin = f_begin; G.f_list = f_list; G.vc_begin = vc_begin; G.vc_corner = vc_corner;
-    G.corners = corners; G.gp = grad_p; G.gv = grad_v;
+    G.corners = corners; G.grad_p = grad_p; G.grad_v = grad_v;
     hipStream_t st = (hipStream_t) stream;
-    k_grad_points<<<blocks_of(n_points), kThreads, 0, st>>>(G);
-    k_grad_faces<<<blocks_of(n_faces), kThreads, 0, st>>>(G);
-    k_grad_vertices<<<blocks_of(n_vertices), kThreads, 0, st>>>(G);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
-    return 0;
+    k_grad_points<<<blocks_of<kThreads>(n_points), kThreads, 0, st>>>(G);
+    k_grad_faces<<<blocks_of<kThreads>(n_faces), kThreads, 0, st>>>(G);
+    k_grad_vertices<<<blocks_of<kThreads>(n_vertices), kThreads, 0, st>>>(G);
+    return launch_status(who);
 }
 
 } // extern "C"

@@ -23,8 +23,7 @@
 #include <string>
 
 #include "../../../include/psdr_hip.h"
-
-namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
+#include "op_common.h"
 
 namespace {
 
@@ -49,19 +48,6 @@ struct Frame {
     float *partial;                     // [tiles][2]: sum m_eff S, sum m_eff
     float *scale;                       // -1 / N of the last eval, 0 if N == 0
 };
-
-// the sum over the workgroup in a fixed order, valid in thread 0: a wave by shuffles, the waves one after the other
-template <int THREADS> __device__ float block_sum(float v, float *s_red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();                                       // (s_red of the previous sum has been read)
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-    if (threadIdx.x == 0)
-        for (int k = 0; k < THREADS / 64; ++k) t += s_red[k];
-    return t;
-}
 
 // the tile's rows and halo of NSRC arrays into NSRC * C planes: plane n C + c holds channel c of array n.  Consecutive lanes read consecutive words of a row.
 template <int C, int K, int NSRC> __device__ __forceinline__ void stage(float *s, const float *const (&src)[NSRC], int W, int H, int tx, int ty) {
@@ -346,8 +332,7 @@ int psdr_hip_ssim_eval(psdr_hip_ssim *h, const float *img, const float *target, 
     case 3: launch_c<3>(h->F, h->K, img, target, mask, out, grad, st); break;
     default: launch_c<4>(h->F, h->K, img, target, mask, out, grad, st); break;
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
+    if (launch_status(who)) return 1;
     h->evaluated = true;
     return 0;
 }

@@ -15,8 +15,7 @@
 #include <string>
 
 #include "../../../include/psdr_hip.h"
-
-namespace psdr { int api_fail(const std::string &msg); }        // api.hip: the message psdr_hip_last_error() returns, -> 1
+#include "op_common.h"
 
 namespace {
 
@@ -73,9 +72,7 @@ int launch(const char *who, const Csr &A, const float *x, int32_t C, float *y, v
     case 3: k_spmv<3><<<blocks, kThreads, 0, s>>>(A, x, y); break;
     default: k_spmv<4><<<blocks, kThreads, 0, s>>>(A, x, y); break;
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return psdr::api_fail(std::string(who) + ": " + hipGetErrorString(e));
-    return 0;
+    return launch_status(std::string(who) + ": ");
 }
 
 // the host-side check of one CSR: "" or what is wrong with it

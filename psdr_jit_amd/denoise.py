@@ -19,18 +19,13 @@ import ctypes as _C
 import torch as _torch
 
 from . import cabi as _cabi
+from ._opcommon import _single_gpu
 
 MAX_GUIDES, MAX_CHANNELS, MAX_LEVELS, MAX_PIXELS = 8, 4, 8, 1 << 24
 
 FIELD_CHANNELS = {"silhouette": 1, "position": 3, "depth": 1, "geoNormal": 3, "shNormal": 3, "uv": 2, "bsdf": 3}          # what a field contributes to the guides
 DEFAULT_SIGMA = {"silhouette": 0.1, "shNormal": 0.25, "geoNormal": 0.25, "bsdf": 0.1}                                      # position, depth, uv: relative, see first_hit_guides
 RELATIVE_SIGMA = 0.05
-
-
-def _single_gpu(what):
-    from . import _shard
-    if _shard()[1] > 1:
-        raise RuntimeError("%s: the denoiser runs on one GPU, torch.distributed is initialised with %d ranks" % (what, _shard()[1]))
 
 
 class _Handle:

@@ -22,19 +22,16 @@ sdf is expected to be finite: nothing checks it (a check would synchronise); a N
 torch.distributed group of more than one rank the calls raise."""
 import collections as _collections
 import ctypes as _C
+import functools as _functools
 import math as _math
 
 import numpy as _np
 
-from .mtet import _as_tensor, _checked_shape
+from ._opcommon import _as_tensor, _ceil_div, _checked_shape, _single_gpu
 
 TILE = (32, 8, 4)          # the vertices of a workgroup's tile (csrc/hip/latreg.hip: kTX, kTY, kTZ)
 
 LatregPlan = _collections.namedtuple("LatregPlan", ["tile", "num_lattice", "num_cells", "workgroups", "scratch_floats"])
-
-
-def _ceil_div(a, b):
-    return -(-a // b)
 
 
 def launch_plan_lr(shape):
@@ -95,7 +92,8 @@ def _checked_scale(sign_scale):
     return k
 
 
-def _make_fn():
+@_functools.lru_cache(maxsize=None)
+def _fn():
     import torch
 
     class _LatRegFn(torch.autograd.Function):
@@ -115,16 +113,6 @@ def _make_fn():
             return None, (g * grad).to(*ctx.like)
 
     return _LatRegFn
-
-
-_FN = None
-
-
-def _fn():
-    global _FN
-    if _FN is None:
-        _FN = _make_fn()
-    return _FN
 
 
 class LatticeRegularizer:
@@ -161,7 +149,6 @@ class LatticeRegularizer:
         import torch
         sdf = self._checked_sdf(sdf)
         w, k = _checked_weights(self.weights), _checked_scale(self.sign_scale)
-        from .denoise import _single_gpu
         _single_gpu("LatticeRegularizer")
         from . import cabi, _device, _stream_ptr
         device = _device()

@@ -21,9 +21,12 @@ The topology (mesh_topology) is numpy and runs once per mesh on the host, usable
 initialised torch.distributed group of more than one rank the calls raise."""
 import collections as _collections
 import ctypes as _C
+import functools as _functools
 import math as _math
 
 import numpy as _np
+
+from ._opcommon import MAX_COUNT, _faces_checked, _single_gpu, _vertex_index
 
 MeshTopology = _collections.namedtuple("MeshTopology", [
     "edges",                    # int32 [e, 2]: the distinct undirected edges (a < b), ascending
@@ -33,41 +36,6 @@ MeshTopology = _collections.namedtuple("MeshTopology", [
     "hinge_begin", "hinge_elem", "hinge_role",          # the same over the hinges: int32 [n + 1], [4 h], [4 h]; role 0 .. 3 = a, b, c, d
 ])
 
-MAX_COUNT = 1 << 26
-
-
-def _faces_checked(faces, n, what):
-    f = _np.asarray(faces)
-    if f.size == 0:
-        f = _np.zeros((0, 3), dtype=_np.int64)
-    if f.ndim != 2 or f.shape[1] != 3:
-        raise ValueError("%s: faces must be [f, 3], got shape %s" % (what, tuple(f.shape)))
-    if not _np.issubdtype(f.dtype, _np.integer):
-        raise ValueError("%s: faces must hold integer ids" % what)
-    f = f.astype(_np.int64)
-    if n <= 0:
-        raise ValueError("%s: the number of vertices must be positive" % what)
-    if n > MAX_COUNT:
-        raise ValueError("%s: %d vertices, at most 2^26" % (what, n))
-    if f.size and (f.min() < 0 or f.max() >= n):
-        raise ValueError("%s: an id is outside [0, %d)" % (what, n))
-    bad = _np.nonzero((f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 2] == f[:, 0]))[0]
-    if bad.size:
-        raise ValueError("%s: face %d repeats a vertex id: %s" % (what, int(bad[0]), f[bad[0]].tolist()))
-    return f
-
-
-def _inverted(table, n):
-    """per vertex the (element, role) pairs of `table` [count, roles] that name it, in ascending (element, role) order: (begin [n + 1], elem, role)"""
-    count, roles = table.shape
-    vertex = table.reshape(-1)
-    code = _np.arange(count * roles, dtype=_np.int64)              # element * roles + role: ascending in both
-    order = _np.argsort(vertex, kind="stable")                     # by vertex; inside a vertex the codes keep their ascending order
-    begin = _np.zeros(n + 1, dtype=_np.int64)
-    _np.cumsum(_np.bincount(vertex, minlength=n), out=begin[1:])
-    code = code[order]
-    i32 = _np.int32
-    return begin.astype(i32), (code // roles).astype(i32), (code % roles).astype(i32)
 
 
 def mesh_topology(faces, num_vertices):
@@ -99,8 +67,8 @@ def mesh_topology(faces, num_vertices):
     two = m == 2
     c, d = opp[by_edge[first[two]]], opp[by_edge[first[two] + 1]]
     hinges = _np.concatenate([edges[two], _np.stack([c, d], 1).reshape(-1, 2)], 1).reshape(-1, 4)
-    eb, ee, er = _inverted(edges, n)
-    hb_, he, hr = _inverted(hinges, n)
+    eb, ee, er = _vertex_index(edges, n)
+    hb_, he, hr = _vertex_index(hinges, n)
     i32 = _np.int32
     return MeshTopology(_np.ascontiguousarray(edges.astype(i32)), _np.ascontiguousarray(hinges.astype(i32)), int((m == 1).sum()), int((m >= 3).sum()),
                         eb, ee, er, hb_, he, hr)
@@ -143,7 +111,8 @@ class _Handle:
             self.ptr = None
 
 
-def _make_fn():
+@_functools.lru_cache(maxsize=None)
+def _fn():
     import torch
 
     class _MeshRegFn(torch.autograd.Function):
@@ -163,16 +132,6 @@ def _make_fn():
             return None, (g * grad).to(*ctx.like)
 
     return _MeshRegFn
-
-
-_FN = None
-
-
-def _fn():
-    global _FN
-    if _FN is None:
-        _FN = _make_fn()
-    return _FN
 
 
 class MeshRegularizer:
@@ -207,7 +166,6 @@ class MeshRegularizer:
         from .precond import laplacian_csr
         self.row_begin, self.col = laplacian_csr(_faces_checked(faces, self.num_vertices, "MeshRegularizer"), self.num_vertices)
         self.terms = None
-        from .denoise import _single_gpu
         _single_gpu("MeshRegularizer")
         from . import _device, _stream_ptr
         import torch
@@ -219,7 +177,6 @@ class MeshRegularizer:
         """-> (out [4]: the loss and the three terms, dloss / dv [n, 3] or None), on the current stream"""
         import torch
         from . import cabi, _stream_ptr
-        from .denoise import _single_gpu
         _single_gpu("MeshRegularizer")
         w, t = _checked_weights(self.weights), _checked_length(self.target_length)
         if not isinstance(v, torch.Tensor) or tuple(v.shape) != (self.num_vertices, 3) or not v.is_floating_point():

@@ -14,6 +14,9 @@ loss = sum_l lambda_l level_loss_l.  Three launches give the loss, the level los
 
 One GPU only: under an initialised torch.distributed group of more than one rank the calls raise."""
 import ctypes as _C
+import functools as _functools
+
+from ._opcommon import _single_gpu
 
 NORMS = {"l1": 0, "l2": 1}          # PSDR_MSLOSS_L1, PSDR_MSLOSS_L2
 MAX_CHANNELS, MAX_SIDE, MAX_PIXELS = 4, 16384, 1 << 24
@@ -49,7 +52,8 @@ class _Handle:
             self.ptr = None
 
 
-def _make_fn():
+@_functools.lru_cache(maxsize=None)
+def _fn():
     import torch
 
     class _MultiScaleLossFn(torch.autograd.Function):
@@ -70,16 +74,6 @@ def _make_fn():
             return (None, gi.to(*ctx.like[0]) if ctx.needs_input_grad[1] else None, (-gi).to(*ctx.like[1]) if ctx.needs_input_grad[2] else None, None)
 
     return _MultiScaleLossFn
-
-
-_FN = None
-
-
-def _fn():
-    global _FN
-    if _FN is None:
-        _FN = _make_fn()
-    return _FN
 
 
 class MultiScaleLoss:
@@ -113,7 +107,6 @@ class MultiScaleLoss:
         self.level_weights = tuple(level_weights)
         self._lambda = (_C.c_float * self.levels)(*level_weights)
         self.level_losses = None
-        from .denoise import _single_gpu
         _single_gpu("MultiScaleLoss")
         from . import _device, _stream_ptr
         import torch
@@ -132,7 +125,6 @@ class MultiScaleLoss:
         """-> (out [1 + L]: the loss and the level losses, dloss / dimg [W H, C] or None), on the current stream"""
         import torch
         from . import cabi, _stream_ptr
-        from .denoise import _single_gpu
         _single_gpu("MultiScaleLoss")
         n = self.width * self.height
         img, target = self._image(img, "img"), self._image(target, "target")

@@ -21,34 +21,17 @@ pass is one gather per lattice vertex over fourteen fixed slots: no sort, no inv
 EXTRACT AT EVERY STEP.  mt(sdf, pos) evaluates the formula on the edges of the LAST extract.  If the signs of sdf have changed since, it still does - with t outside [0, 1] on
 the edges that no longer cross - and the mesh is no longer the isosurface.  One GPU only: under an initialised torch.distributed group of more than one rank the calls raise."""
 import collections as _collections
+import functools as _functools
 
 import numpy as _np
 
-MAX_LATTICE = 1 << 24
+from ._opcommon import MAX_LATTICE, _as_tensor, _ceil_div, _checked_shape, _single_gpu  # noqa: F401
+
 TILE = 256          # entries per workgroup of the scans (csrc/hip/mtet.hip: kThreads)
 WAVE = 64
 
 MtetTopology = _collections.namedtuple("MtetTopology", ["faces", "edges", "num_vertices", "num_faces"])
 MtetPlan = _collections.namedtuple("MtetPlan", ["tile", "wave", "num_lattice", "num_cells", "vertex_blocks", "cell_blocks", "vertex_passes", "cell_passes", "scratch_ints"])
-
-
-def _ceil_div(a, b):
-    return -(-a // b)
-
-
-def _checked_shape(shape, what):
-    try:
-        s = tuple(shape)
-    except TypeError:
-        raise ValueError("%s: shape must be three integers (nx, ny, nz), got %r" % (what, shape)) from None
-    if len(s) != 3 or any(isinstance(n, bool) or not isinstance(n, (int, _np.integer)) for n in s):
-        raise ValueError("%s: shape must be three integers (nx, ny, nz), got %r" % (what, shape))
-    s = tuple(int(n) for n in s)
-    if min(s) < 2:
-        raise ValueError("%s: shape = %r, every extent must be at least 2" % (what, s))
-    if s[0] * s[1] * s[2] > MAX_LATTICE:
-        raise ValueError("%s: shape = %r has %d lattice vertices, at most 2^24" % (what, s, s[0] * s[1] * s[2]))
-    return s
 
 
 def launch_plan_mt(shape):
@@ -80,12 +63,8 @@ def lattice_points(shape, lo=-1.0, hi=1.0):
     return torch.from_numpy(_np.stack([x.ravel(), y.ravel(), z.ravel()], 1).astype(_np.float32))
 
 
-def _as_tensor(a):
-    import torch
-    return a if isinstance(a, torch.Tensor) else torch.as_tensor(_np.asarray(a))
-
-
-def _make_fn():
+@_functools.lru_cache(maxsize=None)
+def _fn():
     import torch
 
     class _MtetFn(torch.autograd.Function):
@@ -107,16 +86,6 @@ def _make_fn():
             return None, gs.to(*ctx.like[0]) if ctx.needs_input_grad[1] else None, gp.to(*ctx.like[1]) if ctx.needs_input_grad[2] else None
 
     return _MtetFn
-
-
-_FN = None
-
-
-def _fn():
-    global _FN
-    if _FN is None:
-        _FN = _make_fn()
-    return _FN
 
 
 class _State:
@@ -166,7 +135,6 @@ class MarchingTetrahedra:
 
     @staticmethod
     def _render_device():
-        from .denoise import _single_gpu
         _single_gpu("MarchingTetrahedra")
         from . import _device
         return _device()

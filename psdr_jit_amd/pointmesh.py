@@ -23,27 +23,22 @@ queries in registers and stream the candidates through LDS; nothing of size N x 
 A face of zero area or with an edge of zero length gives a finite point of the triangle, never a NaN; it is the closest point except where a face's first two vertices
 coincide in position, where the cascade returns that vertex.
 
-launch_plan_pm(n_queries, n_candidates) is the scans' split into query blocks x candidate slices, stated a second time in C (psdr_hip_pointmesh_plan); the result does not
+launch_plan_pm(n_queries, n_candidates) is the scans' split into query blocks x candidate slices, which psdr_hip_pointmesh_plan states in C; the result does not
 depend on it.  One GPU only: under an initialised torch.distributed group of more than one rank the calls raise."""
 import collections as _collections
 import ctypes as _C
+import functools as _functools
 import math as _math
 
 import numpy as _np
 
-MAX_COUNT = 1 << 26
-THREADS = 256                # lanes of a workgroup
+from ._opcommon import MAX_COUNT, NARROW_MAX, TARGET_GROUPS, SCAN_THREADS as THREADS, _ceil_div, _checked_points, _faces_checked, _inverted, _single_gpu, _vertex_index, slice_plan  # noqa: F401
+
 TILE = 256                   # candidates per LDS tile
 WIDE_QUERIES = 2             # queries per lane for n_queries > NARROW_MAX, else 1
-NARROW_MAX = 1024
-TARGET_GROUPS = 2048         # workgroups the grid aims at (section 7k's constant)
 
 LaunchPlan = _collections.namedtuple("LaunchPlan", ["tile", "queries_per_lane", "slices", "slice_len"])
 Nearest = _collections.namedtuple("Nearest", ["face_of_point", "bary_p", "dist2_p", "point_of_face", "bary_f", "dist2_f"])
-
-
-def _ceil_div(a, b):
-    return -(-a // b)
 
 
 def launch_plan_pm(n_queries, n_candidates):
@@ -52,14 +47,7 @@ def launch_plan_pm(n_queries, n_candidates):
     A workgroup holds 256 queries_per_lane queries; slice s holds the candidates [s slice_len, min(n_candidates, (s + 1) slice_len)); the grid is query blocks x slices.
     The same split serves both scans: points against faces and faces against points."""
     n, m = int(n_queries), int(n_candidates)
-    if not (1 <= n <= MAX_COUNT and 1 <= m <= MAX_COUNT):
-        raise ValueError("launch_plan_pm: n_queries = %d, n_candidates = %d, both must lie in [1, 2^26]" % (n, m))
-    qpl = WIDE_QUERIES if n > NARROW_MAX else 1
-    qblocks = _ceil_div(n, THREADS * qpl)
-    tiles = _ceil_div(m, TILE)
-    want = min(_ceil_div(TARGET_GROUPS, qblocks), tiles)
-    slice_len = _ceil_div(tiles, want) * TILE
-    return LaunchPlan(TILE, qpl, _ceil_div(m, slice_len), slice_len)
+    return LaunchPlan(*slice_plan(n, m, TILE, WIDE_QUERIES, "launch_plan_pm: n_queries = %d, n_candidates = %d, both must lie in [1, 2^26]" % (n, m)))
 
 
 def _checked_weights(weights):
@@ -81,7 +69,6 @@ def _checked_faces(mesh_or_faces, num_vertices, what):
         faces = _np.asarray(mesh_or_faces)
         if num_vertices is None:
             raise ValueError("%s: num_vertices is required with a face array" % what)
-    from .meshreg import _faces_checked
     f = _faces_checked(faces, int(num_vertices), what)
     if f.shape[0] == 0:
         raise ValueError("%s: the mesh has no faces" % what)
@@ -115,6 +102,48 @@ def _scan(points, v, faces, direction, device):
     return index, bary, dist2
 
 
+def _function_arguments(points, v, faces, what):
+    """the argument rules of closest_points_on_mesh (and of sdf.py's functions), before a device is looked for -> (points, v, faces on a GPU or None, host faces int64 or
+    None)"""
+    import torch
+    points = _checked_points(points, what, "points")
+    if not hasattr(v, "shape") or len(v.shape) != 2 or int(v.shape[0]) < 1:
+        raise ValueError("%s: v must be [n, 3] with n >= 1" % what)
+    n = int(v.shape[0])
+    v = _checked_vertices(v, n, what)
+    if isinstance(faces, torch.Tensor) and faces.is_cuda:
+        if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not 1 <= faces.shape[0] <= MAX_COUNT:
+            raise ValueError("%s: faces on the GPU must be an int32 [F, 3] tensor with 1 <= F <= 2^26, got %s %s" % (what, faces.dtype, tuple(faces.shape)))
+        if n > MAX_COUNT:
+            raise ValueError("%s: %d vertices, at most 2^26" % (what, n))
+        return points, v, faces, None
+    f, n = _checked_faces(faces.detach().numpy() if isinstance(faces, torch.Tensor) else faces, n, what)
+    return points, v, None, f
+
+
+def _on_device(points, v, faces_gpu, faces_host, what):
+    """-> (device, points, v, faces) float32 / int32 contiguous on the render device"""
+    import torch
+    _single_gpu(what)
+    from . import _device
+    device = _device()
+    with torch.cuda.device(device):
+        fd = faces_gpu.to(device).contiguous() if faces_host is None else torch.from_numpy(_np.ascontiguousarray(faces_host, _np.int32)).to(device)
+        return device, points.detach().to(device, torch.float32).contiguous(), v.detach().to(device, torch.float32).contiguous(), fd
+
+
+def _device_topology(obj, device):
+    """(faces int32 [F, 3], vc_begin int32 [n + 1], vc_corner int32 [3 F]) of obj.faces / obj.num_vertices on `device`: uploaded once per object, kept in obj._topology (the
+    copies are ordered on the current stream)"""
+    import torch
+    if obj._topology is None or obj._topology[0] != device:
+        begin, elem, role = _vertex_index(obj.faces, obj.num_vertices)
+        corner = (3 * elem.astype(_np.int64) + role).astype(_np.int32)
+        up = lambda a: torch.from_numpy(_np.ascontiguousarray(a, _np.int32)).to(device)
+        obj._topology = (device, up(obj.faces), up(begin), up(corner))
+    return obj._topology[1:]
+
+
 def closest_points_on_mesh(points, v, faces):
     """For every point the lowest index of its nearest face, the barycentrics of the closest point on it and the squared distance: (face int32 [N], bary float32 [N, 3],
     dist2 float32 [N]) on the render device, detached, computed on torch's current stream without a host synchronisation.  points [N, 3] and v [n, 3] on any device and of
@@ -123,31 +152,14 @@ def closest_points_on_mesh(points, v, faces):
     faces on the host (an array, a list, a CPU tensor) are checked like a mesh's (a repeated or out-of-range id is a ValueError) and uploaded at every call, which waits
     for the copy; an int32 tensor that already lies on a GPU is used as it is - the kernels clamp every id into range - and then nothing synchronises."""
     import torch
-    from .chamfer import _checked_points
     what = "closest_points_on_mesh"
-    points = _checked_points(points, what, "points")
-    if not hasattr(v, "shape") or len(v.shape) != 2 or int(v.shape[0]) < 1:
-        raise ValueError("%s: v must be [n, 3] with n >= 1" % what)
-    n = int(v.shape[0])
-    v = _checked_vertices(v, n, what)
-    on_device = isinstance(faces, torch.Tensor) and faces.is_cuda
-    if on_device:
-        if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not 1 <= faces.shape[0] <= MAX_COUNT:
-            raise ValueError("%s: faces on the GPU must be an int32 [F, 3] tensor with 1 <= F <= 2^26, got %s %s" % (what, faces.dtype, tuple(faces.shape)))
-        if n > MAX_COUNT:
-            raise ValueError("%s: %d vertices, at most 2^26" % (what, n))
-    else:
-        f, n = _checked_faces(faces.detach().numpy() if isinstance(faces, torch.Tensor) else faces, n, what)
-    from .denoise import _single_gpu
-    _single_gpu(what)
-    from . import _device
-    device = _device()
+    device, p, vd, fd = _on_device(*_function_arguments(points, v, faces, what), what)
     with torch.cuda.device(device):
-        fd = faces.to(device).contiguous() if on_device else torch.from_numpy(_np.ascontiguousarray(f, _np.int32)).to(device)
-        return _scan(points.detach().to(device, torch.float32).contiguous(), v.detach().to(device, torch.float32).contiguous(), fd, 0, device)
+        return _scan(p, vd, fd, 0, device)
 
 
-def _make_fn():
+@_functools.lru_cache(maxsize=None)
+def _fn():
     import torch
 
     class _PointMeshFn(torch.autograd.Function):
@@ -166,16 +178,6 @@ def _make_fn():
             return None, (g * gp).to(*ctx.like[0]) if ctx.needs_input_grad[1] else None, (g * gv).to(*ctx.like[1]) if ctx.needs_input_grad[2] else None
 
     return _PointMeshFn
-
-
-_FN = None
-
-
-def _fn():
-    global _FN
-    if _FN is None:
-        _FN = _make_fn()
-    return _FN
 
 
 class PointMeshDistance:
@@ -199,23 +201,10 @@ class PointMeshDistance:
         self.terms = self.nearest = None
         self._topology = None
 
-    def _device_topology(self, device):
-        """(faces int32 [F, 3], vc_begin int32 [n + 1], vc_corner int32 [3 F]) on `device`: uploaded once per object (the copies are ordered on the current stream)"""
-        import torch
-        if self._topology is None or self._topology[0] != device:
-            from .meshreg import _inverted
-            begin, elem, role = _inverted(self.faces, self.num_vertices)
-            corner = (3 * elem.astype(_np.int64) + role).astype(_np.int32)
-            up = lambda a: torch.from_numpy(_np.ascontiguousarray(a, _np.int32)).to(device)
-            self._topology = (device, up(self.faces), up(begin), up(corner))
-        return self._topology[1:]
-
     def _eval(self, points, v, want_grad):
         """-> (out [3]: the loss and the two direction means, dloss / dpoints [N, 3] or None, dloss / dv [n, 3] or None), on the current stream"""
         w = _checked_weights(self.weights)
-        from .chamfer import _checked_points, _inverted
         points, v = _checked_points(points, "PointMeshDistance", "points"), _checked_vertices(v, self.num_vertices, "PointMeshDistance")
-        from .denoise import _single_gpu
         _single_gpu("PointMeshDistance")
         import torch
         from . import cabi, _device, _stream_ptr
@@ -224,7 +213,7 @@ class PointMeshDistance:
         N, n, F = int(points.shape[0]), self.num_vertices, int(self.faces.shape[0])
         ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(device):
-            faces, vc_begin, vc_corner = self._device_topology(device)
+            faces, vc_begin, vc_corner = _device_topology(self, device)
             fop = bp = dp = pof = bf = df = pb = pl = fb = fl = None
             if w[0] > 0.0:
                 fop, bp, dp = _scan(points, v, faces, 0, device)
@@ -248,7 +237,6 @@ class PointMeshDistance:
 
     def __call__(self, points, v):
         """the loss, a 0-d tensor"""
-        from .chamfer import _checked_points
         return _fn().apply(self, _checked_points(points, "PointMeshDistance", "points"), _checked_vertices(v, self.num_vertices, "PointMeshDistance"))
 
     def value_and_grad(self, points, v):

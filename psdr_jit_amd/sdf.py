@@ -24,10 +24,12 @@ the same input gives the same bits.
 The winding scan splits the faces into the slices of launch_plan_pm(N, F) and adds slice sums in ascending order, so the last bits of w depend on that plan - a pure function of
 (N, F).  Nothing of size N x F exists and nothing synchronises with the host.  One GPU only: under an initialised torch.distributed group of more than one rank the calls raise."""
 import collections as _collections
+import functools as _functools
 
 import numpy as _np
 
-from .pointmesh import MAX_COUNT, _checked_faces, _checked_vertices, _scan, launch_plan_pm
+from ._opcommon import _checked_points, _inverted, _single_gpu
+from .pointmesh import _checked_faces, _checked_vertices, _device_topology, _function_arguments, _on_device, _scan, launch_plan_pm
 
 SignedDistanceResult = _collections.namedtuple("SignedDistanceResult", ["sdf", "winding", "face", "bary", "dist2"])
 Nearest = _collections.namedtuple("Nearest", ["face", "bary", "dist2"])
@@ -51,37 +53,6 @@ def _winding(points, v, faces, dist2, orientation, device):
     cabi.check(cabi.lib().psdr_hip_sdf_winding(points.data_ptr(), N, v.data_ptr(), n, faces.data_ptr(), F, records.data_ptr(), partial.data_ptr(),
                                                None if dist2 is None else dist2.data_ptr(), orientation, w.data_ptr(), None if s is None else s.data_ptr(), _stream_ptr()))
     return w, s
-
-
-def _function_arguments(points, v, faces, what):
-    """the argument rules of closest_points_on_mesh, before a device is looked for -> (points, v, faces on a GPU or None, host faces int64 or None)"""
-    import torch
-    from .chamfer import _checked_points
-    points = _checked_points(points, what, "points")
-    if not hasattr(v, "shape") or len(v.shape) != 2 or int(v.shape[0]) < 1:
-        raise ValueError("%s: v must be [n, 3] with n >= 1" % what)
-    n = int(v.shape[0])
-    v = _checked_vertices(v, n, what)
-    if isinstance(faces, torch.Tensor) and faces.is_cuda:
-        if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not 1 <= faces.shape[0] <= MAX_COUNT:
-            raise ValueError("%s: faces on the GPU must be an int32 [F, 3] tensor with 1 <= F <= 2^26, got %s %s" % (what, faces.dtype, tuple(faces.shape)))
-        if n > MAX_COUNT:
-            raise ValueError("%s: %d vertices, at most 2^26" % (what, n))
-        return points, v, faces, None
-    f, n = _checked_faces(faces.detach().numpy() if isinstance(faces, torch.Tensor) else faces, n, what)
-    return points, v, None, f
-
-
-def _on_device(points, v, faces_gpu, faces_host, what):
-    """-> (device, points, v, faces) float32 / int32 contiguous on the render device"""
-    import torch
-    from .denoise import _single_gpu
-    _single_gpu(what)
-    from . import _device
-    device = _device()
-    with torch.cuda.device(device):
-        fd = faces_gpu.to(device).contiguous() if faces_host is None else torch.from_numpy(_np.ascontiguousarray(faces_host, _np.int32)).to(device)
-        return device, points.detach().to(device, torch.float32).contiguous(), v.detach().to(device, torch.float32).contiguous(), fd
 
 
 def winding_number(points, v, faces):
@@ -114,7 +85,8 @@ def signed_distance(points, v, faces, orientation=1):
     return SignedDistanceResult(s, w, face, bary, dist2)
 
 
-def _make_fn():
+@_functools.lru_cache(maxsize=None)
+def _fn():
     import torch
 
     class _SignedDistanceFn(torch.autograd.Function):
@@ -135,16 +107,6 @@ def _make_fn():
             return None, gp.to(*ctx.like[0]) if ctx.needs_input_grad[1] else None, gv.to(*ctx.like[1]) if ctx.needs_input_grad[2] else None
 
     return _SignedDistanceFn
-
-
-_FN = None
-
-
-def _fn():
-    global _FN
-    if _FN is None:
-        _FN = _make_fn()
-    return _FN
 
 
 class SignedDistance:
@@ -169,32 +131,19 @@ class SignedDistance:
         self.winding = self.nearest = None
         self._topology = None
 
-    def _device_topology(self, device):
-        """(faces int32 [F, 3], vc_begin int32 [n + 1], vc_corner int32 [3 F]) on `device`: uploaded once per object (the copies are ordered on the current stream)"""
-        import torch
-        if self._topology is None or self._topology[0] != device:
-            from .meshreg import _inverted
-            begin, elem, role = _inverted(self.faces, self.num_vertices)
-            corner = (3 * elem.astype(_np.int64) + role).astype(_np.int32)
-            up = lambda a: torch.from_numpy(_np.ascontiguousarray(a, _np.int32)).to(device)
-            self._topology = (device, up(self.faces), up(begin), up(corner))
-        return self._topology[1:]
-
     def _checked(self, points, v):
-        from .chamfer import _checked_points
         return _checked_points(points, "SignedDistance", "points"), _checked_vertices(v, self.num_vertices, "SignedDistance"), _checked_orientation(self.orientation, "SignedDistance")
 
     def _forward(self, points, v):
         """-> (device, points, v float32 on it, s [N], face [N], bary [N, 3]), on the current stream"""
         points, v, orientation = self._checked(points, v)
-        from .denoise import _single_gpu
         _single_gpu("SignedDistance")
         import torch
         from . import _device
         device = _device()
         p, vd = points.detach().to(device, torch.float32).contiguous(), v.detach().to(device, torch.float32).contiguous()
         with torch.cuda.device(device):
-            faces = self._device_topology(device)[0]
+            faces = _device_topology(self, device)[0]
             face, bary, dist2 = _scan(p, vd, faces, 0, device)
             w, s = _winding(p, vd, faces, dist2, orientation, device)
         self.winding, self.nearest = w, Nearest(face, bary, dist2)
@@ -204,10 +153,9 @@ class SignedDistance:
         """the vector-Jacobian product for g float32 [N] on `device` -> (gp [N, 3], gv [n, 3]), on the current stream"""
         import torch
         from . import cabi, _stream_ptr
-        from .chamfer import _inverted
         N, n, F = int(p.shape[0]), self.num_vertices, int(self.faces.shape[0])
         with torch.cuda.device(device):
-            faces, vc_begin, vc_corner = self._device_topology(device)
+            faces, vc_begin, vc_corner = _device_topology(self, device)
             f_begin, f_list = _inverted(face, F)
             gp, gv = torch.empty_like(p), torch.empty_like(vd)
             corners = torch.empty((F, 9), device=device, dtype=torch.float32)

@@ -18,7 +18,10 @@ atomics: the same input gives the same bits.
 SSIM assumes a bounded range: tone-map HDR renders into [0, data_range] first.  One GPU only: under an initialised torch.distributed group of more than one rank the
 calls raise."""
 import ctypes as _C
+import functools as _functools
 import math as _math
+
+from ._opcommon import _single_gpu
 
 PADDINGS = {"same": 0, "valid": 1}          # PSDR_SSIM_SAME, PSDR_SSIM_VALID
 MAX_CHANNELS, MAX_SIDE, MAX_PIXELS = 4, 16384, 1 << 24
@@ -56,7 +59,8 @@ class _Handle:
             self.ptr = None
 
 
-def _make_fn():
+@_functools.lru_cache(maxsize=None)
+def _fn():
     import torch
 
     class _SSIMLossFn(torch.autograd.Function):
@@ -76,16 +80,6 @@ def _make_fn():
             return None, (g * grad).to(*ctx.like) if ctx.needs_input_grad[1] else None, None, None
 
     return _SSIMLossFn
-
-
-_FN = None
-
-
-def _fn():
-    global _FN
-    if _FN is None:
-        _FN = _make_fn()
-    return _FN
 
 
 class SSIMLoss:
@@ -128,7 +122,6 @@ class SSIMLoss:
         self.width, self.height, self.channels, self.window, self.sigma, self.padding = width, height, channels, window, float(sigma), padding
         self.data_range, self.k1, self.k2, self.c1, self.c2 = data_range, k1, k2, c1, c2
         self.ssim = None
-        from .denoise import _single_gpu
         _single_gpu("SSIMLoss")
         from . import _device, _stream_ptr
         import torch
@@ -146,7 +139,6 @@ class SSIMLoss:
         """-> (out [2]: the loss and the mean SSIM, dloss / dimg [W H, C] or None), on the current stream"""
         import torch
         from . import cabi, _stream_ptr
-        from .denoise import _single_gpu
         _single_gpu("SSIMLoss")
         n = self.width * self.height
         # every argument is looked at before the first one is moved to the device

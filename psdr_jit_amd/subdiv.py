@@ -15,6 +15,7 @@ the same input gives the same bits, forward and backward.
 """
 import collections as _collections
 import ctypes as _C
+import functools as _functools
 
 import numpy as _np
 
@@ -150,7 +151,8 @@ class _Handle:
             self.ptr = None
 
 
-def _make_fn():
+@_functools.lru_cache(maxsize=None)
+def _fn():
     """the autograd function, made on first use: subdivision_level() needs neither torch nor the native library"""
     import torch
 
@@ -167,16 +169,6 @@ def _make_fn():
             return None, None, None, ctx.sub._run(g, ctx.uv, not ctx.adjoint).to(*ctx.like)
 
     return _ChainFn
-
-
-_FN = None
-
-
-def _fn():
-    global _FN
-    if _FN is None:
-        _FN = _make_fn()
-    return _FN
 
 
 class Subdivision:

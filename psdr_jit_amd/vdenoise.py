@@ -34,7 +34,8 @@ import math as _math
 import torch as _torch
 
 from . import cabi as _cabi
-from .denoise import _Handle, _frame_guides, _single_gpu
+from ._opcommon import _single_gpu
+from .denoise import _Handle, _frame_guides
 
 REC709 = (0.2126, 0.7152, 0.0722)
 

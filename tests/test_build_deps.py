@@ -50,6 +50,14 @@ def test_every_included_header_is_in_its_units_dependency_list():
         assert ({os.path.realpath(src)} | listed) <= whole, "unit %s: %s not in HIP_SRCS + HIP_DEPS" % (name, sorted(({os.path.realpath(src)} | listed) - whole))
 
 
+def test_the_operator_units_are_one_list_compiled_in_this_order():
+    b = _load_build()
+    names = [u[0] for u in b.hip_units()]
+    order = ["precond", "adaptive", "denoise", "vdenoise", "subdiv", "msloss", "ssim", "meshreg", "chamfer", "sdf", "mtet", "latreg", "pointmesh"]
+    assert [u[0] for u in b.OPERATOR_UNITS] == order
+    assert names[names.index("scene") + 1:] == order          # after the host, kernel and scene units, and nothing after them
+
+
 def test_no_kernel_unit_depends_on_the_host_source():
     b = _load_build()
     api = os.path.realpath(b.API_SRC)

@@ -81,9 +81,10 @@ def test_entry_points_declared_exported_listed(psdr):
         assert hasattr(psdr, name)
     units = {u[0]: u for u in build.hip_units()}
     assert units["chamfer"][1].endswith("chamfer.hip") and units["chamfer"][1] in build.HIP_SRCS
-    assert [u[0] for u in build.MESH_OPERATOR_UNITS] == ["meshreg", "chamfer"]
+    names = [u[0] for u in build.hip_units()]
+    assert names.index("meshreg") + 1 == names.index("chamfer") and names.index("ssim") + 1 == names.index("meshreg")
     deps = {os.path.relpath(d, ROOT) for d in units["chamfer"][3]}
-    assert {os.path.join("include", "psdr_hip.h"), os.path.join("psdr_jit_amd", "isa_lint.py")} <= deps
+    assert {os.path.join("include", "psdr_hip.h"), os.path.join("psdr_jit_amd", "csrc", "hip", "nn_scan.h"), os.path.join("psdr_jit_amd", "csrc", "hip", "op_common.h"), os.path.join("psdr_jit_amd", "isa_lint.py")} <= deps
     contract = text[text.index("THE STREAM CONTRACT"):text.index("const char *psdr_hip_last_error")]
     assert "psdr_hip_chamfer_nearest" in contract and "psdr_hip_chamfer_eval" in contract and "psdr_hip_chamfer_plan" in contract
 

@@ -142,7 +142,7 @@ def test_entry_points_declared_exported_listed(psdr):
     units = {u[0]: u for u in build.hip_units()}
     assert units["meshreg"][1].endswith("meshreg.hip") and units["meshreg"][1] in build.HIP_SRCS
     deps = {os.path.relpath(d, ROOT) for d in units["meshreg"][3]}
-    assert {os.path.join("include", "psdr_hip.h"), os.path.join("psdr_jit_amd", "isa_lint.py")} <= deps
+    assert {os.path.join("include", "psdr_hip.h"), os.path.join("psdr_jit_amd", "csrc", "hip", "op_common.h"), os.path.join("psdr_jit_amd", "isa_lint.py")} <= deps
     # the stream contract names the handle: rule 3 (creates) and rule 5 (handles that own work frames)
     assert re.search(r"\*\s+3\. Every psdr_hip_\*_create \([^)]*meshreg[^)]*\)", text)
     assert re.search(r"\*\s+5\. [^\n]*\n[^\n]*meshreg handle", text)

@@ -40,7 +40,7 @@ def test_entry_points_declared_exported_listed(psdr):
     units = {u[0]: u for u in build.hip_units()}
     assert units["msloss"][1].endswith("msloss.hip")
     deps = {os.path.relpath(d, ROOT) for d in units["msloss"][3]}
-    assert {os.path.join("include", "psdr_hip.h"), os.path.join("psdr_jit_amd", "isa_lint.py")} <= deps
+    assert {os.path.join("include", "psdr_hip.h"), os.path.join("psdr_jit_amd", "csrc", "hip", "op_common.h"), os.path.join("psdr_jit_amd", "isa_lint.py")} <= deps
     # the stream contract names the handle: rule 3 (creates) and rule 5 (handles that own work frames)
     assert re.search(r"\*\s+3\. Every psdr_hip_\*_create \([^)]*msloss[^)]*\)", text)
     assert re.search(r"\*\s+5\. [^\n]*msloss handle owns work frames", text)

@@ -41,9 +41,9 @@ def test_entry_points_declared_exported_listed(psdr):
         assert hasattr(psdr, name)
     units = {u[0]: u for u in build.hip_units()}
     assert units["pointmesh"][1].endswith("pointmesh.hip") and units["pointmesh"][1] in build.HIP_SRCS
-    assert [u[0] for u in build.MESH_DISTANCE_UNITS] == ["pointmesh"] and [u[0] for u in build.hip_units()][-1] == "pointmesh"
+    assert [u[0] for u in build.OPERATOR_UNITS][-1] == "pointmesh" and [u[0] for u in build.hip_units()].count("pointmesh") == 1 and [u[0] for u in build.hip_units()][-1] == "pointmesh"
     deps = {os.path.relpath(d, ROOT) for d in units["pointmesh"][3]}
-    assert {os.path.join("include", "psdr_hip.h"), os.path.join("psdr_jit_amd", "isa_lint.py")} <= deps
+    assert {os.path.join("include", "psdr_hip.h"), os.path.join("psdr_jit_amd", "csrc", "hip", "mesh_pair.h"), os.path.join("psdr_jit_amd", "csrc", "hip", "nn_scan.h"), os.path.join("psdr_jit_amd", "csrc", "hip", "op_common.h"), os.path.join("psdr_jit_amd", "isa_lint.py")} <= deps
     contract = text[text.index("THE STREAM CONTRACT"):text.index("const char *psdr_hip_last_error")]
     assert all(name in contract for name in NEW)
 

@@ -155,9 +155,9 @@ def test_entry_points_declared_exported_listed(psdr):
     names = [u[0] for u in build.hip_units()]
     units = {u[0]: u for u in build.hip_units()}
     assert units["sdf"][1].endswith("sdf.hip") and units["sdf"][1] in build.HIP_SRCS
-    assert [u[0] for u in build.MESH_FIELD_UNITS] == ["sdf"] and names.index("chamfer") < names.index("sdf") < names.index("pointmesh") and names[-1] == "pointmesh"
+    assert names.count("sdf") == 1 and names.index("chamfer") < names.index("sdf") < names.index("pointmesh") and names[-1] == "pointmesh"
     deps = {os.path.relpath(d, ROOT) for d in units["sdf"][3]}
-    assert {os.path.join("include", "psdr_hip.h"), os.path.join("psdr_jit_amd", "isa_lint.py")} <= deps
+    assert {os.path.join("include", "psdr_hip.h"), os.path.join("psdr_jit_amd", "csrc", "hip", "mesh_pair.h"), os.path.join("psdr_jit_amd", "csrc", "hip", "nn_scan.h"), os.path.join("psdr_jit_amd", "csrc", "hip", "op_common.h"), os.path.join("psdr_jit_amd", "isa_lint.py")} <= deps
     contract = text[text.index("THE STREAM CONTRACT"):text.index("const char *psdr_hip_last_error")]
     assert all(name in contract for name in NEW)
 

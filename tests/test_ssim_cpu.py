@@ -80,9 +80,13 @@ def test_entry_points_declared_exported_listed(psdr):
     for name in ("SSIMLoss", "gaussian_window"):
         assert hasattr(psdr, name)
     units = {u[0]: u for u in build.hip_units()}
-    assert units["ssim"][1].endswith("ssim.hip") and [u[0] for u in build.OPERATOR_UNITS][-1] == "ssim" and len(build.OPERATOR_UNITS) == 7
+    names = [u[0] for u in build.hip_units()]
+    operators = names[names.index("scene") + 1:]          # the operator units follow the render and scene units
+    assert operators == [u[0] for u in build.OPERATOR_UNITS]
+    # ssim is the seventh operator and the last of those on frames: the mesh operators begin right after it
+    assert units["ssim"][1].endswith("ssim.hip") and operators[:7] == ["precond", "adaptive", "denoise", "vdenoise", "subdiv", "msloss", "ssim"] and operators[7] == "meshreg"
     deps = {os.path.relpath(d, ROOT) for d in units["ssim"][3]}
-    assert {os.path.join("include", "psdr_hip.h"), os.path.join("psdr_jit_amd", "isa_lint.py")} <= deps
+    assert {os.path.join("include", "psdr_hip.h"), os.path.join("psdr_jit_amd", "csrc", "hip", "op_common.h"), os.path.join("psdr_jit_amd", "isa_lint.py")} <= deps
     # the stream contract names the handle: rule 3 (creates) and rule 5 (handles that own work frames)
     assert re.search(r"\*\s+3\. Every psdr_hip_\*_create \([^)]*ssim[^)]*\)", text)
     assert re.search(r"\*\s+5\. [^\n]*ssim handle", text)
