@@ -264,7 +264,9 @@ typedef struct psdr_counters {
  *   5. What it does not: a denoise / vdenoise / precond / msloss handle owns work frames and so does an ssim handle, so calls on one such handle must follow each other on one stream or be ordered
  *      by the caller; the same holds for a meshreg handle (it owns the contribution buffers and partial sums of its eval).  subdiv handles are read-only after the create and
  *      may be applied from any number of streams.  The chamfer entry points (psdr_hip_chamfer_nearest, psdr_hip_chamfer_eval) have no handle and no create: their work
- *      arrays (keys, partial) are the caller's, one set per call in flight, and psdr_hip_chamfer_plan touches no device.  The same holds for the point-to-mesh entry points
+ *      arrays (keys, partial) are the caller's, one set per call in flight, and psdr_hip_chamfer_plan touches no device; the grid search beside them is stateless too
+ *      (psdr_hip_chamfer_grid_build, psdr_hip_chamfer_grid_nearest: the grid, work, keys, list and stats are the caller's - a built grid is read-only and may be searched
+ *      from any number of streams that wait for its build; psdr_hip_chamfer_grid_plan touches no device).  The same holds for the point-to-mesh entry points
  *      (psdr_hip_pointmesh_nearest, psdr_hip_pointmesh_eval: records, keys, corners and partial are the caller's; psdr_hip_pointmesh_plan touches no device) and for the
  *      signed-distance entry points (psdr_hip_sdf_winding, psdr_hip_sdf_grad: records, partial and corners are the caller's), and for the isosurface entry points
  *      (psdr_hip_mtet_count, psdr_hip_mtet_emit, psdr_hip_mtet_vertices, psdr_hip_mtet_vertices_adj: mask, base, the cell arrays, scratch and totals are the caller's and
@@ -839,6 +841,54 @@ int psdr_hip_chamfer_nearest(const float *x, int32_t n, const float *y, int32_t 
 int psdr_hip_chamfer_eval(const float *x, int32_t n, const float *y, int32_t m, const int32_t *index_xy, const float *dist2_xy, const int32_t *index_yx, const float *dist2_yx,
                           const int32_t *x_begin, const int32_t *x_list, const int32_t *y_begin, const int32_t *y_list, const float *weights, int32_t squared,
                           double *partial, float *out, float *grad_x, float *grad_y, void *stream);
+
+/* THE SAME NEAREST NEIGHBOURS THROUGH A UNIFORM GRID OVER THE CANDIDATES (csrc/hip/nn_grid.h, entry points in csrc/hip/chamfer.hip; psdr_jit_amd/pointgrid.py; DESIGN.md
+ * section 7q; numpy restatement: tests/pointgrid_ref.py).  Offered beside the scan, which it never replaces.  Stateless like the chamfer entry points above: every array is
+ * the caller's, plain launches (and one clear) on `stream`, no host synchronisation, no copy to the host, no float atomics.  Added under ABI 16: nothing existing changed.
+ *
+ * THE CONTRACT FIXES THE RESULTS, NOT THE SCHEDULE: for finite inputs, index and dist2 of psdr_hip_chamfer_grid_nearest equal psdr_hip_chamfer_nearest's bit for bit - the
+ * lowest j that minimises the float32 d2 of the chamfer section, and that d2.  With non-finite inputs the values are unspecified and every index lies in range.
+ *     the grid     res cells per axis over the bounding box [lo, hi] of y, res = the largest r in [1, 256] with 2 r^3 <= m: a function of m alone, so that nothing is read
+ *                  back to size an array.  Per axis, on the device, once: inv = fl(res / fl(hi - lo)), width = fl(fl(hi - lo) / res); the axis has dim = res cells, or
+ *                  dim = 1 when its extent is zero or inv is not a finite positive number.
+ *     the cell     c(v) = clamp((int) floor(fl(fl(v - lo) inv)), 0, dim - 1), the clamp done in float (a NaN goes to 0).  Every step is monotone non-decreasing in v,
+ *                  so c is.  A query outside the box starts from its clamped cell.  Cell (c0, c1, c2) has the number (c0 res + c1) res + c2.
+ *     the build    the box by integer atomic minimum / maximum on order-preserving keys of the floats; every candidate's cell and a histogram by integer atomicAdd; an
+ *                  exclusive scan over the cells into cell_begin [res^3 + 1]; a scatter of (x, y, z, index) into cell order.  The order inside a cell is not deterministic
+ *                  and nothing depends on it: the lexicographic minimum over (d2, j) does not.
+ *     the planes   plane(a, upper, k), 1 <= k < dim: a float b with c(b) < k - then every candidate of a cell >= k along axis a has a coordinate > b, c being monotone.  It is
+ *                  searched from fl(lo + fl(k width)) downwards by at most 8 steps, the first fl(2^-22 max(|lo|, |hi|)) long and each twice the one before, and is the
+ *                  first b for which c(b) < k was evaluated; when none of them has it, the plane is -infinity: no certificate.
+ *                  plane(a, lower, k), 0 <= k < dim - 1: the mirror image, a float b with c(b) > k, from fl(lo + fl((k + 1) width)) upwards, else +infinity.
+ *     the walk     a query visits the cells at Chebyshev distance s = 0, 1, ... from its own.  After shell s the unvisited cells lie, along some axis a, at >= c_a + s + 1
+ *                  or at <= c_a - s - 1.  A side beyond the grid holds no candidate.  For a side inside it, g = fl(plane - x_a) (upper) or fl(x_a - plane) (lower): when
+ *                  g >= 0, every candidate y of that side has |fl(x_a - y_a)| >= g (rounding is monotone), hence fl((x_a - y_a)^2) >= fl(g g), and d2, a rounded sum of
+ *                  non-negative terms, is not below it.  The query stops when every such side has g >= 0 and fl(g g) > best - strictly: on equality a lower index may
+ *                  wait farther out.  A NaN passes neither comparison, so it never certifies.  No epsilon anywhere.
+ *     the fallback a query not certified after max_shells = res / 4 shells, within [4, 16] (far outside the box, in the hollow of a surface cloud, between two clusters) goes onto a compacted
+ *                  list whose length stays on the device, and a fixed grid of workgroups (fallback_groups x fallback_slices) strides over that length with the scan's
+ *                  inner loop over ALL m candidates in their original order, merging the slices by the integer minimum of the scan's keys.
+ * EVERY LOOP of every kernel has an iteration bound that does not depend on the floats in the data: strides over integer counts, shells <= max_shells, the cells of a
+ * shell, cell ranges clamped into [0, m], at most 8 steps of a plane search.  That is why non-finite input can neither fault nor hang.
+ *
+ * psdr_hip_chamfer_grid_plan(n, m) -> res, max_shells and the lengths of every array, a pure function, callable without a GPU (psdr_jit_amd/pointgrid.py: grid_plan states
+ * it in Python).  Lengths in 32-bit words.  The grid blob: [0, 16) the header - lo[3], inv[3], width[3] as float32, dim[3] as int32, 4 unused; [planes_at, + 6 res) the
+ * planes, plane (a, side, k) at planes_at + (2 a + side) res + k, side 0 = upper; [begin_at, + cells) cell_begin, cells = res^3 + 1; [points_at, + 4 m) the candidates in
+ * cell order, (x, y, z, the bits of the original index); begin_at and points_at are multiples of 4, and the blob must be 16-byte aligned; grid_words = points_at + 4 m.
+ * The build's work array: work_words = 8 + 2 m + ceil(cells / 2048).  The search's arrays: keys uint64 [n], list int32 [n], stats uint64 [2].  The fallback's fixed grid:
+ * fallback_groups x fallback_slices workgroups, slice s holding the candidates [s fallback_slice_len, min(m, (s + 1) fallback_slice_len)).  lanes_per_query: the lanes
+ * that share one query's walk, 8 for n <= 65 536 and 1 beyond; the results and the statistics do not depend on it.
+ * psdr_hip_chamfer_grid_build(y, m, grid, grid_words, work, work_words): fills the grid blob of the candidates y [m, 3] in eight launches; work is free again once they ran.
+ * psdr_hip_chamfer_grid_nearest(x, n, y, m, grid, grid_words, keys, list, index, dist2, stats): index int32 [n], dist2 float32 [n] of the queries x [n, 3] in the grid of
+ * y (THE grid built from this y: the caller's duty; the resolution is taken from m, and whatever is read from the blob is clamped into range, so that a foreign blob gives
+ * wrong numbers, not a fault).  stats[0] = the queries the fallback finished, stats[1] = the (query, candidate) pairs tested - by the walk every candidate of every visited
+ * cell, by the fallback m per listed query.  A clear of stats and three launches: the walk (lanes_per_query lanes per query), the fallback, the unpacking of the keys.
+ * All three are refused with psdr_hip_last_error text before any device call for n or m outside [1, 2^26], a NULL array, and grid_words or work_words below the plan's. */
+int psdr_hip_chamfer_grid_plan(int32_t n, int32_t m, int32_t *res, int32_t *max_shells, int64_t *cells, int64_t *planes_at, int64_t *begin_at, int64_t *points_at,
+                               int64_t *grid_words, int64_t *work_words, int32_t *fallback_groups, int32_t *fallback_slices, int32_t *fallback_slice_len, int32_t *lanes_per_query);
+int psdr_hip_chamfer_grid_build(const float *y, int32_t m, uint32_t *grid, int64_t grid_words, int32_t *work, int64_t work_words, void *stream);
+int psdr_hip_chamfer_grid_nearest(const float *x, int32_t n, const float *y, int32_t m, const uint32_t *grid, int64_t grid_words, uint64_t *keys, int32_t *list,
+                                  int32_t *index, float *dist2, uint64_t *stats, void *stream);
 
 /* THE POINT-TO-MESH DISTANCE - FOR EVERY POINT THE NEAREST FACE, FOR EVERY FACE THE NEAREST POINT, VALUE AND BOTH GRADIENTS (csrc/hip/pointmesh.hip; psdr_jit_amd/pointmesh.py;
  * DESIGN.md section 7l).  What a user fitting a mesh to a scan needs: the distance from the scan's points to the closed triangles themselves, not to a frozen sample of them

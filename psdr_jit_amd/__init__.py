@@ -1478,6 +1478,8 @@ from .ssim import SSIMLoss, gaussian_window  # noqa: E402,F401
 from .meshreg import MeshRegularizer, mesh_topology  # noqa: E402,F401
 # the Chamfer distance between two point sets (exact nearest neighbours, value and both gradients) and points sampled from a mesh's surface (chamfer.py; kernels: csrc/hip/chamfer.hip)
 from .chamfer import ChamferDistance, SurfaceSampler, nearest_points, launch_plan, sample_surface, sampling_csr  # noqa: E402,F401
+# the same nearest neighbours, bit for bit, through a uniform grid over the candidates (pointgrid.py; kernels: csrc/hip/nn_grid.h)
+from .pointgrid import PointGrid, GridPlan, grid_plan  # noqa: E402,F401
 # the point-to-mesh distance: for every point the nearest face, for every face the nearest point, value and both gradients (pointmesh.py; kernels: csrc/hip/pointmesh.hip)
 from .pointmesh import PointMeshDistance, closest_points_on_mesh, launch_plan_pm  # noqa: E402,F401
 # the signed distance to a mesh: the generalized winding number for the sign, the signed distance and its gradients (sdf.py; kernels: csrc/hip/sdf.hip)

@@ -43,7 +43,7 @@ OPERATOR_UNITS = [
     ("msloss", "msloss.hip", "psdr_hip_msloss_*: the multi-scale image loss over a residual pyramid, value and gradient in three launches", ("op_common.h",)),
     ("ssim", "ssim.hip", "psdr_hip_ssim_*: the SSIM loss 1 - mean structural similarity under a Gaussian window, value and image gradient in three launches", ("op_common.h",)),
     ("meshreg", "meshreg.hip", "psdr_hip_meshreg_*: the mesh regularisers (uniform Laplacian, normal consistency, edge length), value and vertex gradient in three launches", ("op_common.h",)),
-    ("chamfer", "chamfer.hip", "psdr_hip_chamfer_*: the Chamfer distance between two point sets, exact nearest neighbours by an LDS-tiled scan over query blocks x candidate slices, value and both gradients", ("nn_scan.h", "op_common.h")),
+    ("chamfer", "chamfer.hip", "psdr_hip_chamfer_*: the Chamfer distance between two point sets, exact nearest neighbours by an LDS-tiled scan over query blocks x candidate slices, value and both gradients; psdr_hip_chamfer_grid_*: the same neighbours through a uniform grid over the candidates", ("nn_scan.h", "nn_grid.h", "op_common.h")),
     ("sdf", "sdf.hip", "psdr_hip_sdf_*: the signed distance to a mesh, the generalized winding number by an LDS-tiled scan over query blocks x face slices for the sign, and the vector-Jacobian product of the signed distance", ("mesh_pair.h", "nn_scan.h", "op_common.h")),
     ("mtet", "mtet.hip", "psdr_hip_mtet_*: isosurface extraction by marching tetrahedra, the crossing masks and face counts of a lattice with their scans, the emit of edges and faces, the vertex positions and their vector-Jacobian product", ("op_common.h",)),
     ("latreg", "latreg.hip", "psdr_hip_latreg_*: the regularisers of a signed distance on a lattice (Eikonal, Laplacian, sign-change cross-entropy), value and gradient by one haloed LDS tile per workgroup in three launches", ("op_common.h",)),

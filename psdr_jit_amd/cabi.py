@@ -20,6 +20,7 @@ SYMBOLS = [
     "psdr_hip_ssim_create", "psdr_hip_ssim_eval", "psdr_hip_ssim_map", "psdr_hip_ssim_destroy",
     "psdr_hip_meshreg_create", "psdr_hip_meshreg_eval", "psdr_hip_meshreg_destroy",
     "psdr_hip_chamfer_plan", "psdr_hip_chamfer_nearest", "psdr_hip_chamfer_eval",
+    "psdr_hip_chamfer_grid_plan", "psdr_hip_chamfer_grid_build", "psdr_hip_chamfer_grid_nearest",
     "psdr_hip_pointmesh_plan", "psdr_hip_pointmesh_nearest", "psdr_hip_pointmesh_eval",
     "psdr_hip_sdf_winding", "psdr_hip_sdf_grad",
     "psdr_hip_mtet_plan", "psdr_hip_mtet_count", "psdr_hip_mtet_emit", "psdr_hip_mtet_vertices", "psdr_hip_mtet_vertices_adj",
@@ -133,6 +134,9 @@ def lib():
         L.psdr_hip_chamfer_plan.argtypes = [C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 4
         L.psdr_hip_chamfer_nearest.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
         L.psdr_hip_chamfer_eval.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 8 + [C.POINTER(C.c_float), C.c_int32] + [C.c_void_p] * 5
+        L.psdr_hip_chamfer_grid_plan.argtypes = [C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 2 + [C.POINTER(C.c_int64)] * 6 + [C.POINTER(C.c_int32)] * 4
+        L.psdr_hip_chamfer_grid_build.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+        L.psdr_hip_chamfer_grid_nearest.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 6
         L.psdr_hip_pointmesh_plan.argtypes = [C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 4
         L.psdr_hip_pointmesh_nearest.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
         L.psdr_hip_pointmesh_eval.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 12 + [C.POINTER(C.c_float), C.c_int32] + [C.c_void_p] * 6

@@ -20,6 +20,9 @@ Written in torch ops, cdist(x, y).min() materialises an N x M matrix and uses th
 backward scatters with float atomics.  Here the scan keeps the queries in registers and streams the candidates through LDS, nothing of size N x M exists, there are no
 float atomics and no host synchronisation, and the same inputs give the same bits.
 
+For large clouds the same neighbours, bit for bit, come from a uniform grid over the candidates instead of the scan (pointgrid.py):
+nearest_points(x, y, search="grid"), nearest_points(x, PointGrid(y)), ChamferDistance(search="grid"), cd(x, y, y_grid=grid).  The default stays "scan".
+
 launch_plan(n, m) is the scan's split into query blocks x candidate slices, which psdr_hip_chamfer_plan states in C; the result does not depend on it.
 SurfaceSampler draws its points on the host (numpy, once per resample) and applies them on the GPU as a sparse matrix through the subdivision operator's kernels.  One GPU
 only: under an initialised torch.distributed group of more than one rank the calls raise."""
@@ -31,6 +34,7 @@ import functools as _functools
 
 import numpy as _np
 
+from . import pointgrid as _pg
 from ._opcommon import MAX_COUNT, NARROW_MAX, TARGET_GROUPS, SCAN_THREADS as THREADS, _ceil_div, _checked_points, _faces_checked, _inverted, _single_gpu, slice_plan  # noqa: F401
 
 TILE = 1024                  # candidates per LDS tile
@@ -69,17 +73,34 @@ def _nearest(x, y, device):
     return index, dist2
 
 
-def nearest_points(x, y):
+def nearest_points(x, y, search="scan", return_stats=False):
     """For every x_i the lowest index j of its nearest y_j and the squared distance: (index int32 [N], dist2 float32 [N]) on the render device, detached, computed on
     torch's current stream without a host synchronisation.  x [N, 3], y [M, 3] on any device and of any float dtype; the distance is the module docstring's d2, bit for
-    bit."""
-    x, y = _checked_points(x, "nearest_points", "x"), _checked_points(y, "nearest_points", "y")
+    bit.
+
+    search: "scan" (the default: the brute-force scan) or "grid": a uniform grid of y is built and searched (pointgrid.py), which returns the same bits.  y may be a
+    PointGrid built earlier; that grid is searched, whatever `search` says.  return_stats=True (grid searches only) adds a third value, an int64 [2] device tensor: the
+    queries that the fallback pass finished, and the (query, candidate) pairs tested."""
+    _pg._checked_search(search, "nearest_points")
+    x = _checked_points(x, "nearest_points", "x")
+    grid = _pg._checked_grid(y, "nearest_points", "y") if isinstance(y, _pg.PointGrid) else None
+    if grid is None:
+        y = _checked_points(y, "nearest_points", "y")
+        if return_stats and search != "grid":
+            raise ValueError("nearest_points: return_stats needs search=\"grid\" or a PointGrid")
     _single_gpu("nearest_points")
     import torch
     from . import _device
     device = _device()
     with torch.cuda.device(device):
-        return _nearest(x.detach().to(device, torch.float32).contiguous(), y.detach().to(device, torch.float32).contiguous(), device)
+        x = x.detach().to(device, torch.float32).contiguous()
+        if grid is None and search == "scan":
+            return _nearest(x, y.detach().to(device, torch.float32).contiguous(), device)
+        if grid is None:
+            grid = _pg.PointGrid(y)
+        _pg._on_render_device(grid, device, "nearest_points", "y")
+        index, dist2, stats = _pg._grid_nearest(x, grid, device, return_stats)
+    return (index, dist2, stats) if return_stats else (index, dist2)
 
 
 @_functools.lru_cache(maxsize=None)
@@ -90,8 +111,8 @@ def _fns():
         """cd(x, y): the forward also produces both gradients, the backward scales them by the incoming scalar"""
 
         @staticmethod
-        def forward(ctx, cd, x, y):
-            out, gx, gy = cd._eval(x, y, True)
+        def forward(ctx, cd, x, y, y_grid):
+            out, gx, gy = cd._eval(x, y, True, y_grid)
             ctx.save_for_backward(gx, gy)
             ctx.like = ((x.device, x.dtype), (y.device, y.dtype))
             return out[0]
@@ -99,7 +120,7 @@ def _fns():
         @staticmethod
         def backward(ctx, g):
             gx, gy = ctx.saved_tensors
-            return None, (g * gx).to(*ctx.like[0]) if ctx.needs_input_grad[1] else None, (g * gy).to(*ctx.like[1]) if ctx.needs_input_grad[2] else None
+            return None, (g * gx).to(*ctx.like[0]) if ctx.needs_input_grad[1] else None, (g * gy).to(*ctx.like[1]) if ctx.needs_input_grad[2] else None, None
 
     class _SampleFn(torch.autograd.Function):
         """p = P v (adjoint False) or P^T g (True); the backward is the other direction"""
@@ -126,17 +147,29 @@ class ChamferDistance:
     current stream without a host synchronisation.  It is differentiable in both arguments: the forward pass produces both gradients, backward only scales them, and they
     return to the inputs' device and dtype.  cd.value_and_grad(x, y) returns (loss, dloss / dx, dloss / dy) detached.  cd.terms holds the detached [2] tensor of the two
     direction means of the last call; cd.nearest its four arrays (index_xy int32 [N], dist2_xy float32 [N], index_yx int32 [M], dist2_yx float32 [M]), None for a
-    direction that is off.  Nothing is kept between calls: the sizes may change from call to call."""
+    direction that is off.  Nothing is kept between calls: the sizes may change from call to call.
 
-    def __init__(self, weights=(1.0, 1.0), squared=True):
+    search = "scan" (the default) or "grid", a plain attribute like the others: with "grid" both directions find their neighbours through a uniform grid (pointgrid.py) -
+    x -> y through a grid of y, y -> x through a grid of x, each built in the call - and every result keeps the bits of the scan.  cd(x, y, y_grid=grid) and
+    cd.value_and_grad(x, y, y_grid=grid) take the x -> y direction through a PointGrid of y built earlier (a fixed target: built once for a whole fit), whatever `search`
+    says; the grid must be the grid of this y."""
+
+    def __init__(self, weights=(1.0, 1.0), squared=True, search="scan"):
         # every argument is checked before a device is looked for
-        self.weights, self.squared = _checked_weights(weights), bool(squared)
+        self.weights, self.squared, self.search = _checked_weights(weights), bool(squared), _pg._checked_search(search, "ChamferDistance")
         self.terms = self.nearest = None
 
-    def _eval(self, x, y, want_grad):
+    def _checked_args(self, x, y, y_grid):
+        x, y = _checked_points(x, "ChamferDistance", "x"), _checked_points(y, "ChamferDistance", "y")
+        _pg._checked_search(self.search, "ChamferDistance")
+        if y_grid is not None and _pg._checked_grid(y_grid, "ChamferDistance", "y_grid").points.shape[0] != y.shape[0]:
+            raise ValueError("ChamferDistance: y_grid holds %d points, y has %d" % (y_grid.points.shape[0], y.shape[0]))
+        return x, y
+
+    def _eval(self, x, y, want_grad, y_grid=None):
         """-> (out [3]: the loss and the two direction means, dloss / dx [N, 3] or None, dloss / dy [M, 3] or None), on the current stream"""
         w = _checked_weights(self.weights)
-        x, y = _checked_points(x, "ChamferDistance", "x"), _checked_points(y, "ChamferDistance", "y")
+        x, y = self._checked_args(x, y, y_grid)
         _single_gpu("ChamferDistance")
         import torch
         from . import cabi, _device, _stream_ptr
@@ -147,11 +180,16 @@ class ChamferDistance:
         with torch.cuda.device(device):
             ixy = dxy = iyx = dyx = xb = xl = yb = yl = None
             if w[0] > 0.0:
-                ixy, dxy = _nearest(x, y, device)
+                if y_grid is not None or self.search == "grid":
+                    if y_grid is not None:
+                        _pg._on_render_device(y_grid, device, "ChamferDistance", "y_grid")
+                    ixy, dxy, _ = _pg._grid_nearest(x, y_grid if y_grid is not None else _pg.PointGrid(y), device)
+                else:
+                    ixy, dxy = _nearest(x, y, device)
                 if want_grad:
                     yb, yl = _inverted(ixy, m)
             if w[1] > 0.0:
-                iyx, dyx = _nearest(y, x, device)
+                iyx, dyx = _pg._grid_nearest(y, _pg.PointGrid(x), device)[:2] if self.search == "grid" else _nearest(y, x, device)
                 if want_grad:
                     xb, xl = _inverted(iyx, n)
             out = torch.empty(3, device=device, dtype=torch.float32)
@@ -162,13 +200,14 @@ class ChamferDistance:
         self.terms, self.nearest = out[1:], (ixy, dxy, iyx, dyx)
         return out, gx, gy
 
-    def __call__(self, x, y):
+    def __call__(self, x, y, y_grid=None):
         """the loss, a 0-d tensor"""
-        return _fns()[0].apply(self, _checked_points(x, "ChamferDistance", "x"), _checked_points(y, "ChamferDistance", "y"))
+        x, y = self._checked_args(x, y, y_grid)
+        return _fns()[0].apply(self, x, y, y_grid)
 
-    def value_and_grad(self, x, y):
+    def value_and_grad(self, x, y, y_grid=None):
         """(loss, dloss / dx, dloss / dy) without autograd, all detached: what a hand-written adjoint needs"""
-        out, gx, gy = self._eval(x, y, True)
+        out, gx, gy = self._eval(x, y, True, y_grid)
         return out[0], gx, gy
 
 

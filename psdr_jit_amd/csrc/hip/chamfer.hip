@@ -18,6 +18,8 @@
 // The evaluation (k_eval, one launch per point set): a lane per point - its own term from (index, dist2), then the points of the other set that chose it through the
 // inverted index (per point the j in ascending order, built by the caller with a stable sort), one store of the gradient, no atomics; the workgroup adds rho(dist2) in a
 // fixed order into its partial sum (in double, so that the mean carries one rounding).  k_finish: one workgroup adds the partial sums of each direction in a fixed order.
+// The grid search (psdr_hip_chamfer_grid_*; kernels and plan: nn_grid.h): the same index and dist2, bit for bit, after testing only the candidates
+// of the cells round a query; offered beside the scan, which stays as it is.
 // No host synchronisation; the same input gives the same bits.  No contraction in this unit (the build's -ffp-contract=off, and the distance is written with __fmul_rn / __fadd_rn).
 #include <cmath>
 #include <cstdint>
@@ -25,6 +27,7 @@
 
 #include "../../../include/psdr_hip.h"
 #include "nn_scan.h"
+#include "nn_grid.h"
 
 namespace {
 
@@ -71,8 +74,7 @@ template <int Q> __global__ void __launch_bounds__(kThreads) k_scan(const float 
                 const int j = base + 4 * g + u;
 #pragma unroll
                 for (int q = 0; q < Q; ++q) {
-                    const float dx = __fsub_rn(qx[q], ax[u]), dy = __fsub_rn(qy[q], ay[u]), dz = __fsub_rn(qz[q], az[u]);
-                    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+                    const float d2 = pair_d2(qx[q], qy[q], qz[q], ax[u], ay[u], az[u]);
                     if (d2 < best[q]) { best[q] = d2; bj[q] = j; }
                 }
             }
@@ -218,6 +220,73 @@ int psdr_hip_chamfer_eval(const float *x, int32_t n, const float *y, int32_t m, 
     if (on_xy || grad_x) k_eval<<<blocks_of<kThreads>(n), kThreads, 0, st>>>(X, squared ? 1 : 0);
     if (on_yx || grad_y) k_eval<<<blocks_of<kThreads>(m), kThreads, 0, st>>>(Y, squared ? 1 : 0);
     k_finish<<<1, kSumThreads, 0, st>>>(partial, bx, by, n, m, weights[0], weights[1], out);
+    return launch_status(who);
+}
+
+int psdr_hip_chamfer_grid_plan(int32_t n, int32_t m, int32_t *res, int32_t *max_shells, int64_t *cells, int64_t *planes_at, int64_t *begin_at, int64_t *points_at,
+                               int64_t *grid_words, int64_t *work_words, int32_t *fallback_groups, int32_t *fallback_slices, int32_t *fallback_slice_len, int32_t *lanes_per_query) {
+    const std::string who = "psdr_hip_chamfer_grid_plan: ";
+    if (!in_range(n)) return psdr::api_fail(who + range_text("n", n));
+    if (!in_range(m)) return psdr::api_fail(who + range_text("m", m));
+    if (!res || !max_shells || !cells || !planes_at || !begin_at || !points_at || !grid_words || !work_words || !fallback_groups || !fallback_slices || !fallback_slice_len || !lanes_per_query)
+        return psdr::api_fail(who + "NULL argument");
+    const grid::GridPlan p = grid::grid_plan_of(n, m);
+    *res = p.res;
+    *max_shells = p.max_shells;
+    *cells = p.cells;
+    *planes_at = p.planes_at;
+    *begin_at = p.begin_at;
+    *points_at = p.points_at;
+    *grid_words = p.grid_words;
+    *work_words = p.work_words;
+    *fallback_groups = p.fb_groups;
+    *fallback_slices = p.fb_slices;
+    *fallback_slice_len = p.fb_slice_len;
+    *lanes_per_query = p.lanes;
+    return 0;
+}
+
+int psdr_hip_chamfer_grid_build(const float *y, int32_t m, uint32_t *grid_blob, int64_t grid_words, int32_t *work, int64_t work_words, void *stream) {
+    const std::string who = "psdr_hip_chamfer_grid_build: ";
+    if (!in_range(m)) return psdr::api_fail(who + range_text("m", m));
+    if (!y || !grid_blob || !work) return psdr::api_fail(who + "NULL argument");
+    const grid::GridPlan p = grid::grid_plan_of(1, m);
+    if (grid_words < p.grid_words) return psdr::api_fail(who + "grid_words = " + std::to_string(grid_words) + ", the plan of m = " + std::to_string(m) + " needs " + std::to_string(p.grid_words));
+    if (work_words < p.work_words) return psdr::api_fail(who + "work_words = " + std::to_string(work_words) + ", the plan of m = " + std::to_string(m) + " needs " + std::to_string(p.work_words));
+    hipStream_t st = (hipStream_t) stream;
+    unsigned int *g = grid_blob, *box_keys = reinterpret_cast<unsigned int *>(work);
+    int *begin = reinterpret_cast<int *>(grid_blob + p.begin_at), *cell_of = work + grid::kWorkHead, *rank = cell_of + m, *sums = rank + m;
+    float4 *points = reinterpret_cast<float4 *>(grid_blob + p.points_at);
+    const int cells = (int) p.cells, by_m = blocks_of<grid::kThreads>(m);
+    grid::k_grid_clear<<<blocks_of<grid::kThreads>(cells), grid::kThreads, 0, st>>>(box_keys, begin, cells);
+    grid::k_grid_box<<<by_m < grid::kBoxGroups ? by_m : grid::kBoxGroups, grid::kThreads, 0, st>>>(y, m, box_keys);
+    grid::k_grid_setup<<<1, grid::kThreads, 0, st>>>(g, box_keys, p.res, (int) p.planes_at);
+    grid::k_grid_count<<<by_m, grid::kThreads, 0, st>>>(y, m, g, p.res, begin, cell_of, rank);
+    grid::k_grid_scan_sums<<<p.scan_groups, grid::kThreads, 0, st>>>(begin, cells, sums);
+    grid::k_grid_scan_top<<<1, 1024, 0, st>>>(sums, p.scan_groups);
+    grid::k_grid_scan_chunk<<<p.scan_groups, grid::kThreads, 0, st>>>(begin, cells, sums);
+    grid::k_grid_scatter<<<by_m, grid::kThreads, 0, st>>>(y, m, cell_of, rank, begin, points);
+    return launch_status(who);
+}
+
+int psdr_hip_chamfer_grid_nearest(const float *x, int32_t n, const float *y, int32_t m, const uint32_t *grid_blob, int64_t grid_words, uint64_t *keys, int32_t *list,
+                                  int32_t *index, float *dist2, uint64_t *stats, void *stream) {
+    const std::string who = "psdr_hip_chamfer_grid_nearest: ";
+    if (!in_range(n)) return psdr::api_fail(who + range_text("n", n));
+    if (!in_range(m)) return psdr::api_fail(who + range_text("m", m));
+    if (!x || !y || !grid_blob || !keys || !list || !index || !dist2 || !stats) return psdr::api_fail(who + "NULL argument");
+    const grid::GridPlan p = grid::grid_plan_of(n, m);
+    if (grid_words < p.grid_words) return psdr::api_fail(who + "grid_words = " + std::to_string(grid_words) + ", the plan of m = " + std::to_string(m) + " needs " + std::to_string(p.grid_words));
+    hipStream_t st = (hipStream_t) stream;
+    unsigned long long *k = reinterpret_cast<unsigned long long *>(keys), *s = reinterpret_cast<unsigned long long *>(stats);
+    const hipError_t e = hipMemsetAsync(s, 0, 2 * sizeof(unsigned long long), st);
+    if (e != hipSuccess) return psdr::api_fail(who + hipGetErrorString(e));
+    const int *begin = reinterpret_cast<const int *>(grid_blob + p.begin_at);
+    const float4 *points = reinterpret_cast<const float4 *>(grid_blob + p.points_at);
+    if (p.lanes == 1) grid::k_grid_search<1><<<blocks_of<grid::kThreads>(n), grid::kThreads, 0, st>>>(x, n, m, grid_blob, p.res, p.max_shells, (int) p.planes_at, begin, points, k, list, s);
+    else grid::k_grid_search<grid::kGroupLanes><<<blocks_of<grid::kThreads / grid::kGroupLanes>(n), grid::kThreads, 0, st>>>(x, n, m, grid_blob, p.res, p.max_shells, (int) p.planes_at, begin, points, k, list, s);
+    grid::k_grid_fallback<<<dim3((unsigned) p.fb_groups, (unsigned) p.fb_slices), grid::kThreads, 0, st>>>(x, n, y, m, p.fb_slice_len, list, s, k);
+    k_unpack<<<blocks_of<kThreads>(n), kThreads, 0, st>>>(k, n, m, index, dist2);
     return launch_status(who);
 }
 

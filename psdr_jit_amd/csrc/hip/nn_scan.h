@@ -49,6 +49,13 @@ __device__ __forceinline__ unsigned long long pack_key(float dist2, int j) { ret
 __device__ __forceinline__ int key_index(unsigned long long key, int m) { return (int) min((unsigned int) (key & 0xffffffffu), (unsigned int) (m - 1)); }
 __device__ __forceinline__ float key_dist2(unsigned long long key) { return __uint_as_float((unsigned int) (key >> 32)); }
 
+// d2 of a (query, candidate) pair of points in the difference form: every operation one float32 rounding, nothing fused, in this order (the chamfer section of
+// include/psdr_hip.h); the one statement of it, which the scan and the grid search (nn_grid.h) both use
+__device__ __forceinline__ float pair_d2(float qx, float qy, float qz, float ax, float ay, float az) {
+    const float dx = __fsub_rn(qx, ax), dy = __fsub_rn(qy, ay), dz = __fsub_rn(qz, az);
+    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+
 // a slice's best for query i: stored where there is one slice, else merged by an integer minimum (associative and commutative: the result does not depend on the order)
 __device__ __forceinline__ void merge_key(unsigned long long *__restrict__ keys, int i, unsigned long long key, int slices) {
     if (slices == 1) keys[i] = key;
