@@ -4,7 +4,11 @@ max_shells) is passed in.  It is the CPU proof of the stopping rule - test_point
 device counts: the queries the fallback finishes and the (query, candidate) pairs tested.
 
 The pairs are well defined by the contract's schedule-free part: a query tests every candidate of every cell of every shell it visits (shells 0 .. s*, s* the first
-shell after which it is certified, or max_shells - 1), and all m candidates once more if the fallback takes it.  The device's walk tests exactly those, whatever the lanes that share a query."""
+shell after which it is certified, or max_shells - 1), and all m candidates once more if the fallback takes it.  The device's walk tests exactly those, whatever the lanes that share a query.
+
+check_build holds a built PointGrid to the restatement's Grid array by array.  The named cases (case, CASES) put the search on each of its paths: res 8 - 11 for the
+first fifteen, shell budgets 4 to 16 for the cavity cases, awkward float32 coordinates and symmetric or hollow clouds for the geometry cases; scan_pass gives the sizes at
+which the build's exclusive scan changes its number of chunks."""
 import numpy as np
 
 import chamfer_ref as cref
@@ -151,6 +155,43 @@ def nearest(x, y, res, max_shells):
     return bj.astype(np.int32), best, stats
 
 
+def _host(t):
+    return np.ascontiguousarray(t.cpu().numpy() if hasattr(t, "cpu") else t)
+
+
+def _first(a, b, what):
+    """a and b are equal entry for entry (floats by their bits), or the first difference is named"""
+    a, b = _host(a).ravel(), _host(b).ravel()
+    assert a.shape == b.shape, "%s: %d entries, expected %d" % (what, a.size, b.size)
+    if a.dtype == F:
+        assert b.dtype == F
+        a, b = a.view(np.uint32), b.view(np.uint32)
+    bad = np.nonzero(a != b)[0]
+    assert bad.size == 0, "%s: %d of %d entries differ, first at %d: %r, expected %r" % (what, bad.size, a.size, bad[0], a[bad[0]], b[bad[0]])
+
+
+def check_build(grid, G, what=""):
+    """A built grid (a PointGrid of the package: box, dims, planes, cell_begin, sorted, points; device tensors or numpy arrays) against the restatement's Grid of the
+    same candidates, array by array and without a tolerance: the box constants and every plane by their bits, infinities included, every entry of cell_begin, and the
+    sorted candidates as far as they are defined - the index column a permutation of 0 .. m - 1, row t the point of its index bit for bit, and inside every cell the
+    same set of indices as the restatement's (the order inside a cell is not defined)."""
+    res, m = G.res, G.m
+    _first(grid.points, G.y, what + " points")
+    _first(grid.box, np.concatenate([G.lo, G.inv, G.width]).astype(F), what + " box (lo, inv, width)")
+    _first(_host(grid.dims).astype(np.int64), np.array(G.dim, np.int64), what + " dims")
+    planes = np.stack([np.stack([G.up[a], G.down[a]]) for a in range(3)]).astype(F)          # plane (axis a, side, k) at (2 a + side) res + k
+    assert planes.shape == (3, 2, res)
+    _first(grid.planes, planes, what + " planes")
+    _first(_host(grid.cell_begin).astype(np.int64), G.begin, what + " cell_begin")
+    rows = _host(grid.sorted).view(np.int32).reshape(-1, 4)
+    assert rows.shape == (m, 4), what
+    index = rows[:, 3].astype(np.int64)
+    _first(np.sort(index), np.arange(m), what + " sorted: the index column is no permutation")
+    _first(rows[:, :3], G.y.view(np.int32)[index], what + " sorted: a row is not the point of its index")
+    cell = np.repeat(np.arange(res ** 3, dtype=np.int64), np.diff(G.begin))                    # the cell of every slot of the sorted order
+    _first(np.sort(cell * m + index), cell * m + G.order, what + " sorted: the indices of a cell")      # (G.order is ascending inside a cell: the sort was stable)
+
+
 # ---- the named cases: (x, y) float32; `plan` is the package's grid_plan and sizes are read from it
 
 def res_changes(plan, top=8):
@@ -170,7 +211,27 @@ def _uniform(n, seed, lo=-1.0, hi=1.0):
 
 
 def _m_for_res(plan, r):
-    return res_changes(plan, r)[-1] if r > 1 else 1
+    """the smallest m with res == r (one bisection; res is monotone in m)"""
+    lo, hi = 0, 1 << 26
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if plan(1, mid).res >= r else (mid, hi)
+    return hi
+
+
+def scan_chunks(plan, m, work_head):
+    """the workgroups of the build's exclusive scan over the cells (2048 cells each), read from the plan: what work_words holds beyond its head (the package's
+    WORK_HEAD) and the two per-candidate arrays.  k_grid_scan_top gives each of its 1024 lanes ceil(chunks / 1024) of them: more than one from 1025 chunks on"""
+    return plan(1, m).work_words - work_head - 2 * m
+
+
+def _unit(r, n):
+    d = r.normal(size=(n, 3))
+    return d / np.sqrt((d * d).sum(1))[:, None]
+
+
+CAVITY_BUDGETS = (4, 5, 8, 12, 16)
+CAVITY_RADIUS = 0.75
 
 
 def case(name, plan):
@@ -244,12 +305,77 @@ def case(name, plan):
     if name == "bunny":                         # the bunny's vertices against a jittered copy
         v, _f = cref.bunny()
         return v, (v + np.random.default_rng(12).normal(0.0, 0.01, v.shape)).astype(F)
+    if name.startswith("cavity_"):              # a full box with a ball cut out of it, the queries in the hollow at every depth: every shell count up to the budget k
+        k = int(name[len("cavity_"):])          # occurs and the deepest queries fall back.  m is the smallest m with max_shells == k: res = 4 k, m = 2 res^3
+        m = _m_for_res(plan, 4 * k)
+        assert plan(1, m).res == 4 * k and plan(1, m).max_shells == k
+        parts, have = [], 0
+        while have < m:                         # (rejection from the one generator until m remain)
+            c = r.uniform(-1.0, 1.0, (m, 3)).astype(F)
+            c = c[(c.astype(np.float64) ** 2).sum(1) >= CAVITY_RADIUS ** 2]
+            parts.append(c)
+            have += len(c)
+        y = np.ascontiguousarray(np.concatenate(parts)[:m])
+        y[0], y[1] = (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)
+        depth = np.linspace(0.0, CAVITY_RADIUS, 300)
+        x = (_unit(r, 300) * (CAVITY_RADIUS - depth)[:, None]).astype(F)
+        return x, y
+    if name in ("tiny", "underflow", "huge"):   # d2 in the denormal range; d2 that underflows to 0 for every pair; d2 near the top of the range (and infinite for far pairs)
+        scale = {"tiny": 1e-20, "underflow": 1e-30, "huge": 3e19}[name]
+        return (_uniform(400, 30).astype(np.float64) * scale).astype(F), (_uniform(m8 + 9, 31).astype(np.float64) * scale).astype(F)
+    if name == "ulps_20":                       # a box 64 ulps wide at 2^20: neighbouring floats
+        return (2.0 ** 20 + 0.125 * r.integers(0, 64, (400, 3))).astype(F), (2.0 ** 20 + 0.125 * r.integers(0, 64, (m8 + 9, 3))).astype(F)
+    if name == "ulps_23":                       # a box 8 ulps wide at 2^23: fewer floats than cells
+        return (2.0 ** 23 + r.integers(0, 8, (400, 3))).astype(F), (2.0 ** 23 + r.integers(0, 8, (m8 + 9, 3))).astype(F)
+    if name == "aniso":                         # extents 10^12 apart
+        scale = np.array([1e6, 1.0, 1e-6])
+        return (_uniform(400, 32).astype(np.float64) * scale).astype(F), (_uniform(m8 + 9, 33).astype(np.float64) * scale).astype(F)
+    if name == "shell":                         # a hollow surface cloud: 16 384 points on the unit sphere, queries on rays from the centre, from the centre itself to
+        y = _unit(r, 16384).astype(F)           # outside the sphere, and five exactly at the centre
+        x = np.concatenate([_unit(r, 200) * np.linspace(0.0, 1.2, 200)[:, None], np.zeros((5, 3))]).astype(F)
+        return x, y
+    if name == "symmetric":                     # the 48 signed permutations of (0.75, 0.5, 0.25), equidistant from the centre (0.875, exact in float32 in any order of
+        import itertools                        # the sum), among 1024 others near the corners of the box [-0.8, 0.8]^3; queries at the centre and within 0.01 of it
+        ring = np.array([[s0 * p[0], s1 * p[1], s2 * p[2]] for p in itertools.permutations((0.75, 0.5, 0.25)) for s0 in (-1, 1) for s1 in (-1, 1) for s2 in (-1, 1)])
+        corner = r.choice([-1.0, 1.0], (m8, 3))
+        others = corner * (0.8 - r.uniform(0.0, 0.04, (m8, 3)))
+        others[:8] = [[s0 * 0.8, s1 * 0.8, s2 * 0.8] for s0 in (-1, 1) for s1 in (-1, 1) for s2 in (-1, 1)]
+        y = np.concatenate([ring, others])[r.permutation(48 + m8)].astype(F)
+        x = np.concatenate([np.zeros((1, 3)), r.uniform(-0.01, 0.01, (69, 3))]).astype(F)
+        return x, np.ascontiguousarray(y)
     raise KeyError(name)
 
 
+def symmetric_ring(y):
+    """the indices of the 48 equidistant candidates of the case "symmetric": those whose coordinates are a signed permutation of (0.75, 0.5, 0.25)"""
+    return np.nonzero((np.sort(np.abs(y), axis=1) == np.array([0.25, 0.5, 0.75], F)).all(1))[0]
+
+
+# ---- the scan's passes: m on both sides of a change of res at which the number of scan chunks (2048 cells each) changes - from one chunk to two at res 13, and from
+# 1024 to 1025 at res 128, where k_grid_scan_top's lanes first take more than one chunk each.  Not in CASES: the definition in numpy takes ten seconds at 4 M points.
+
+SCAN_PASSES = {"12": ("scan_12_13", 13, -1), "13": ("scan_12_13", 13, 0), "127": ("scan_127_128", 128, -1), "128": ("scan_127_128", 128, 0)}
+_SCAN = {}
+
+
+def scan_pass(which, plan):
+    """(x, y, index, dist2, stats) by the restatement for one side of a change of res: 257 uniform queries, m uniform candidates; computed once (do not modify)"""
+    if which not in _SCAN:
+        _name, res, off = SCAN_PASSES[which]
+        m = _m_for_res(plan, res) + off
+        x, y = _uniform(257, 300 + res), _uniform(m, 400 + res - off)
+        p = plan(len(x), m)
+        assert p.res == res + off
+        _SCAN[which] = (x, y) + nearest(x, y, p.res, p.max_shells)
+    return _SCAN[which]
+
+
 WELL_SPREAD = ("uniform", "lattice", "bunny")                # the fallback's share must stay at or under FALLBACK_CAP (and "sampled", which the GPU test draws)
-MUST_FALL_BACK = ("outside_far", "clusters")                # the fallback must take some queries
-CASES = ("uniform", "lattice", "tie_far_low", "tie_near_low", "copies", "identical_y", "same", "planar", "collinear", "far", "outside_near", "outside_far", "clusters", "hub", "bunny")
+CAVITIES = tuple("cavity_%d" % k for k in CAVITY_BUDGETS)
+GEOMETRY = ("tiny", "underflow", "huge", "ulps_20", "ulps_23", "aniso", "shell", "symmetric")
+MUST_FALL_BACK = ("outside_far", "clusters") + CAVITIES + ("shell", "aniso", "underflow", "symmetric")                # the fallback must take some queries
+CASES = ("uniform", "lattice", "tie_far_low", "tie_near_low", "copies", "identical_y", "same", "planar", "collinear", "far", "outside_near", "outside_far", "clusters", "hub",
+         "bunny") + CAVITIES + GEOMETRY
 FALLBACK_CAP = 0.05
 
 _REF = {}

@@ -8,7 +8,19 @@ every shell a query visits and the fallback m per listed query, whatever the lan
 the fallback's share is at most 5 %, on the far-away and between-clusters cases it is above zero.
 
 "An exact copy of the winner in a neighbouring / a far cell" cannot exist in a grid - equal coordinates have equal cells - so the case "copies" holds exact copies at
-other positions of the index order (same cell), and the ties across cells are the equidistant twins of tie_far_low / tie_near_low and the lattice's."""
+other positions of the index order (same cell), and the ties across cells are the equidistant twins of tie_far_low / tie_near_low and the lattice's.
+
+Beyond res 8 - 11 (tests/pointgrid_ref.py has the constructions, tests/test_pointgrid_cpu.py the conditions that keep each case on its path):
+  cavity_4 .. cavity_16   a full box with a ball cut out, queries in the hollow at every depth: shell budgets 4, 5, 8, 12, 16 (res 16 .. 64, m up to 524 288), every shell
+                          count up to the budget, the walk's column decomposition at s >= 5, the hand-over to the list after exactly max_shells shells, and from a
+                          budget of 8 a fallback of 31 - 32 slices of 2 - 16 tiles
+  tiny, underflow, huge, ulps_20, ulps_23, aniso, shell, symmetric
+                          d2 denormal / 0 for every pair / up to 1e37 and infinite beyond; boxes 64 and 8 ulps wide; extents 10^12 apart; a hollow sphere with queries at
+                          its centre; 48 candidates exactly equidistant from a query
+  test_scan_passes        m on both sides of res 12 -> 13 and 127 -> 128: one, two, 1001 and 1025 chunks of the exclusive scan - the last the first size at which a lane
+                          of the scan's second level takes more than one chunk sum - against search="scan" on the device
+Every named case and every scan pass also holds the device's BUILD to the restatement's, array by array (_build: box, dims, every plane, every cell_begin entry, the
+sorted rows and each cell's set of indices)."""
 import numpy as np
 import pytest
 
@@ -34,9 +46,10 @@ def _bits(a):
 
 
 def _grid(psdr, x, y):
-    """(index, dist2, (fallback, pairs)) of the device's grid search"""
+    """(index, dist2, (fallback, pairs)) of the device's grid search; x and y numpy arrays, or tensors that are on the device already"""
     import torch
-    idx, d2, stats = psdr.nearest_points(torch.from_numpy(np.ascontiguousarray(x)), torch.from_numpy(np.ascontiguousarray(y)), search="grid", return_stats=True)
+    tensor = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    idx, d2, stats = psdr.nearest_points(tensor(x), tensor(y), search="grid", return_stats=True)
     assert idx.dtype == torch.int32 and d2.dtype == torch.float32 and stats.dtype == torch.int64 and stats.shape == (2,)
     assert idx.is_cuda and d2.is_cuda and stats.is_cuda and not idx.requires_grad and not d2.requires_grad
     return idx.cpu().numpy(), d2.cpu().numpy(), tuple(int(v) for v in stats.cpu())
@@ -75,6 +88,49 @@ def test_named_cases(psdr, name):
         assert fallback <= pref.FALLBACK_CAP * len(x)
     if name in pref.MUST_FALL_BACK:
         assert fallback > 0
+    _build(psdr, y, stats["grid"], name)
+
+
+def _build(psdr, y, G, what):
+    """the device's build of y against the restatement's, array by array (pointgrid_ref.check_build); -> the PointGrid, its candidates on the device"""
+    import torch
+    grid = psdr.PointGrid(torch.from_numpy(y).cuda() if isinstance(y, np.ndarray) else y)
+    p = grid.plan
+    assert (p.res, grid.num_points) == (G.res, G.m) and grid.box.shape == (9,) and grid.dims.shape == (3,) and grid.planes.shape == (6 * p.res,)
+    pref.check_build(grid, G, what)
+    return grid
+
+
+@pytest.mark.parametrize("which", sorted(pref.SCAN_PASSES, key=int))
+def test_scan_passes(psdr, which):
+    """m on both sides of the change of res 12 -> 13 (one chunk of 2048 cells in the exclusive scan, then two) and of 127 -> 128 (1024 chunks, then 1025: k_grid_scan_top's
+    lanes take two chunk sums each for the first time): the build array by array, then the search against search="scan" on the device, the statistics the restatement's"""
+    import torch
+    from psdr_jit_amd import pointgrid
+    x, y, _idx, _d2, stats = pref.scan_pass(which, psdr.grid_plan)
+    chunks = pref.scan_chunks(psdr.grid_plan, len(y), pointgrid.WORK_HEAD)
+    assert {"12": chunks == 1, "13": chunks == 2, "127": 1 < chunks <= 1024, "128": chunks > 1024}[which]
+    yd = torch.from_numpy(y).cuda()                                           # (the candidates go to the device once)
+    grid = _build(psdr, yd, stats["grid"], "res " + which)
+    xd = torch.from_numpy(x).cuda()
+    want = tuple(t.cpu().numpy() for t in psdr.nearest_points(xd, yd, search="scan"))
+    _same(psdr, xd, yd, "res " + which, want=want, stats=stats)
+    if which == "128":                                                        # a grid built before the call against the one _same built in its call: same bits, same statistics
+        idx, d2, st = psdr.nearest_points(xd, grid, return_stats=True)
+        assert _bits(idx.cpu().numpy()) == _bits(want[0]) and _bits(d2.cpu().numpy()) == _bits(want[1])
+        assert tuple(int(v) for v in st.cpu()) == (stats["fallback"], stats["pairs"])
+
+
+def test_chamfer_distance_at_a_budget_of_eight_shells(psdr):
+    """cavity_8 (m = 65 536, n = 300, max_shells 8), both directions: x -> y walks up to eight shells and falls back through 32 slices of two tiles; y -> x builds a
+    grid of 300 points (res 5) and searches it with 65 536 queries, the most that eight lanes share.  Loss, terms, both gradients and the nearest arrays equal the scan's byte for byte"""
+    import torch
+    x, y = pref.reference("cavity_8", psdr.grid_plan)[:2]
+    assert psdr.grid_plan(len(x), len(y)).max_shells == 8 and psdr.grid_plan(len(y), len(x)).lanes_per_query == psdr.grid_plan(1, 1).lanes_per_query
+    xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
+    scan = _eval(psdr.ChamferDistance((1.0, 0.5)), xd, yd)
+    assert len(scan) == 8
+    assert _eval(psdr.ChamferDistance((1.0, 0.5), search="grid"), xd, yd) == scan
 
 
 def test_both_walks_round_the_switch_of_lanes_per_query(psdr):

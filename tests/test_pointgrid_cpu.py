@@ -2,7 +2,13 @@
 are declared, exported, listed and named in the stream contract under ABI 16, the operator list is what it was and nn_grid.h is among chamfer's dependencies; every entry
 point refuses bad arguments before any device call and the Python surface before it looks for a device; the numpy restatement tests/pointgrid_ref.py - cell function,
 build, shell walk, stopping rule, fallback - equals the definition's scan (chamfer_ref.nearest) bit for bit on every named case, with the fallback's share under the cap
-on the well-spread cases and above zero where it must be; and a property sweep of the planes and of the cell function's monotonicity."""
+on the well-spread cases and above zero where it must be; and a property sweep of the planes and of the cell function's monotonicity.
+
+The cases that the GPU tests rely on for a particular path carry their conditions here (_conditions): the cavity cases reach every shell count up to a budget of 4, 5, 8,
+12 and 16 shells with some queries certified by the last shell and some falling back, through slices of more than one tile from a budget of 8; the geometry cases really
+have denormal, vanishing and near-overflow d2, boxes a few ulps wide, extents 10^12 apart, a hollow sphere, 48 exactly equidistant candidates.  The statistics change
+when the budget is one shell off; the scan-pass sizes sit where the number of scan chunks changes (1 -> 2 and 1024 -> 1025); and check_build, which the GPU tests hold
+the device's build to array by array, refuses each kind of wrong array."""
 import ctypes as C
 import os
 import re
@@ -209,6 +215,152 @@ def test_restatement_is_the_definition(psdr, name):
         assert (d == np.float32(0.0625)).all() and (pref.reference(name, psdr.grid_plan)[2] == 5).all()
     if name in ("planar", "collinear"):
         assert st["grid"].dim.count(1) == (1 if name == "planar" else 2)
+    _conditions(psdr, name, x, y, st)
+
+
+def _conditions(psdr, name, x, y, st):
+    """what each of the cavity and geometry cases is for: a case that stops exercising it fails here, on the CPU, and does not pass silently on the GPU"""
+    from psdr_jit_amd import pointgrid
+    n, m = len(x), len(y)
+    p = psdr.grid_plan(n, m)
+    idx, d2 = pref.reference(name, psdr.grid_plan)[2:4]
+    seen = np.bincount(st["shells"], minlength=p.max_shells + 1)
+    assert st["grid"].res == p.res and len(seen) == p.max_shells + 1
+    if name in pref.CAVITIES:
+        k = int(name.split("_")[1])
+        assert p.max_shells == k and p.res == 4 * k and m == 2 * p.res ** 3 and psdr.grid_plan(n, m - 1).res == p.res - 1
+        assert (seen[2:] > 0).all(), "not every shell count from 2 to %d occurs: %s" % (k, seen.tolist())
+        assert 0 < st["fallback"] < n
+        assert st["fell"].sum() == st["fallback"] and (st["shells"][st["fell"]] == k).all()          # the fallback takes a query after exactly max_shells shells
+        assert ((st["shells"] == k) & ~st["fell"]).any()                                             # ... and not one that the last shell certified
+        if k >= 8:                                   # slices of more than one LDS tile, all 32 of them where the tiles divide evenly: 64, 216 and 512 tiles make
+            assert pointgrid.FALLBACK_SLICES == 32 and p.fallback_slice_len > pointgrid.TILE             # 32 x 2, 31 x 7 (the last slice short) and 32 x 16
+            assert (p.fallback_slices, p.fallback_slice_len // pointgrid.TILE) == {8: (32, 2), 12: (31, 7), 16: (32, 16)}[k]
+        else:
+            assert p.fallback_slices < 32 and p.fallback_slice_len == pointgrid.TILE
+    if name in pref.GEOMETRY and name not in ("shell", "symmetric"):
+        assert (n, m) == (400, pref._m_for_res(psdr.grid_plan, 8) + 9)
+    tiny = np.float32(2.0 ** -126)                                                                   # the smallest normal float32
+    if name == "tiny":
+        assert (d2 > 0).all() and (d2 < tiny).all() and st["fallback"] == 0
+    if name == "underflow":
+        assert (np.abs(y).max(0) > tiny).all() and not d2.any() and not idx.any() and st["fallback"] == n
+        dx = x[:, None, 0] - y[None, :, 0]
+        assert not (dx * dx).any()                                                                   # every pair, not only the winners
+    if name == "huge":
+        assert np.isfinite(d2).all() and d2.max() > 1e37                                             # (the largest float32 is 3.4e38)
+        with np.errstate(over="ignore"):
+            assert np.isinf((x[0] - y) ** 2).any()                                                  # (far pairs overflow: an infinite d2 must never win)
+    if name in ("ulps_20", "ulps_23"):
+        at = np.float32(2.0 ** (20 if name == "ulps_20" else 23))
+        for a in range(3):
+            v = np.unique(y[:, a])
+            assert (np.diff(v) == np.spacing(at)).all() and v[0] == at and len(v) == (64 if name == "ulps_20" else 8)
+        assert st["grid"].dim == [p.res] * 3
+        if name == "ulps_23":
+            assert p.res == 8 and (d2 == 0).sum() > n // 2                                           # as many floats along an axis as cells: 512 distinct points
+    if name == "aniso":
+        extent = st["grid"].hi - st["grid"].lo
+        assert extent[0] / extent[2] > 1e11 and st["fallback"] == n and st["grid"].dim == [p.res] * 3
+    if name == "shell":
+        assert (n, m, p.res, p.max_shells) == (205, 16384, 20, 5)
+        assert (seen[1:] > 0).all() and 0 < st["fallback"] < n and st["fell"][200:].all() and not x[200:].any()
+    if name == "symmetric":
+        ring = pref.symmetric_ring(y)
+        assert n == 70 and len(ring) == 48 and st["fallback"] == n
+        assert not x[0].any() and d2[0] == np.float32(0.875) and idx[0] == ring.min()
+        d = (x[0] - y[ring]) ** 2
+        assert ((d[:, 0] + d[:, 1]) + d[:, 2] == np.float32(0.875)).all()                            # equidistant from the centre, exactly
+        assert np.isin(idx, ring).all() and len(set(idx.tolist())) > 8                               # off the centre the winner moves round the ring
+
+
+def test_the_statistics_pin_the_shell_budget(psdr):
+    """the device's (fallback, pairs) are asked to EQUAL the restatement's at the plan's max_shells: on cavity_8 a budget of one shell less or one more gives other
+    figures, so that equality does pin the budget (and "not certified after exactly max_shells shells goes to the list")"""
+    x, y, _idx, _d2, st = pref.reference("cavity_8", psdr.grid_plan)
+    p = psdr.grid_plan(len(x), len(y))
+    assert p.max_shells == 8
+    at = {8: (st["fallback"], st["pairs"])}
+    for shells in (7, 9):
+        idx, d2, other = pref.nearest(x, y, p.res, shells)
+        at[shells] = (other["fallback"], other["pairs"])
+        assert np.array_equal(idx, pref.reference("cavity_8", psdr.grid_plan)[2])                    # (the results do not depend on the budget)
+    print("cavity_8: (fallback, pairs) at a budget of 7, 8, 9 shells: %s" % [at[k] for k in (7, 8, 9)])
+    assert at[7] != at[8] and at[9] != at[8] and at[7][0] >= at[8][0] >= at[9][0]
+
+
+@pytest.mark.parametrize("which", sorted(pref.SCAN_PASSES, key=int))
+def test_scan_passes_restatement(psdr, which):
+    """m on both sides of the change of res 12 -> 13 (one chunk of 2048 cells, then two) and 127 -> 128 (1024 chunks, then 1025: the first size at which a lane of the
+    second scan level takes more than one chunk sum): the chunk counts read from the plan, and the restatement against the definition - on 16 of the 257 queries at
+    four million candidates, to keep numpy's scan short"""
+    from psdr_jit_amd import pointgrid
+    plan = psdr.grid_plan
+    x, y, idx, d2, st = pref.scan_pass(which, plan)
+    _name, res, off = pref.SCAN_PASSES[which]
+    m = len(y)
+    assert len(x) == 257 and plan(1, m).res == res + off == int(which) and plan(1, m - off).res == res and plan(1, m - off - 1).res == res - 1
+    chunks = pref.scan_chunks(plan, m, pointgrid.WORK_HEAD)
+    assert chunks == -(-((res + off) ** 3 + 1) // pointgrid.SCAN_CHUNK)
+    assert {"12": chunks == 1, "13": chunks == 2, "127": 1 < chunks <= 1024, "128": chunks > 1024}[which], chunks
+    if which == "128":
+        assert m == 4194304 and chunks == 1025
+    take = slice(None) if m < 100000 else slice(0, 257, 17)
+    assert len(x[take]) in (257, 16)
+    want_i, want_d = cref.nearest(x[take], y)
+    assert np.array_equal(idx[take], want_i) and d2[take].tobytes() == want_d.tobytes()
+    print("scan pass at res %s: m = %d, %d chunks, fallback %d, pairs %d, shells %s" % (which, m, chunks, st["fallback"], st["pairs"], np.bincount(st["shells"]).tolist()))
+
+
+class _Built:
+    """what check_build reads of a PointGrid, made from the restatement's Grid: numpy arrays in the blob's layout"""
+
+    def __init__(self, G):
+        self.points = G.y.copy()
+        self.box = np.concatenate([G.lo, G.inv, G.width]).astype(np.float32)
+        self.dims = np.array(G.dim, np.int32)
+        self.planes = np.stack([np.stack([G.up[a], G.down[a]]) for a in range(3)]).astype(np.float32).ravel()
+        self.cell_begin = G.begin.astype(np.int32)
+        order = G.order.copy()
+        for c in np.nonzero(np.diff(G.begin) > 1)[0]:                                                # another order inside every cell: it is not defined
+            order[G.begin[c]:G.begin[c + 1]] = order[G.begin[c]:G.begin[c + 1]][::-1]
+        self.sorted = np.concatenate([G.y[order].view(np.int32), order.astype(np.int32)[:, None]], 1)
+
+
+def test_check_build_tells_a_wrong_array(psdr):
+    """the helper the GPU tests hold the device's build to: it accepts the restatement's own arrays with the cells' contents reordered, and refuses one wrong plane, one
+    wrong infinity, one wrong cell_begin entry in the middle, a wrong constant, a row with another point's coordinates and two indices swapped across cells"""
+    G = pref.reference("uniform", psdr.grid_plan)[4]["grid"]
+    pref.check_build(_Built(G), G)
+    mid = len(G.begin) // 2
+
+    def plane(b):
+        b.planes[G.res + 3] = np.nextafter(b.planes[G.res + 3], np.float32(np.inf))
+
+    def infinity(b):
+        assert b.planes[0] == -np.inf
+        b.planes[0] = G.lo[0]
+
+    def begin(b):
+        b.cell_begin[mid] += 1
+
+    def constant(b):
+        b.box[4] = np.nextafter(b.box[4], np.float32(0))
+
+    def row(b):
+        b.sorted[5, 0] = b.sorted[6, 0] + 1
+
+    def swapped(b):
+        b.sorted[[0, -1]] = b.sorted[[-1, 0]]
+
+    def dims(b):
+        b.dims[1] = 1
+
+    for spoil in (plane, infinity, begin, constant, row, swapped, dims):
+        b = _Built(G)
+        spoil(b)
+        with pytest.raises(AssertionError):
+            pref.check_build(b, G)
 
 
 def test_restatement_on_small_sizes_and_sampled_points(psdr):
